@@ -2,7 +2,7 @@
 """
 Headline benchmark: rendered rays/s at 128 samples/ray, SRN-chairs-shaped 1-view frame (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]            # N=1 directly; N>1 starts its own N ranks
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   # N=1 directly; N>1 starts its own N ranks
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" = one pass of the hot path (NeRFRenderer.forward -> pnr_render: coarse sampling, fused point network,
@@ -10,9 +10,12 @@ alpha compositing) over one frame of synthetic rays already resident in HBM.  Wi
 own contiguous range of the ray batch and one RCCL all_gather per step reassembles the pixels
 (pixel_nerf_multiscale_amd.parallel.ShardedRenderer): --scaling weak = an N x larger batch (per-GPU work fixed),
 --scaling strong = ONE frame cut into N ranges (BASELINE cfg4: one DTU frame over 8 GPUs).  Rank 0 prints ONE JSON
-line with the whole-job throughput, the roofline of the dominant kernel (hipEvents around it, recorded by the
-library on the stream it runs on), a CPU baseline (the oracle restatement timed on this box's host cores, N=1
-only) and, at N=1, a `secondary` list: the other BASELINE.json shapes timed the same way over a few steps.
+line with the whole-job throughput and the roofline of the dominant kernel (hipEvents around it, recorded by the
+library on the stream it runs on during the timed steps).  A plain run does only that.  --full adds what takes work of
+its own: a CPU baseline (the oracle restatement timed on this box's host cores, N=1 only) with the PSNR of the GPU path
+against it, the stand-alone stage kernels' HBM figures and a `secondary` list (the other BASELINE.json shapes timed the
+same way over a few steps) at N=1, and the `strong` record at N>1.  --dump-outputs DIR writes what the last timed step
+returned (the frame's rgb and depth) as DIR/<name>.npy; the inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -222,7 +225,8 @@ def _all_ranks(vals, device, dist, world):
 
 def time_workload(workload, precision, device, steps, warmup, world=1, scaling="weak", dist=None, brackets=1):
     """W warmup + K timed steps of one workload (barrier + synchronize on both sides, max over ranks).  Returns the
-    per-workload record plus (spec, net, rend, rays) for the parity legs.  At world > 1 the record carries what a missed
+    per-workload record, (spec, net, rend, rays) for the parity legs, and what the last timed step of the first bracket
+    returned (rgb, depth of the whole frame, on every rank).  At world > 1 the record carries what a missed
     scaling target would need to be diagnosed: every rank's own dominant-kernel time (rank 0, min, max over ranks) and
     the all_gather timed on its own (events around the collective on the stream it is ordered on)."""
     import ctypes as C
@@ -249,7 +253,7 @@ def time_workload(workload, precision, device, steps, warmup, world=1, scaling="
     t0 = time.perf_counter()
     for i in range(steps):
         rend.point_events = (evs[2 * i].value, evs[2 * i + 1].value)
-        sharded(rays)
+        last = sharded(rays)                # (rgb, depth) of the whole frame; every call returns fresh tensors
     barrier()
     dt_own = time.perf_counter() - t0
     best = 0
@@ -319,7 +323,7 @@ def time_workload(workload, precision, device, steps, warmup, world=1, scaling="
                         "kernel_ms_per_rank": [round(float(x), 4) for x in per_rank[:, 0]],
                         "collective_ms_per_rank": [round(float(x), 4) for x in per_rank[:, 1]],
                         "rays_per_rank": [int(x) for x in per_rank[:, 3]]}
-    return rec, (spec, net, rend, rays)
+    return rec, (spec, net, rend, rays), last
 
 
 def psnr_vs_fp32_path(workload, precision, device, rend, net, rays, n_sample=2048):
@@ -397,6 +401,24 @@ def stage_kernels_hbm(device, n_launch=20):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6 - 4096      # 64 MB of .npy files in all; the 4 KiB leave room for their headers
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: the last timed step's return value, rgb (SB, B, 3) and depth (SB, B), as float32 .npy files.  Above
+    DUMP_MAX_BYTES in all, a fixed strided sample of the B rays (the same rays in every run of the same arguments)."""
+    arrs = {"rgb": last[0], "depth": last[1]}
+    arrs = {k: t.detach().float().cpu().numpy() for k, t in arrs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        B = arrs["depth"].shape[1]
+        idx = np.linspace(0, B - 1, B * DUMP_MAX_BYTES // total).astype(np.int64)
+        arrs = {k: np.ascontiguousarray(a[:, idx]) for k, a in arrs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks from here, BEFORE anything touches
     the GPU in this process (an exec/fork after GPU initialisation is not allowed on the pool), and pass their exit code on."""
@@ -422,12 +444,20 @@ def main():
     ap.add_argument("--scaling", default="auto", choices=["auto", "weak", "strong"],
                     help="N>1: weak = N x the frame's rays, strong = one frame cut into N ranges; auto = strong for the "
                          "DTU workload (BASELINE cfg4 is one frame over 8 GPUs), weak otherwise")
-    ap.add_argument("--cpu-rays", type=int, default=4096, help="rays of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--secondary-steps", type=int, default=3, help="timed steps per secondary workload at N=1 (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the stage kernels' HBM figures and the secondary shapes "
+                         "(N=1), the strong-scaling record (N>1); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (the frame's rgb and depth) as DIR/<name>.npy, float32")
+    ap.add_argument("--cpu-rays", type=int, default=4096, help="--full: rays of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--secondary-steps", type=int, default=3,
+                    help="--full: timed steps per secondary workload at N=1 (0 = skip)")
     ap.add_argument("--strong-steps", type=int, default=5,
-                    help="N>1, headline workload: timed steps of the strong-scaling record (one DTU frame over the N ranks) "
-                         "added to the same JSON line (0 = skip)")
+                    help="--full, N>1, headline workload: timed steps of the strong-scaling record (one DTU frame over the "
+                         "N ranks) added to the same JSON line (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -463,8 +493,10 @@ def main():
             dist.init_process_group("nccl", device_id=device)
     scaling = args.scaling if args.scaling != "auto" else ("strong" if args.workload.startswith("dtu") else "weak")
 
-    rec, (spec, net, rend, rays) = time_workload(args.workload, args.precision, device, args.steps, args.warmup, world,
-                                                 scaling, dist)
+    rec, (spec, net, rend, rays), last = time_workload(args.workload, args.precision, device, args.steps, args.warmup,
+                                                       world, scaling, dist)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     traffic, traffic_src = pmc_traffic(args.workload, args.precision) if world == 1 else (None, None)
     rec["roofline"]["traffic"] = traffic
     rec["roofline"]["traffic_source"] = traffic_src
@@ -497,19 +529,19 @@ def main():
         out["ranks"] = rec["ranks"]
     if one_card:
         out["rehearsal"] = f"{world} ranks on ONE card over gloo (PNR_BENCH_ONE_CARD=1): protocol check, not a measurement"
-    if world > 1 and args.workload == DEFAULT and args.strong_steps > 0:
+    if args.full and world > 1 and args.workload == DEFAULT and args.strong_steps > 0:
         # the OTHER scaling mode in the same N-rank run: BASELINE cfg 4's one DTU frame cut into N ray ranges ("strong";
         # the headline above gives every rank a frame, "weak").  Same protocol, its own record.
         del net, rend, rays
         torch.cuda.empty_cache()
-        r3, (spec3, net3, rend3, rays3) = time_workload(STRONG_WORKLOAD, args.precision, device, args.strong_steps, 1, world,
-                                                        "strong", dist)
+        r3, (spec3, net3, rend3, rays3), _ = time_workload(STRONG_WORKLOAD, args.precision, device, args.strong_steps, 1,
+                                                           world, "strong", dist)
         out["strong"] = {"workload": STRONG_WORKLOAD, "scaling": "strong", "dtype": args.precision, "value": r3["value"],
                          "unit": "rays/s", "steps": args.strong_steps, "ms_per_step": r3["ms_per_step"],
                          "rays_per_step": r3["config"]["rays_per_step"], "rays_per_gpu": r3["config"]["rays_per_gpu"],
                          "roofline_frac": r3["roofline"]["frac"], "ranks": r3["ranks"]}
         del net3, rend3, rays3
-    if rank == 0 and world == 1 and args.cpu_rays > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_rays > 0:
         v, cdt, res, idx, noise = cpu_baseline(spec, args.cpu_rays, rays)
         out["cpu_baseline"] = {"value": v, "unit": "rays/s", "cores": torch.get_num_threads(), "host_cpu_count": os.cpu_count(),
                                "kind": "port",
@@ -522,7 +554,7 @@ def main():
         out["psnr_vs_oracle_db"] = psnr(o[lvl].rgb.cpu(), res[lvl]["rgb"])
         if args.precision != "fp32":
             out["meets_8c"] = bool(out["psnr_vs_oracle_db"] >= PSNR_BOUND_8C_DB)
-    if rank == 0 and world == 1 and args.secondary_steps > 0 and args.workload == DEFAULT:
+    if args.full and rank == 0 and world == 1 and args.secondary_steps > 0 and args.workload == DEFAULT:
         # the other BASELINE.json shapes, driver-timed in the same run: rays/s, dominant-kernel fraction, PSNR of the
         # low-precision kernel vs the fp32 HIP path on a 2048-ray sample of the frame
         del net, rend, rays
@@ -530,7 +562,7 @@ def main():
         sec = []
         for wl, prec in SECONDARY:
             try:
-                r2, (spec2, net2, rend2, rays2) = time_workload(wl, prec, device, args.secondary_steps, 1, brackets=2)
+                r2, (spec2, net2, rend2, rays2), _ = time_workload(wl, prec, device, args.secondary_steps, 1, brackets=2)
             except Exception as ex:        # a secondary shape must not cost the headline line; the row says what happened
                 sec.append({"workload": wl, "dtype": prec, "error": f"{type(ex).__name__}: {ex}"[:300], "meets_8c": False})
                 torch.cuda.empty_cache()
