@@ -331,6 +331,54 @@ int64_t pnr_debug_gemm_grid(int32_t M, int32_t N, int32_t Rn, int32_t rows_per_s
 int32_t pnr_debug_gemm_tile(int32_t block, int32_t M, int32_t N, int32_t Rn, int32_t rows_per_split, int32_t split,
                             int32_t* out3);
 
+/* Test entry into the training path's linear-layer dispatch (csrc/train_f32.hip: gemm, gemm16, grad_w, head_dx) and its bf16
+ * copy kernels: ONE product on caller-owned device buffers, chosen by the production dispatchers from the same shape,
+ * alignment and operand-form predicates, asynchronous on `stream`.  The outputs say what ran: `kernel` the launch site
+ * (PNR_DBG_K_*), `epilogue` the epilogue form of a forward / dX tile kernel (PNR_DBG_EPI_*), and for a weight gradient
+ * `splits` / `rows_per_split` (its row slices) and `reduce` (1: k_reduce_parts, 2: k_reduce_parts2).  Operands by op:
+ *   FWD      y (m, n) = mask(act(x) (m, k) . w (n, k)^T + b) + r;  act = relu if `relu`; mask keeps mk > 0 (fp32) or a bf16 mk16
+ *            with the sign clear and not zero.  mode 0 / 1 / 3: gemm's fp32 / bf16 / bf16x3 products (x, mk fp32);
+ *            mode PNR_DBG_MODE_TAPE16: gemm16 with any of x16, mk16, y16 (the bf16 copy of y; y may then be NULL) and
+ *            w16 (w as bf16 (n, k), leading dimension k).  y16 shares ldy, x16 ldx, mk16 ldm.
+ *   DX       y (m, n) = mask(x (m, k) . w (k, n));  mode 0: w16 = the fp32 (n, k) copy of w^T (gemm's Wt) or NULL;
+ *            mode PNR_DBG_MODE_TAPE16: gemm16 with w16 = bf16 (n, k) copy of w^T, x16, mk16, y16 as for FWD.
+ *   HEAD_DX  y (m, n) = mask(x (m, 4) . w (4, n)), y16 optional: the output head's dX kernel (its own shape limits).
+ *   DW       y (n, k) += g (m, n)^T . act(x) (m, k) (ldy), db (n) += column sums of g; y and/or db may be NULL.  mode = grad_w's
+ *            `half` (0, 1, 3); x16 / g16: the bf16 tape forms.  ws (ws_floats floats): the per-split partials.
+ *   TO_BF16 (y16 (m) = RNE(x)), COLS_TO_BF16 (y16 (m, k) = RNE of the first k columns of x (m, ldx)),
+ *   W_TO_BF16 (y16 (m, k) = RNE(x), and y16t (k, m) = its transpose unless NULL). */
+enum { PNR_DBG_OP_FWD = 0, PNR_DBG_OP_DX = 1, PNR_DBG_OP_HEAD_DX = 2, PNR_DBG_OP_DW = 3, PNR_DBG_OP_TO_BF16 = 4,
+       PNR_DBG_OP_COLS_TO_BF16 = 5, PNR_DBG_OP_W_TO_BF16 = 6 };
+enum { PNR_DBG_MODE_TAPE16 = 16 };
+enum {      /* launch sites of the dispatchers */
+    PNR_DBG_K_NONE = 0,
+    /* gemm */
+    PNR_DBG_K_SGEMM_DMA_WT = 1, PNR_DBG_K_MGEMM_BF16X3 = 2, PNR_DBG_K_MGEMM_BF16 = 3, PNR_DBG_K_SGEMM_DMA = 4,
+    PNR_DBG_K_MGEMM_F32 = 5, PNR_DBG_K_LINEAR_HEAD_512 = 6, PNR_DBG_K_LINEAR_HEAD_256 = 7, PNR_DBG_K_GEMM_F32 = 8,
+    /* gemm16 */
+    PNR_DBG_K_HGEMM_DMA_M16 = 9, PNR_DBG_K_HGEMM_DMA = 10, PNR_DBG_K_MGEMM_BF16_A16_M16 = 11, PNR_DBG_K_MGEMM_BF16_A16 = 12,
+    PNR_DBG_K_MGEMM_BF16_M16 = 13, PNR_DBG_K_MGEMM_BF16_G16 = 14,
+    /* head_dx */
+    PNR_DBG_K_HEAD_DX = 15,
+    /* grad_w */
+    PNR_DBG_K_COL_SUMS16 = 16, PNR_DBG_K_COL_SUMS = 17, PNR_DBG_K_GRAD_W_SKINNY48 = 18, PNR_DBG_K_GRAD_W_SKINNY96 = 19,
+    PNR_DBG_K_MGEMM_BF16X3_DW = 20, PNR_DBG_K_HGEMM_DMA_KT = 21, PNR_DBG_K_MGEMM_BF16_DW_A16B16 = 22,
+    PNR_DBG_K_MGEMM_BF16_DW_B16 = 23, PNR_DBG_K_MGEMM_BF16_DW = 24, PNR_DBG_K_SGEMM_DMA_KT = 25, PNR_DBG_K_MGEMM_F32_DW = 26,
+    PNR_DBG_K_GRAD_W_HEAD = 27, PNR_DBG_K_GRAD_W_F32 = 28,
+    PNR_DBG_K_COUNT = 29
+};
+enum { PNR_DBG_EPI_NONE = 0, PNR_DBG_EPI_LDS = 1, PNR_DBG_EPI_LDS_C16 = 2, PNR_DBG_EPI_REG_VEC = 3, PNR_DBG_EPI_REG_ELEM = 4 };
+typedef struct {
+    int32_t op, mode, relu, n, k, reserved0;
+    int64_t m;
+    const void* x; const void* x16; const void* w; const void* w16; const float* b; const float* r; const void* mk;
+    const void* mk16; void* y; void* y16; void* y16t; const float* g; const void* g16; float* db; float* ws;
+    uint64_t ws_floats;
+    int32_t ldx, ldw, ldr, ldm, ldy, ldg;
+    int32_t kernel, epilogue, splits, rows_per_split, reduce, reserved1;      /* out */
+} pnr_debug_linear_args;
+int32_t pnr_debug_linear(pnr_debug_linear_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,18 @@ class pnr_outputs(C.Structure):
                 ("coarse_weights_stride", C.c_int32), ("fine_weights_stride", C.c_int32)]
 
 
+class pnr_debug_linear_args(C.Structure):
+    _fields_ = [
+        ("op", C.c_int32), ("mode", C.c_int32), ("relu", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("reserved0", C.c_int32),
+        ("m", C.c_int64),
+        ("x", _fp), ("x16", _fp), ("w", _fp), ("w16", _fp), ("b", _fp), ("r", _fp), ("mk", _fp), ("mk16", _fp), ("y", _fp),
+        ("y16", _fp), ("y16t", _fp), ("g", _fp), ("g16", _fp), ("db", _fp), ("ws", _fp), ("ws_floats", C.c_uint64),
+        ("ldx", C.c_int32), ("ldw", C.c_int32), ("ldr", C.c_int32), ("ldm", C.c_int32), ("ldy", C.c_int32), ("ldg", C.c_int32),
+        ("kernel", C.c_int32), ("epilogue", C.c_int32), ("splits", C.c_int32), ("rows_per_split", C.c_int32),
+        ("reduce", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 # every symbol include/pnr.h declares: name -> (restype, argtypes)
 _i32, _i64, _u64, _f = C.c_int32, C.c_int64, C.c_uint64, C.c_float
 PROTOTYPES = {
@@ -118,6 +130,7 @@ PROTOTYPES = {
     "pnr_event_destroy": (_i32, [_fp]),
     "pnr_debug_gemm_grid": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "pnr_debug_gemm_tile": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32)]),
+    "pnr_debug_linear": (_i32, [C.POINTER(pnr_debug_linear_args), _fp]),
 }
 
 

@@ -294,13 +294,18 @@ __device__ __forceinline__ bool mgemm_tile(int M, int N, int Rn, int r_per_split
 // C, the residual R, the relu mask and the bf16 copy move as 16-byte (8-byte) rows instead of single elements: 16 instead of
 // 64 memory instructions per thread and tensor (the element-wise form was 30-45 % of the forward / dX launch).  Same
 // products, same sums.  16-byte accesses need every leading dimension % 4 == 0 and aligned bases; otherwise by element.
+// (host and device: pnr_debug_linear reports the epilogue form a launch takes)
+__host__ __device__ __forceinline__ bool mgemm_vec_ok(const float* bias, const float* R, int ldr, const void* Mk, int ldm, bool m16,
+                                                      const float* C, int ldc, const uint16_t* C16, int ldc16, size_t zs_c) {
+    return ((ldc | ldr | ldm | ldc16) & 3) == 0 && (((uintptr_t)C | (uintptr_t)R | (uintptr_t)bias) & 15) == 0 &&
+           ((uintptr_t)Mk & (m16 ? 7 : 15)) == 0 && ((uintptr_t)C16 & 7) == 0 && (zs_c & 3) == 0;
+}
 template <bool SPLIT, bool M16>
 __device__ __forceinline__ void mgemm_epilogue(const f32x16 (&acc)[2][2], int m0, int n0, int wm, int wn, int lc, int lr, int bz,
                                                const float* __restrict__ bias, const float* R, int ldr, const void* __restrict__ Mk,
                                                int ldm, float* C, int ldc, uint16_t* __restrict__ C16, int ldc16, int M, int N,
                                                size_t zs_c) {
-    const bool vec_ok = ((ldc | ldr | ldm | ldc16) & 3) == 0 && (((uintptr_t)C | (uintptr_t)R | (uintptr_t)bias) & 15) == 0 &&
-                        ((uintptr_t)Mk & (M16 ? 7 : 15)) == 0 && ((uintptr_t)C16 & 7) == 0 && (zs_c & 3) == 0;
+    const bool vec_ok = mgemm_vec_ok(bias, R, ldr, Mk, ldm, M16, C, ldc, C16, ldc16, zs_c);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int m = m0 + wm + 32 * i + lc;
@@ -325,6 +330,8 @@ __device__ __forceinline__ void mgemm_epilogue(const f32x16 (&acc)[2][2], int m0
                     continue;
                 }
                 if (Mk) {
+                    // The two mask forms differ on NaN only: the fp32 mask (m > 0) drops a NaN pre-activation, the bf16 one (sign
+                    // clear and not zero) keeps a positive-sign NaN (tests/test_gpu_train_gemm.py pins both).
                     if (M16) {               // bf16 tape value > 0: sign clear and not zero
                         const uint16_t* mp = (const uint16_t*)Mk + (size_t)m * ldm + n;
                         uint16_t b16[4] = {0, 0, 0, 0};
@@ -374,10 +381,14 @@ __device__ __forceinline__ void mgemm_epilogue(const f32x16 (&acc)[2][2], int m0
 // one 512-byte ROW SEGMENT: the mask, the residual, C and the bf16 copy move as whole 128-byte lines.  Same values, same
 // operations in the same order per element (acc + bias, mask, + residual, round) — bit-identical to mgemm_epilogue.
 // Requires the vector conditions of mgemm_epilogue and N % 4 == 0 (tile_epilogue_ok); every thread of the block calls it.
-__device__ __forceinline__ bool tile_epilogue_ok(const float* bias, const float* R, int ldr, const void* Mk, int ldm, bool m16,
-                                                 const float* C, int ldc, const uint16_t* C16, int ldc16, int N) {
-    return ((ldc | ldr | ldm | ldc16 | N) & 3) == 0 && (((uintptr_t)C | (uintptr_t)R | (uintptr_t)bias) & 15) == 0 &&
-           ((uintptr_t)Mk & (m16 ? 7 : 15)) == 0 && ((uintptr_t)C16 & 7) == 0;
+__host__ __device__ __forceinline__ bool tile_epilogue_ok(const float* bias, const float* R, int ldr, const void* Mk, int ldm,
+                                                          bool m16, const float* C, int ldc, const uint16_t* C16, int ldc16, int N) {
+    return (N & 3) == 0 && mgemm_vec_ok(bias, R, ldr, Mk, ldm, m16, C, ldc, C16, ldc16, 0);
+}
+// tile_epilogue_lds's form for a result that only leaves as its bf16 copy (eight columns per lane)
+__host__ __device__ __forceinline__ bool tile_epilogue_c16_only(bool m16, const float* R, const void* Mk, int ldm, const float* C,
+                                                                const uint16_t* C16, int ldc16, int N) {
+    return (m16 || !Mk) && !C && !R && C16 && (N & 7) == 0 && (((uintptr_t)C16 | (uintptr_t)Mk) & 15) == 0 && ((ldc16 | ldm) & 7) == 0;
 }
 template <bool M16>
 __device__ __forceinline__ void tile_epilogue_lds(const f32x16 (&acc)[2][2], char* tile, int t, int m0, int n0, int wm, int wn, int lc,
@@ -398,7 +409,7 @@ __device__ __forceinline__ void tile_epilogue_lds(const f32x16 (&acc)[2][2], cha
                     make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
             }
     __syncthreads();
-    if ((M16 || !Mk) && !C && !R && C16 && (N & 7) == 0 && (((uintptr_t)C16 | (uintptr_t)Mk) & 15) == 0 && ((ldc16 | ldm) & 7) == 0) {
+    if (tile_epilogue_c16_only(M16, R, Mk, ldm, C, C16, ldc16, N)) {
         // only the bf16 copy leaves (fc_0-type forward, dh of the backward): a lane takes EIGHT columns, so the copy and the
         // mask move as 16-byte pieces (8-byte accesses run at 0.54-0.70x the 16-byte rate: MI355X_MICROARCH.md), a quarter-wave
         // per 256-byte row segment.  Same operations per element.
@@ -1976,15 +1987,30 @@ static inline bool al16(const void* p, int ld) { return ((uintptr_t)p & 15) == 0
 // dX = dY W) — the GEMM then runs on k_hgemm_dma.
 struct G16 { const uint16_t* X16; const uint16_t* Mk16; uint16_t* Y16; const uint16_t* W16 = nullptr; };
 
+// What a dispatcher below launched (gemm16 / gemm / head_dx / grad_w), for pnr_debug_linear only: production calls pass no record,
+// so the dispatch costs one pointer test per launch.  id: PNR_DBG_K_* of the launch site; epi: PNR_DBG_EPI_* of a tile kernel's
+// epilogue (evaluated with the kernel's own arguments); splits / rows / reduce: the row slicing of a weight gradient.
+struct DbgSite { int id, epi, splits, rows, reduce; };
+#define PNR_SITE(d, k) do { if (d) (d)->id = (k); } while (0)
+static int epilogue_form(bool lds_kernel, const float* bias, const float* R, int ldr, const void* Mk, int ldm, bool m16, const float* C,
+                         int ldc, const uint16_t* C16, int ldc16, int N) {
+    if (lds_kernel && tile_epilogue_ok(bias, R, ldr, Mk, ldm, m16, C, ldc, C16, ldc16, N))
+        return tile_epilogue_c16_only(m16, R, Mk, ldm, C, C16, ldc16, N) ? PNR_DBG_EPI_LDS_C16 : PNR_DBG_EPI_LDS;
+    return mgemm_vec_ok(bias, R, ldr, Mk, ldm, m16, C, ldc, C16, ldc16, 0) ? PNR_DBG_EPI_REG_VEC : PNR_DBG_EPI_REG_ELEM;
+}
+#define PNR_EPI(d, ...) do { if (d) (d)->epi = epilogue_form(__VA_ARGS__); } while (0)
+
 template <bool RELU_X, bool TRANS_W>
 static int32_t gemm16(const G16& g, const float* X, int ldx, const float* W, int ldw, const float* b, const float* R, int ldr,
-                      const float* Mk, int ldm, float* Y, int ldy, int64_t M, int N, int K, hipStream_t s) {
+                      const float* Mk, int ldm, float* Y, int ldy, int64_t M, int N, int K, hipStream_t s, DbgSite* dbg = nullptr) {
     if (M == 0) return PNR_OK;
     if (!(N >= 32 && K >= 32 && K % 32 == 0 && N % 4 == 0 && al16(W, ldw))) return PNR_E_UNSUPPORTED;
     const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
     if (g.X16 && g.W16 && K % 64 == 0 && ldx % 8 == 0 && ((uintptr_t)g.X16 & 15) == 0 && ((uintptr_t)g.W16 & 15) == 0 && !(Mk && !g.Mk16)) {
         // both operands bf16 and row-contiguous in the reduction index: the LDS-DMA k-loop (W16 is (N, K), leading dimension K)
         const void* Mp16 = (const void*)g.Mk16;
+        PNR_SITE(dbg, g.Mk16 ? PNR_DBG_K_HGEMM_DMA_M16 : PNR_DBG_K_HGEMM_DMA);
+        PNR_EPI(dbg, true, b, R, ldr, Mp16, ldm, g.Mk16 != nullptr, Y, ldy, g.Y16, ldy, N);
         if (g.Mk16)
             hipLaunchKernelGGL((k_hgemm_dma<RELU_X, true>), grid, dim3(256), 0, s, g.X16, ldx, g.W16, K, b, R, ldr, Mp16, ldm, Y, ldy,
                                g.Y16, ldy, (int)M, N, K);
@@ -2000,6 +2026,9 @@ static int32_t gemm16(const G16& g, const float* X, int ldx, const float* W, int
     hipLaunchKernelGGL((k_mgemm_bf16<true, !TRANS_W, RELU_X, false, false, A16, false, M16>), grid, dim3(256), 0, s, Xp, ldx, \
                        (const void*)W, ldw, b, R, ldr, Mp, ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0, (size_t)0,    \
                        (size_t)0, g.Y16, ldy)
+    PNR_SITE(dbg, g.X16 ? (g.Mk16 ? PNR_DBG_K_MGEMM_BF16_A16_M16 : PNR_DBG_K_MGEMM_BF16_A16)
+                        : (g.Mk16 ? PNR_DBG_K_MGEMM_BF16_M16 : PNR_DBG_K_MGEMM_BF16_G16));
+    PNR_EPI(dbg, false, b, R, ldr, Mp, ldm, g.Mk16 != nullptr, Y, ldy, g.Y16, ldy, N);
     if (g.X16 && g.Mk16) PNR_G16_LAUNCH(true, true);
     else if (g.X16) PNR_G16_LAUNCH(true, false);
     else if (g.Mk16) PNR_G16_LAUNCH(false, true);
@@ -2013,16 +2042,20 @@ static int32_t gemm16(const G16& g, const float* X, int ldx, const float* W, int
 template <bool RELU_X, bool TRANS_W>
 static int32_t gemm(const float* X, int ldx, const float* W, int ldw, const float* b, const float* R, int ldr,
                     const float* Mk, int ldm, float* Y, int ldy, int64_t M, int N, int K, hipStream_t s, int half = 0,
-                    const float* Wt = nullptr) {
+                    const float* Wt = nullptr, DbgSite* dbg = nullptr) {
     if (M == 0) return PNR_OK;
     if (TRANS_W && Wt && !half && N >= 32 && K >= 64 && K % 16 == 0 && al16(X, ldx) && ((uintptr_t)Wt & 15) == 0) {
         const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
+        PNR_SITE(dbg, PNR_DBG_K_SGEMM_DMA_WT);
+        PNR_EPI(dbg, true, b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N);
         hipLaunchKernelGGL((k_sgemm_dma<RELU_X>), grid, dim3(256), 0, s, X, ldx, Wt, K, b, R, ldr, Mk, ldm, Y, ldy, (int)M, N, K);
         PNR_LAUNCH_CHECK();
         return PNR_OK;
     }
     if (half && N >= 32 && K >= 32 && K % 32 == 0 && N % 4 == 0 && al16(X, ldx) && al16(W, ldw)) {
         const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
+        PNR_SITE(dbg, half == 3 ? PNR_DBG_K_MGEMM_BF16X3 : PNR_DBG_K_MGEMM_BF16);
+        PNR_EPI(dbg, false, b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N);
         if (half == 3)
             hipLaunchKernelGGL((k_mgemm_bf16x3<true, !TRANS_W, RELU_X, false, false>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R,
                                ldr, Mk, ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0);
@@ -2035,12 +2068,16 @@ static int32_t gemm(const float* X, int ldx, const float* W, int ldw, const floa
     if (!TRANS_W && !half && N >= 32 && K >= 64 && K % 16 == 0 && al16(X, ldx) && al16(W, ldw)) {
         // fp32 products, activations x weights as stored: both operands row-contiguous in the reduction index -> LDS-DMA k-loop
         const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
+        PNR_SITE(dbg, PNR_DBG_K_SGEMM_DMA);
+        PNR_EPI(dbg, true, b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N);
         hipLaunchKernelGGL((k_sgemm_dma<RELU_X>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R, ldr, Mk, ldm, Y, ldy, (int)M, N, K);
         PNR_LAUNCH_CHECK();
         return PNR_OK;
     }
     if (N >= 32 && K >= 16) {       // MFMA tile kernel; the skinny heads (N = 4, K = 4) stay on the FMA kernel
         const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
+        PNR_SITE(dbg, PNR_DBG_K_MGEMM_F32);
+        PNR_EPI(dbg, false, b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N);
         hipLaunchKernelGGL((k_mgemm_f32<true, !TRANS_W, RELU_X, false, false>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R, ldr,
                            Mk, ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0, vec_flags(X, ldx, W, ldw));
         PNR_LAUNCH_CHECK();
@@ -2050,6 +2087,7 @@ static int32_t gemm(const float* X, int ldx, const float* W, int ldw, const floa
         // the output head (lin_out, d_out = 4)
         int64_t blocks = (M + 15) / 16;
         if (blocks > 2048) blocks = 2048;
+        PNR_SITE(dbg, K == 512 ? PNR_DBG_K_LINEAR_HEAD_512 : PNR_DBG_K_LINEAR_HEAD_256);
         if (K == 512)
             hipLaunchKernelGGL((k_linear_head<RELU_X, 2>), dim3((unsigned)blocks), dim3(256), 0, s, X, ldx, W, ldw, b, Y, ldy, (int)M);
         else
@@ -2058,6 +2096,7 @@ static int32_t gemm(const float* X, int ldx, const float* W, int ldw, const floa
         return PNR_OK;
     }
     dim3 grid((unsigned)((M + 63) / 64), (N + 63) / 64);
+    PNR_SITE(dbg, PNR_DBG_K_GEMM_F32);
     hipLaunchKernelGGL((k_gemm_f32<RELU_X, TRANS_W>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R, ldr, Mk, ldm, Y,
                        ldy, (int)M, N, K);
     PNR_LAUNCH_CHECK();
@@ -2101,11 +2140,12 @@ static bool head_dx_ok(const float* X, const float* W, int ldw, const float* Mk,
            al16(Y, ldy) && (!Mk || al16(Mk, ldm));
 }
 static int32_t head_dx(const float* X, const float* W, int ldw, const float* Mk, int ldm, float* Y, int ldy, uint16_t* Y16, int64_t P,
-                       int N, hipStream_t s) {
+                       int N, hipStream_t s, DbgSite* dbg = nullptr) {
     if (P == 0) return PNR_OK;
     const int per_row = N >> 2;
     int64_t blocks = (P * per_row + 255) / 256;
     if (blocks > 8192) blocks = 8192;
+    PNR_SITE(dbg, PNR_DBG_K_HEAD_DX);
     hipLaunchKernelGGL(k_head_dx, dim3((unsigned)blocks), dim3(256), 0, s, (const float4*)X, W, ldw, Mk, ldm, Y, ldy, Y16, ldy, P, N);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
@@ -2175,7 +2215,8 @@ __global__ void k_reduce_parts2(const float* __restrict__ pw, const float* __res
 template <bool RELU_X>
 static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* dW, int ldw, float* db, int64_t M,
                       int N, int K, hipStream_t s, int half, const DetWs& ws, const uint16_t* X16 = nullptr,
-                      const uint16_t* dY16 = nullptr /* the gradient stream's bf16 copy (with X16): read instead of dY */) {
+                      const uint16_t* dY16 = nullptr /* the gradient stream's bf16 copy (with X16): read instead of dY */,
+                      DbgSite* dbg = nullptr) {
     if ((!dW && !db) || M == 0) return PNR_OK;
     const size_t zs_w = (size_t)N * K, zs_b = (size_t)N;
     // rows per split: the kernel's natural slice, enlarged until the splits fit the scratch
@@ -2194,8 +2235,10 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
         return (int)nz;
     };
     float* pw = ws.part;                 // (nz, N, K)
+    int rows = 0, nz = 0;
     auto finish = [&](int nz) -> int32_t {
         float* pb = pw + (size_t)nz * zs_w;
+        if (dbg) { dbg->splits = nz; dbg->rows = rows; dbg->reduce = dW && db ? 2 : 1; }
         if (dW && db) {          // one launch for the weight and its bias (60 -> 40 launches per training step)
             hipLaunchKernelGGL(k_reduce_parts2, dim3((unsigned)((zs_w + zs_b + 255) / 256)), dim3(256), 0, s, pw, pb, nz, zs_w, zs_b, dW, ldw, K, db);
             PNR_LAUNCH_CHECK();
@@ -2212,10 +2255,10 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
         return PNR_OK;
     };
     if (!ws.part || ws.floats < zs_w + zs_b) return PNR_E_WORKSPACE;
-    int rows, nz;
     if (!dW) {
         nz = splits_for(2048, &rows);
         float* pb = pw + (size_t)nz * zs_w;
+        PNR_SITE(dbg, dY16 ? PNR_DBG_K_COL_SUMS16 : PNR_DBG_K_COL_SUMS);
         if (dY16) hipLaunchKernelGGL(k_col_sums16, dim3((N + 255) / 256, (unsigned)nz), dim3(256), 0, s, dY16, ldy, pb, (int)M, N, rows, zs_b);
         else hipLaunchKernelGGL(k_col_sums, dim3((N + 255) / 256, (unsigned)nz), dim3(256), 0, s, dY, ldy, pb, (int)M, N, rows, zs_b);
         PNR_LAUNCH_CHECK();
@@ -2239,6 +2282,7 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
         nz = (int)((M + rows - 1) / rows);
         float* pbs = pw + (size_t)nz * zs_w;
         const dim3 grid((N + 255) / 256, (unsigned)nz);
+        PNR_SITE(dbg, K <= 48 ? PNR_DBG_K_GRAD_W_SKINNY48 : PNR_DBG_K_GRAD_W_SKINNY96);
         if (K <= 48) hipLaunchKernelGGL((k_grad_w_skinny<48>), grid, dim3(256), 0, s, dY, ldy, X, ldx, pw, K, db ? pbs : nullptr, (int)M, N, K, rows, zs_w, zs_b);
         else hipLaunchKernelGGL((k_grad_w_skinny<96>), grid, dim3(256), 0, s, dY, ldy, X, ldx, pw, K, db ? pbs : nullptr, (int)M, N, K, rows, zs_w, zs_b);
         PNR_LAUNCH_CHECK();
@@ -2263,37 +2307,47 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
     if (mfma_shape) {
         // dW = A B with A(n, r = m) = dY[m][n] and B(r = m, k) = act(X[m][k]): both stored reduction-major
         const dim3 grid = mgemm_grid(nz, ((N + 127) / 128) * ((K + 127) / 128));
-        if (use_half && half == 3)
+        if (use_half && half == 3) {
+            PNR_SITE(dbg, PNR_DBG_K_MGEMM_BF16X3_DW);
             hipLaunchKernelGGL((k_mgemm_bf16x3<false, false, false, RELU_X, true>), grid, dim3(256), 0, s, dY, ldy, X, ldx,
                                (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk,
                                N, K, (int)M, rows, zs_w, zs_b);
-        else if (dma_kt && rows % 64 == 0)
+        } else if (dma_kt && rows % 64 == 0) {
+            PNR_SITE(dbg, PNR_DBG_K_HGEMM_DMA_KT);
             hipLaunchKernelGGL((k_hgemm_dma_kt<RELU_X>), grid, dim3(256), 0, s, dY16, ldy, X16, ldx, pw, K, pbk, N, K, (int)M, rows,
                                zs_w, zs_b);
-        else if (use_half && X16 && dY16)
+        } else if (use_half && X16 && dY16) {
+            PNR_SITE(dbg, PNR_DBG_K_MGEMM_BF16_DW_A16B16);
             hipLaunchKernelGGL((k_mgemm_bf16<false, false, false, RELU_X, true, true, true, false>), grid, dim3(256), 0, s,
                                (const void*)dY16, ldy, (const void*)X16, ldx, (const float*)nullptr, (const float*)nullptr, 0,
                                (const void*)nullptr, 0, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
-        else if (use_half && X16)
+        } else if (use_half && X16) {
+            PNR_SITE(dbg, PNR_DBG_K_MGEMM_BF16_DW_B16);
             hipLaunchKernelGGL((k_mgemm_bf16<false, false, false, RELU_X, true, false, true, false>), grid, dim3(256), 0, s,
                                (const void*)dY, ldy, (const void*)X16, ldx, (const float*)nullptr, (const float*)nullptr, 0,
                                (const void*)nullptr, 0, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
-        else if (use_half)
+        } else if (use_half) {
+            PNR_SITE(dbg, PNR_DBG_K_MGEMM_BF16_DW);
             hipLaunchKernelGGL((k_mgemm_bf16<false, false, false, RELU_X, true>), grid, dim3(256), 0, s, dY, ldy, X, ldx,
                                (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk,
                                N, K, (int)M, rows, zs_w, zs_b);
-        else if (dma32 && rows % 16 == 0)
+        } else if (dma32 && rows % 16 == 0) {
+            PNR_SITE(dbg, PNR_DBG_K_SGEMM_DMA_KT);
             hipLaunchKernelGGL((k_sgemm_dma_kt<RELU_X>), grid, dim3(256), 0, s, dY, ldy, X, ldx, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
-        else
+        } else {
+            PNR_SITE(dbg, PNR_DBG_K_MGEMM_F32_DW);
             hipLaunchKernelGGL((k_mgemm_f32<false, false, false, RELU_X, true>), grid, dim3(256), 0, s, dY, ldy, X, ldx,
                                (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk,
                                N, K, (int)M, rows, vec_flags(dY, ldy, X, ldx), zs_w, zs_b);
+        }
     } else if (head) {
         dim3 grid((K + 127) / 128, (unsigned)nz);
+        PNR_SITE(dbg, PNR_DBG_K_GRAD_W_HEAD);
         hipLaunchKernelGGL((k_grad_w_head<RELU_X>), grid, dim3(256), 0, s, (const float4*)dY, X, ldx, pw, K, pbk, (int)M, K, rows,
                            zs_w, zs_b);
     } else {
         dim3 grid((N + 63) / 64, (K + 63) / 64, (unsigned)nz);
+        PNR_SITE(dbg, PNR_DBG_K_GRAD_W_F32);
         hipLaunchKernelGGL((k_grad_w_f32<RELU_X>), grid, dim3(256), 0, s, dY, ldy, X, ldx, pw, K, pbk, (int)M, N, K, rows, zs_w, zs_b);
     }
     PNR_LAUNCH_CHECK();
@@ -2638,6 +2692,81 @@ extern "C" int32_t pnr_debug_gemm_tile(int32_t block, int32_t M, int32_t N, int3
                           : mgemm_tile_of<false>(block, M, N, Rn, rows_per_split, bx, by, bz);
     out3[0] = bx; out3[1] = by; out3[2] = bz;
     return ok ? 1 : 0;
+}
+
+// One product through the production dispatchers (include/pnr.h: pnr_debug_linear_args); tests/test_gpu_train_gemm.py.
+template <bool RELU>
+static int32_t debug_linear(pnr_debug_linear_args* a, hipStream_t s, DbgSite* d) {
+    const int64_t M = a->m;
+    const int N = a->n, K = a->k;
+    const float* X = (const float*)a->x;
+    const float* W = (const float*)a->w;
+    const float* Mk = (const float*)a->mk;
+    float* Y = (float*)a->y;
+    const G16 g{(const uint16_t*)a->x16, (const uint16_t*)a->mk16, (uint16_t*)a->y16, (const uint16_t*)a->w16};
+    switch (a->op) {
+    case PNR_DBG_OP_FWD:
+        if (a->mode == PNR_DBG_MODE_TAPE16)
+            return gemm16<RELU, false>(g, X, a->ldx, W, a->ldw, a->b, a->r, a->ldr, Mk, a->ldm, Y, a->ldy, M, N, K, s, d);
+        if (a->mode != 0 && a->mode != 1 && a->mode != 3) return PNR_E_UNSUPPORTED;
+        return gemm<RELU, false>(X, a->ldx, W, a->ldw, a->b, a->r, a->ldr, Mk, a->ldm, Y, a->ldy, M, N, K, s, a->mode, nullptr, d);
+    case PNR_DBG_OP_DX:
+        if (a->mode == PNR_DBG_MODE_TAPE16)
+            return gemm16<RELU, true>(g, X, a->ldx, W, a->ldw, a->b, a->r, a->ldr, Mk, a->ldm, Y, a->ldy, M, N, K, s, d);
+        if (a->mode != 0 && a->mode != 1 && a->mode != 3) return PNR_E_UNSUPPORTED;
+        return gemm<RELU, true>(X, a->ldx, W, a->ldw, a->b, a->r, a->ldr, Mk, a->ldm, Y, a->ldy, M, N, K, s, a->mode,
+                                (const float*)a->w16, d);
+    case PNR_DBG_OP_HEAD_DX:
+        if (!head_dx_ok(X, W, a->ldw, Mk, a->ldm, Y, a->ldy, N, K)) return PNR_E_UNSUPPORTED;
+        return head_dx(X, W, a->ldw, Mk, a->ldm, Y, a->ldy, (uint16_t*)a->y16, M, N, s, d);
+    case PNR_DBG_OP_DW:
+        return grad_w<RELU>(a->g, a->ldg, X, a->ldx, Y, a->ldy, a->db, M, N, K, s, a->mode, DetWs{a->ws, a->ws_floats},
+                            (const uint16_t*)a->x16, (const uint16_t*)a->g16, d);
+    }
+    return PNR_E_UNSUPPORTED;
+}
+
+extern "C" int32_t pnr_debug_linear(pnr_debug_linear_args* a, void* stream) {
+    if (!a) return PNR_E_NULL;
+    a->kernel = PNR_DBG_K_NONE;
+    a->epilogue = PNR_DBG_EPI_NONE;
+    a->splits = a->rows_per_split = a->reduce = 0;
+    if (a->m < 0 || a->m > 0x7fffffff || a->n < 0 || a->k < 0) return PNR_E_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t M = a->m;
+    switch (a->op) {
+    case PNR_DBG_OP_TO_BF16:
+        if (!a->x || !a->y16) return PNR_E_NULL;
+        if (M > 0) hipLaunchKernelGGL(k_to_bf16, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const float*)a->x, M, (uint16_t*)a->y16);
+        PNR_LAUNCH_CHECK();
+        return PNR_OK;
+    case PNR_DBG_OP_COLS_TO_BF16: {
+        if (!a->x || !a->y16) return PNR_E_NULL;
+        if (a->k % 2 || a->ldx % 2 || a->k > a->ldx || ((uintptr_t)a->x & 7) || ((uintptr_t)a->y16 & 3)) return PNR_E_ALIGN;
+        const int64_t n2 = M * (a->k / 2);
+        if (n2 > 0) hipLaunchKernelGGL(k_cols_to_bf16, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, (const float*)a->x, M, a->ldx, a->k,
+                                       (uint16_t*)a->y16);
+        PNR_LAUNCH_CHECK();
+        return PNR_OK;
+    }
+    case PNR_DBG_OP_W_TO_BF16: {
+        if (!a->x || !a->y16) return PNR_E_NULL;
+        W16Table tb{};
+        tb.w[0] = (const float*)a->x; tb.wb[0] = (uint16_t*)a->y16; tb.wt[0] = (uint16_t*)a->y16t;
+        tb.rows[0] = (int)M; tb.cols[0] = a->k; tb.n = 1;
+        if (M * a->k > 0) hipLaunchKernelGGL(k_w_to_bf16, dim3((unsigned)((M * a->k + 255) / 256), 1u), dim3(256), 0, s, tb);
+        PNR_LAUNCH_CHECK();
+        return PNR_OK;
+    }
+    }
+    DbgSite d{};
+    const int32_t rc = a->relu ? debug_linear<true>(a, s, &d) : debug_linear<false>(a, s, &d);
+    a->kernel = d.id;
+    a->epilogue = d.epi;
+    a->splits = d.splits;
+    a->rows_per_split = d.rows;
+    a->reduce = d.reduce;
+    return rc;
 }
 
 extern "C" int32_t pnr_composite_bwd(const float* rays, const float* z, const float* rgbsigma, int64_t n_rays,
