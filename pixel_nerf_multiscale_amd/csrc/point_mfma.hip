@@ -263,14 +263,6 @@ __global__ void k_pack_mlp(pnr_mlp m, Layout y, char* __restrict__ out, const fl
         } else {                                        // LIN_OUT: fragment f = k-step f, rows 0..3 valid
             if (row < 4) val = m.lin_out_w[(size_t)row * HID + 32 * f + perm_k(g, j)];
         }
-#ifdef PNR_DIAG_WMASK      // experiment only (tools/dev): weights rounded to 10 - PNR_DIAG_WMASK mantissa bits of the 16-bit format
-        {
-            uint32_t hb = Num<DT>::cvt(val);
-            hb = (hb + (1u << (PNR_DIAG_WMASK - 1))) & ~((1u << PNR_DIAG_WMASK) - 1u) & 0xffffu;
-            st[e] = (uint16_t)hb;
-            continue;
-        }
-#endif
         st[e] = Num<DT>::cvt(val);
     }
 }
@@ -914,11 +906,7 @@ __global__ void __launch_bounds__(256, 1) k_point_mfma(MfmaArgs a) {
             const int plain_here = (one_part && !MULTIVIEW) ? a.n_blocks - a.nb1 : 0;
             // one gathered group in front of the block's last lin_z part (multi-scale): block b's statement prefetches block
             // b + 1's image of that group while its chunks run
-#ifdef PNR_NO_IMAGE_PREFETCH      // A/B builds only (tools/dev, with the generator's `noprefetch`)
-            const bool pf = false;
-#else
             const bool pf = n_groups == 1 && !one_part;
-#endif
             for (int b = 0; b < a.nb1; b += b_step) {
                 // ---- x += lin_z[b](z): all but the block's last part as separate x-stage calls
                 for (int grp = 0; grp < n_groups; ++grp) {
@@ -1174,9 +1162,6 @@ int32_t point_mfma(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* v
     // compositing from the LDS ring: fused render launches whose rays are at most a tile long, where the ring fits behind the
     // bias table; everything else composites from the (rgb, sigma) / z the launch leaves in global memory
     a.job.cmp_lds = (a.job.on && a.job.K <= CMP_MAX_K && lds + CMP_BYTES <= (size_t)LDS_LIMIT) ? 1 : 0;
-#ifdef PNR_NO_LDS_COMPOSITE      // A/B builds only (tools/dev): every launch takes the memory route
-    a.job.cmp_lds = 0;
-#endif
     if (a.job.cmp_lds) lds += CMP_BYTES;
     const void* fn;
     const bool mv = a.NS > 1;

@@ -838,11 +838,7 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma(
     }
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)ring;
     const uint32_t dst0 = __builtin_amdgcn_readfirstlane(ring_lds + (loads_b ? 16384 : 0) + 8192 * (wv & 1));
-#if defined(PNR_HG_DIAG) && PNR_HG_DIAG == 4
-    const char* src_tile = (const char*)src + (size_t)(x0 & 2047) * ld * 2;       // timing only: the A rows stay L2-resident
-#else
     const char* src_tile = (const char*)src + (size_t)x0 * ld * 2;
-#endif
     auto issue = [&](int ks) __attribute__((always_inline)) {
         const char* sb = src_tile + (size_t)ks * 128;                // 64 k = 128 B further along every row
         const uint32_t dst = dst0 + (uint32_t)(ks & 1) * 32768u;
@@ -870,9 +866,7 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma(
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
     const int nk = K >> 6;
-#if !(defined(PNR_HG_DIAG) && PNR_HG_DIAG == 2)
     issue(0);
-#endif
     // fragment addresses within a slot (fixed over the loop): row r, logical chunk 2 s + lr of the row's eight
     uint32_t fa[2][4], fb[2][4];
 #pragma unroll
@@ -888,13 +882,8 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma(
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();          // every wave's pieces of k-step ks are in; slot (ks + 1) & 1 has no reader left
         asm volatile("" ::: "memory");
-#if !(defined(PNR_HG_DIAG) && PNR_HG_DIAG == 2)
         if (ks + 1 < nk) issue(ks + 1);
-#endif
         const char* slot = ring + (ks & 1) * 32768;
-#if defined(PNR_HG_DIAG) && PNR_HG_DIAG == 3
-        continue;
-#endif
 #pragma unroll
         for (int sp = 0; sp < 4; ++sp) {
             bf16x8 a0 = *(const bf16x8*)(slot + fa[0][sp]);
@@ -912,9 +901,6 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma(
             acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc[1][1], 0, 0, 0);
         }
     }
-#if defined(PNR_HG_DIAG) && PNR_HG_DIAG == 1
-    if (acc[0][0][0] != 1.2345e-31f) return;          // timing only: no epilogue
-#endif
     if (tile_epilogue_ok(bias, R, ldr, Mk, ldm, M16, C, ldc, C16, ldc16, N))
         tile_epilogue_lds<M16>(acc, ring, t, m0, n0, wm, wn, lc, lr, bias, R, ldr, Mk, ldm, C, ldc, C16, ldc16, M, N);
     else
@@ -1921,10 +1907,7 @@ uint64_t train_tape_bytes_p(const pnr_params* prm, const pnr_mlp* mlp, const pnr
 // Scratch for the weight gradients (carved from the backward workspace): every row split of a dW GEMM writes its own
 // (N, K) slice, the slices are then summed in a fixed order — no fp32 atomics race, so gradients are reproducible.
 struct DetWs { float* part; uint64_t floats; };
-#ifndef PNR_DET_MAX_SPLITS
-#define PNR_DET_MAX_SPLITS 64
-#endif
-static const int DET_MAX_SPLITS = PNR_DET_MAX_SPLITS;
+static constexpr int DET_MAX_SPLITS = 64;
 static uint64_t det_ws_floats(const pnr_mlp* mlp) {
     const uint64_t H = mlp->d_hidden, L = mlp->d_latent, D = mlp->d_in;
     uint64_t wmax = H * H;
@@ -2292,10 +2275,8 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
     // 512 slots (48 slices of 1024 rows were 1.5 rounds), and a third less partial-sum traffic for k_reduce_parts
     const bool dma_kt = use_half && X16 && dY16 && M % 64 == 0 && N % 128 == 0 && K % 128 == 0 && ldy % 8 == 0 && ldx % 8 == 0 &&
                         (((uintptr_t)dY16 | (uintptr_t)X16) & 15) == 0;
-#ifndef PNR_DW_SLICES
-#define PNR_DW_SLICES 32
-#endif
-    int rows_dma = (int)(((M + PNR_DW_SLICES - 1) / PNR_DW_SLICES + 63) / 64 * 64);
+    static constexpr int DW_SLICES = 32;
+    int rows_dma = (int)(((M + DW_SLICES - 1) / DW_SLICES + 63) / 64 * 64);
     if (rows_dma < 256) rows_dma = 256;
     // (the same slices for every bf16-product weight gradient, whichever kernel and tape format: the two tape formats stay
     // bit-identical)

@@ -1,8 +1,11 @@
 """The hand-scheduled statements of the fused kernel are generated (tools/gen_resblock_asm.py).  CPU checks: the committed
 .inc is what the generator produces today, and the generator's audit enforces the statement rules R1-R4 of its header —
-R1 is the root cause of round 2's fp16 race (a pending compiler load landing in a register the statement had already written)."""
+R1 is the root cause of round 2's fp16 race (a pending compiler load landing in a register the statement had already written).
+And the product has one build: no switch in the kernel sources or the generator selects another."""
+import ast
 import importlib.util
 import os
+import re
 
 import pytest
 
@@ -19,10 +22,41 @@ def _gen():
 def test_committed_inc_is_current(tmp_path, monkeypatch):
     out = tmp_path / "resblock_asm.inc"
     monkeypatch.setenv("PNR_ASM_OUT", str(out))
-    monkeypatch.delenv("PNR_ASM_DIAG", raising=False)
     _gen().main()                    # runs audit_all on what it wrote
     committed = open(os.path.join(ROOT, "pixel_nerf_multiscale_amd", "csrc", "resblock_asm.inc")).read()
     assert out.read_text() == committed, "regenerate: python tools/gen_resblock_asm.py"
+
+
+def _env_reads(path):
+    """The key of every os.environ / os.getenv use in a Python file (the use's source text where the key is no literal)."""
+    tree = ast.parse(open(path).read())
+    parent = {c: p for p in ast.walk(tree) for c in ast.iter_child_nodes(p)}
+    keys = []
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Attribute) and node.attr in ("environ", "getenv"):
+            use = parent[node]
+            if isinstance(use, ast.Attribute):                   # os.environ.get(...)
+                use = parent[use]
+            key = (use.args[0] if isinstance(use, ast.Call) and use.args else
+                   use.slice if isinstance(use, ast.Subscript) else
+                   use.left if isinstance(use, ast.Compare) else None)
+            keys.append(key.value if isinstance(key, ast.Constant) else ast.unparse(use))
+    return keys
+
+
+def test_product_has_one_build():
+    """The only macro a preprocessor conditional of the kernel sources tests is PNR_STAMPS (the instrumented build: exact
+    results plus cycle stamps), and the generator reads no environment variable but its output path."""
+    csrc = os.path.join(ROOT, "pixel_nerf_multiscale_amd", "csrc")
+    tested = {}
+    for name in sorted(n for n in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, n))):
+        text = open(os.path.join(csrc, name)).read().replace("\\\n", " ")
+        for m in re.finditer(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif|elifdef|elifndef)\b(.*)$", text, re.M):
+            cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(1))
+            for macro in set(re.findall(r"\b[A-Za-z_]\w*", cond)) - {"defined"}:
+                tested.setdefault(macro, []).append(name)
+    assert set(tested) == {"PNR_STAMPS"}, tested
+    assert _env_reads(os.path.join(ROOT, "tools", "gen_resblock_asm.py")) == ["PNR_ASM_OUT"]
 
 
 def test_audit_rejects_rule_violations():

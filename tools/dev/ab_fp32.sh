@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of two libraries on ONE box, fp32 paths: the fp32 inference frame (bench.py --precision fp32) and the fp32 training step, interleaved
+# A/B of two libraries on ONE box, fp32 paths: the fp32 inference frame (bench.py --precision fp32) and the fp32 training step, interleaved.  ab_fp32.sh LIB_A.so LIB_B.so
 cd "$(dirname "$0")/../.."
 for r in 1 2 3; do
   for v in "$@"; do

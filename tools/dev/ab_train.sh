@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of two libraries on ONE box: tools/bench_train.py bf16, interleaved three times.  exp_r4_ab_train.sh LIB_A.so LIB_B.so
+# A/B of two libraries on ONE box: tools/bench_train.py bf16, interleaved three times.  ab_train.sh LIB_A.so LIB_B.so
 cd "$(dirname "$0")/../.."
 for r in 1 2 3; do
   for v in "$@"; do

@@ -12,7 +12,8 @@ MFMA shape: v_mfma_f32_16x16x32_{bf16,f16}, TWO per 1-KiB weight fragment (the w
 groups).  Same LDS bytes, same MFMA cycles per FLOP as one 32x32x16 per fragment, but the chip holds a ~15 % higher
 clock on this shape under the kernel's load (tools/dev/ubench/shape_ubench.hip: 1.92-1.96 vs 1.66-1.69 GHz, 11 %
 less wall time per chunk; MI355X_MICROARCH.md 'DVFS give-back' item 7).  The kernel is limited by board power, not by a
-pipe: PNR_ASM_DIAG builds without the weight DMA run 12 % faster but only 4 % fewer cycles.
+pipe: a build without the weight DMA ran 12 % faster but only 4 % fewer cycles
+(profiles/r03_stage_cost_matrix.txt).
 
 Data layout (shared with k_pack_mlp and the kernel prologue, point_mfma.hip):
   * lane l: c = l & 15 (column), g = l >> 4 (k-quarter).  The wave's points are (cg, c), cg = 0, 1.
@@ -56,17 +57,6 @@ s20-s31, s33-s43 (s32 is the ABI stack pointer: left alone).
 import os
 import re
 
-# timing experiments only (results are garbage): nobarrier, nodma, nowait, nosnap, dma1, dmaearly, dmaplain, dmaquarter, nodsread,
-# nolgkm, noadvance; placement: align4; cache policy of the weight stream (results stay exact): nt0 .. nt3;
-# fp16 saturation by v_pk_min instead of MODE.FP16_OVFL (round-3 form): satmin;
-# hazard experiments of round 2 (kept for the record, all explained by rule R1): fullwait, ldswait, nosat, cvtnop, drainA/B/C, waitA4, sleepA, barA
-DIAG = os.environ.get("PNR_ASM_DIAG", "")
-# pieces q >= NT_FROM of every stage carry the non-temporal hint (nt0 = all .. nt3 = a quarter of the stream; default: none)
-# cache policy of the park stores / reduce loads (experiments: parknt, reducent; results stay exact)
-PARK_POLICY = " nt" if "parknt" in DIAG else ""
-REDUCE_POLICY = " nt" if "reducent" in DIAG else ""
-NT_FROM = next((int(m.group(1)) for m in [re.search(r"\bnt([0-3])\b", DIAG)] if m), 4)
-
 
 def A(i):
     return f"v[{96 + 4 * i}:{99 + 4 * i}]"
@@ -106,8 +96,6 @@ class Emit:
         self.L.append(line)
 
     def ds_read(self, tag, text):
-        if "nodsread" in DIAG and tag.startswith("A"):      # timing only: no weight-fragment reads
-            return
         self.L.append(text)
         self.reads.append(tag)
         assert len(self.reads) <= 15, ("more than 15 LDS reads in flight", self.reads)
@@ -116,8 +104,7 @@ class Emit:
         idx = max([i for i, t in enumerate(self.reads) if t in tags], default=-1)
         if idx < 0:
             return
-        if "nolgkm" not in DIAG:                            # timing only: no counted LDS waits
-            self.e(f"s_waitcnt lgkmcnt({len(self.reads) - 1 - idx})")
+        self.e(f"s_waitcnt lgkmcnt({len(self.reads) - 1 - idx})")
         self.reads = self.reads[idx + 1:]
 
     def drain(self):
@@ -133,22 +120,16 @@ class Emit:
         assert st == self.reads, ("LDS scoreboard differs between loop entry and back edge", st, self.reads)
 
     def relu_pack(self, dst, a0, a1, tmp):
-        if "nosnap" in DIAG:
-            return
         self.e(f"v_accvgpr_read_b32 v{tmp}, a{a0}")
         self.e(f"v_accvgpr_read_b32 v{tmp + 1}, a{a1}")
         self.relu_pack_v(dst, tmp, tmp + 1)
 
     def relu_pack_v(self, dst, v0, v1):
         self.e(f"{self.cvt} v{dst}, v{v0}, v{v1}")
-        if "cvtnop" in DIAG:
-            self.e("s_nop 1")
         self.e(f"v_pk_max_i16 v{dst}, v{dst}, 0")
         # fp16: no saturating v_pk_min here — the kernel runs with MODE.FP16_OVFL set (k_point_mfma's entry), under which the
         # conversion itself clamps an overflowing finite value to +-65504 (measured on gfx950 for v_cvt_pk_f16_f32:
         # tools/dev/ubench/ovfl_ubench.hip, profiles/r04_fp16_ovfl.txt; -2.3 % kernel time on the headline frame)
-        if self.dt == "f16" and "satmin" in DIAG:                # the round-3 form, for A/B runs
-            self.e(f"v_pk_min_i16 v{dst}, v{dst}, s38")
 
     def snapshot_ks(self, ks):
         """relu(x) of row groups 2ks, 2ks+1 -> the two B fragments of k-step ks (16 accumulator reads, 8 packs)."""
@@ -160,8 +141,6 @@ class Emit:
 
     def loader_advance(self):
         e = self.e
-        if "noadvance" in DIAG:                             # timing only: the loader re-reads one stage
-            return
         e("s_add_u32 s21, s21, 1")
         e("s_add_u32 s24, s24, 0x4000")
         e("s_addc_u32 s25, s25, 0")
@@ -186,7 +165,7 @@ class Emit:
         vm_alt = (flag test, N): where the run-time flag is set, extra LDS-DMA pieces (younger than the pieces this stage must
         see landed) are in flight, and the counted wait is vmcnt(N) instead of vmcnt(4) — loads retire in order."""
         e = self.e
-        if vm_alt and "nodma" not in DIAG and "nowait" not in DIAG:
+        if vm_alt:
             test, n = vm_alt
             self.uid = getattr(self, "uid", 100) + 1
             e(test)
@@ -201,12 +180,6 @@ class Emit:
             e("s_waitcnt vmcnt(4)")
         e("s_barrier")
         pend = None
-        if "dmaearly" in DIAG:
-            e(f"s_mov_b32 m0, {m0_sreg}")
-            e("s_nop 0")
-            for q in range(4):
-                e("global_load_lds_dwordx4 v15, s[24:25]" + (f" offset:{q * 1024}" if q else ""))
-            self.loader_advance()
         for f in range(16):
             if f % 4 == 0:
                 self.need([f"A{(f + i) & 7}" for i in range(4)])
@@ -215,15 +188,12 @@ class Emit:
             if pend:
                 self.ds_read(*pend)
             e(m2)
-            if "dmaearly" in DIAG:
-                pass
-            elif f % 4 == 1:
+            if f % 4 == 1:
                 q = f >> 2
                 if q == 0:
                     e(f"s_mov_b32 m0, {m0_sreg}")
                     e("s_nop 0")
-                if "dma1" not in DIAG or q == 0:
-                    e("global_load_lds_dwordx4 v15, s[24:25]" + (f" offset:{q * 1024}" if q else "") + (" nt" if q >= NT_FROM else ""))
+                e("global_load_lds_dwordx4 v15, s[24:25]" + (f" offset:{q * 1024}" if q else ""))
                 if q == 3:
                     self.loader_advance()
             base = rd_cur if f < 8 else rd_nxt
@@ -247,8 +217,6 @@ def entry_guard(e):
 def setup_cursor(E, cfg, stream):
     e = E.e
     entry_guard(e)
-    if "align4" in DIAG:                                     # placement experiment: shift the statement's text by 4 bytes
-        e("s_nop 0")
     e("s_nop 15")
     e("s_nop 15")                                            # accumulator writes of the caller's last MFMAs retired
     e("s_mov_b32 s39, m0")                                   # hipcc may keep a value in M0 across the statement
@@ -265,7 +233,7 @@ def setup_cursor(E, cfg, stream):
     e("s_add_u32 s24, s36, s35")
     e("s_addc_u32 s25, s37, 0")
     if E.dt == "f16":
-        e("s_mov_b32 s38, 0x7bff7bff")
+        e("s_mov_b32 s38, 0x7bff7bff")                       # fp16 bound of the round-3 v_pk_min saturation: no longer read
 
 
 def exit_cursor(E, advance):
@@ -478,15 +446,6 @@ def gen(dt):
     E = Emit(dt)
     e = E.e
     setup_cursor(E, "%21", "%22")
-    if "drainA" in DIAG:
-        e("s_waitcnt vmcnt(0)")
-    if "waitA4" in DIAG:
-        e("s_waitcnt vmcnt(4)")
-    if "sleepA" in DIAG:
-        e("s_sleep 4")
-    if "barA" in DIAG:
-        e("s_waitcnt vmcnt(4)")
-        e("s_barrier")
     # Block loop: %29 = lin_z k-steps | blocks WITH the lin_z prefix << 16 | blocks without << 20.  Consecutive blocks of a
     # tile run inside ONE statement when nothing has to happen between them (one lin_z part per block: the B image in LDS
     # serves them all) — a statement boundary costs ~700 cycles (drains, cursor set-up, the first fragments' LDS latency).
@@ -516,8 +475,6 @@ def gen(dt):
     e("s_sub_u32 s31, s31, 1")
     bias_b_operand()
     e("9:")
-    if "drainB" in DIAG:
-        e("s_waitcnt vmcnt(0)")
     fixed_bases(E, "%24", "%23")
     e("v_add_u32 v14, s33, %26")
     e("v_mov_b32 v15, %25")
@@ -555,12 +512,7 @@ def gen(dt):
                     e("global_load_lds_dwordx4 %31, s[34:35]" + (f" offset:{q * 1024}" if q else "") + " sc1")
             e(f"{lab}:")
         return hook
-    if "noprefetch" in DIAG:
-        bias_kstep_with_snapshot(E, 0)
-        alt = [None, None]
-    else:
-        bias_kstep_with_snapshot(E, 0, {14: prefetch_half(0)}, {14: prefetch_half(1)}, (PF, 12))
-        alt = [(PF, 20), (PF, 12)]
+    bias_kstep_with_snapshot(E, 0, {14: prefetch_half(0)}, {14: prefetch_half(1)}, (PF, 12))
 
     def mm_fc0(acc, half):
         def mm(f):
@@ -600,11 +552,9 @@ def gen(dt):
     # chunk 1's fc_0.bias rows into the second accumulator, then F(0) with the last five k-steps of the snapshot in its first stage
     hbias(ACC[1], "g")
     E.need([f"h{rgl}{cg}" for rgl in range(2) for cg in range(2)])
-    F(ACC[0], 2, tail_snapshot_hooks(E), need_bias=False, vm_alts=alt)
+    F(ACC[0], 2, tail_snapshot_hooks(E), need_bias=False, vm_alts=((PF, 20), (PF, 12)))
     # the loop head: outstanding = [g-bias reads?]  make the state explicit: the g reads are waited for here
     E.need([f"g{rgl}{cg}" for rgl in range(2) for cg in range(2)])
-    if "drainC" in DIAG:
-        e("s_waitcnt vmcnt(0)")
     e("s_mov_b32 s34, 7")
     E.loop_begin("1")
     # c even: F(c+1) on v72.., h_c from v40.. (its conversion + the preload of chunk c+2 ride in F's first stage)
@@ -702,12 +652,12 @@ def gen_viewspill(dt):
     e("s_cbranch_scc0 7f")
     for t in range(16):
         for q in range(4):
-            e(f"global_store_dwordx4 %17, a[{16 * t + 4 * q}:{16 * t + 4 * q + 3}], s[24:25]" + (f" offset:{q * 1024}" if q else "") + PARK_POLICY)
+            e(f"global_store_dwordx4 %17, a[{16 * t + 4 * q}:{16 * t + 4 * q + 3}], s[24:25]" + (f" offset:{q * 1024}" if q else ""))
         e("s_add_u32 s24, s24, 0x1000")
         e("s_addc_u32 s25, s25, 0")
     e("s_branch 8f")
     e("7:")
-    if dt == "f16":
+    if dt == "f16":                                          # round-3 saturation bounds: no longer read (MODE.FP16_OVFL)
         e("s_mov_b32 s38, 0x7bff7bff")
         e("s_mov_b32 s35, 0xfbfffbff")
     for t in range(16):
@@ -718,10 +668,7 @@ def gen_viewspill(dt):
                 e(f"v_accvgpr_read_b32 v{68 + 2 * (i & 1)}, a{a0}")
                 e(f"v_accvgpr_read_b32 v{69 + 2 * (i & 1)}, a{a0 + 1}")
                 e(f"{E.cvt} v{buf + i}, v{68 + 2 * (i & 1)}, v{69 + 2 * (i & 1)}")
-                if dt == "f16" and "satmin" in DIAG:             # round-3 form; MODE.FP16_OVFL clamps in the conversion now
-                    e(f"v_pk_min_f16 v{buf + i}, v{buf + i}, s38")
-                    e(f"v_pk_max_f16 v{buf + i}, v{buf + i}, s35")
-            e(f"global_store_dwordx4 %17, v[{buf}:{buf + 3}], s[24:25]" + (f" offset:{q * 1024}" if q else "") + PARK_POLICY)
+            e(f"global_store_dwordx4 %17, v[{buf}:{buf + 3}], s[24:25]" + (f" offset:{q * 1024}" if q else ""))
         e("s_add_u32 s24, s24, 0x800")
         e("s_addc_u32 s25, s25, 0")
     # No vmcnt wait: the stores read their own buffer registers (written once each), the tiles are free for the next view's
@@ -745,7 +692,7 @@ def gen_viewreduce(dt):
 
         def loads(b):
             for q in range(4):
-                e(f"global_load_dwordx4 v[{b + 4 * q}:{b + 4 * q + 3}], %19, s[24:25]" + (f" offset:{q * 1024}" if q else "") + REDUCE_POLICY)
+                e(f"global_load_dwordx4 v[{b + 4 * q}:{b + 4 * q + 3}], %19, s[24:25]" + (f" offset:{q * 1024}" if q else ""))
             e("s_add_u32 s24, s24, 0x1000")
             e("s_addc_u32 s25, s25, 0")
         for t in range(D):
@@ -767,7 +714,7 @@ def gen_viewreduce(dt):
         for t in range(16):
             for q in range(2):
                 buf = 96 + 8 * t + 4 * q
-                e(f"global_load_dwordx4 v[{buf}:{buf + 3}], %19, s[24:25]" + (f" offset:{q * 1024}" if q else "") + REDUCE_POLICY)
+                e(f"global_load_dwordx4 v[{buf}:{buf + 3}], %19, s[24:25]" + (f" offset:{q * 1024}" if q else ""))
             e("s_add_u32 s24, s24, 0x800")
             e("s_addc_u32 s25, s25, 0")
         for t in range(16):
@@ -928,28 +875,8 @@ def main():
                              ("bf16", "PNR_LINOUT_ASM_BF16", gen_linout), ("f16", "PNR_LINOUT_ASM_F16", gen_linout),
                              ("bf16", "PNR_VIEWSPILL_ASM_BF16", gen_viewspill), ("f16", "PNR_VIEWSPILL_ASM_F16", gen_viewspill),
                              ("bf16", "PNR_VIEWREDUCE_ASM_BF16", gen_viewreduce), ("f16", "PNR_VIEWREDUCE_ASM_F16", gen_viewreduce)):
-            lines = fn(dt)
-            if "nobarrier" in DIAG:
-                lines = [l for l in lines if l != "s_barrier"]
-            if "nowait" in DIAG:
-                lines = [("s_nop 0" if l == "s_waitcnt vmcnt(4)" else l) for l in lines]
-            if "fullwait" in DIAG or "drain" in DIAG:
-                pass
-            if "nosat" in DIAG:
-                lines = [l for l in lines if not l.startswith("v_pk_min_i16")]
-            if "fullwait" in DIAG:
-                lines = [("s_waitcnt vmcnt(0)" if l == "s_waitcnt vmcnt(4)" else l) for l in lines]
-            if "ldswait" in DIAG:
-                lines = [("s_waitcnt lgkmcnt(0)" if l.startswith("s_waitcnt lgkmcnt(") else l) for l in lines]
-            if "dmaplain" in DIAG:      # timing only: ordinary loads into (garbage) registers instead of LDS-DMA
-                lines = [l.replace("global_load_lds_dwordx4 v15,", "global_load_dwordx4 v[68:71], v15,") for l in lines]
-            if "dmaquarter" in DIAG:
-                lines = [l.replace("global_load_lds_dwordx4", "global_load_lds_dword") for l in lines]
-            if "nodma" in DIAG:
-                lines = [l for l in lines if not l.startswith("global_load_lds")]
-                lines = [("s_nop 0" if l == "s_waitcnt vmcnt(4)" else l) for l in lines]
             f.write(f"#define {name} \\\n")
-            for l in lines:
+            for l in fn(dt):
                 f.write(f'    "{l}\\n\\t" \\\n')
             f.write('    ""\n\n')
         clob = ["memory", "scc", "vcc"] + [f"v{i}" for i in list(range(10, 24)) + list(range(40, 56)) + list(range(60, 88)) + list(range(96, 256))] \
