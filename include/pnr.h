@@ -379,6 +379,12 @@ typedef struct {
 } pnr_debug_linear_args;
 int32_t pnr_debug_linear(pnr_debug_linear_args* args, void* stream);
 
+/* The route pnr_point_mlp_bwd takes for the latent-map gradient of these maps and n_points points (host only, no launch):
+ * PNR_DBG_LATG_LDS per-block partial maps in LDS + an ordered reduction (one level of at most 64 KiB that fits the device's
+ * LDS), PNR_DBG_LATG_FIXED_POINT 64-bit fixed-point integer atomics (every other map), PNR_DBG_LATG_NONE nothing to do. */
+enum { PNR_DBG_LATG_NONE = 0, PNR_DBG_LATG_LDS = 1, PNR_DBG_LATG_FIXED_POINT = 2 };
+int32_t pnr_debug_latent_grad_route(const pnr_views* views, int64_t n_points);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,8 +127,10 @@ def index_latent(uv, latents):
         gy = (uvb[:, :, 1] / (H - 1)) * 2 - 1
         ix = ((gx + 1) / 2) * (W - 1)
         iy = ((gy + 1) / 2) * (H - 1)
-        ix = torch.clamp(ix, 0, W - 1)      # NaN propagates, like ATen's clip via min/max
-        iy = torch.clamp(iy, 0, H - 1)
+        # clip: NaN propagates, like ATen's clip via min/max; the gradient follows clip_coordinates_set_grad, zero AT a bound
+        # as well as beyond it (torch.clamp's own gradient is 1 at the bound: a nonzero d(uv) exactly on a map border)
+        ix = torch.where((ix > 0) & (ix < W - 1), ix, ix.detach().clamp(0, W - 1))
+        iy = torch.where((iy > 0) & (iy < H - 1), iy, iy.detach().clamp(0, H - 1))
         x0 = torch.floor(ix); y0 = torch.floor(iy)
         x1 = x0 + 1; y1 = y0 + 1
         w_nw = (x1 - ix) * (y1 - iy)

@@ -1508,7 +1508,7 @@ static __global__ void __launch_bounds__(256) k_abs_max_cols(const float* __rest
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / L;
         const float v = fabsf(x[r * ld + (i - r * L)]);
-        if (v <= 3.4e38f) m = fmaxf(m, v);                    // finite values set the scale
+        if (v <= __FLT_MAX__) m = fmaxf(m, v);                // every finite value sets the scale (up to 3.40282347e38)
         else bad = 1u;                                        // NaN / inf: remembered in out[1], k_latq_finalize propagates it
     }
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -2705,6 +2705,13 @@ static int32_t debug_linear(pnr_debug_linear_args* a, hipStream_t s, DbgSite* d)
                             (const uint16_t*)a->x16, (const uint16_t*)a->g16, d);
     }
     return PNR_E_UNSUPPORTED;
+}
+
+// Which latent-gradient route pnr_point_mlp_bwd takes for these maps (include/pnr.h); tests/test_gpu_train_fp64.py.
+extern "C" int32_t pnr_debug_latent_grad_route(const pnr_views* vw, int64_t n_points) {
+    if (!vw || vw->n_levels < 1 || n_points <= 0) return PNR_DBG_LATG_NONE;
+    if (latent_grad_in_lds(vw)) return PNR_DBG_LATG_LDS;
+    return latent_q_bytes(vw) > 0 ? PNR_DBG_LATG_FIXED_POINT : PNR_DBG_LATG_NONE;
 }
 
 extern "C" int32_t pnr_debug_linear(pnr_debug_linear_args* a, void* stream) {

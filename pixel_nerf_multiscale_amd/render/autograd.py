@@ -249,9 +249,14 @@ def render_train(rend, net, rays, want_weights):
     out_c = sigma_noise(point_mlp_rays(net, net.mlp_coarse, r, z_c))
     comp_c = Composite.apply(r, z_c, out_c, rend.white_bkgd)
     res = AttrDict(coarse=rend._format_outputs(comp_c, SB, want_weights))
+    keep = getattr(rend, "keep_samples", False)          # the sample positions, as the fused path leaves them
+    if keep:
+        res.coarse.z = z_c.detach().reshape(SB, B, -1)
     if rend.using_fine:
         z_f = SampleFine.apply(rend, r, z_c, comp_c[0], comp_c[2], seed, noise)
         mlp_f = net.mlp_fine if net.mlp_fine is not None else net.mlp_coarse
         out_f = sigma_noise(point_mlp_rays(net, mlp_f, r, z_f))
         res.fine = rend._format_outputs(Composite.apply(r, z_f, out_f, rend.white_bkgd), SB, want_weights)
+        if keep:
+            res.fine.z = z_f.detach().reshape(SB, B, -1)
     return res

@@ -345,9 +345,9 @@ def test_weight_gradients_are_run_to_run_identical(train_precision):
 def test_latent_map_gradients_are_run_to_run_identical(NS, SB, lat):
     """Latent maps that fit the LDS (the SRN / NMR shapes the reference trains on): per-block partial maps filled by
     channel-owning threads in point order + an ordered reduction — no float atomics, so the encoder's incoming gradient
-    is BIT-identical from run to run, and it still matches the atomics-free reference arithmetic (checked against the
-    gradient of a float64 oracle elsewhere in this file; here: two runs, and a third with the batch rendered twice as
-    large proves the slices are really summed, not overwritten)."""
+    is BIT-identical from run to run (two runs here).  That the slices are really summed, not overwritten or dropped, is
+    checked against a float64 oracle, every entry, at block-boundary point counts in
+    test_gpu_train_fp64.py::test_route_and_block_boundaries_match_fp64."""
     spec = gu._case(seed=79, d_hidden=512, lat=[lat], image=(128, 128), focal=131.25, NS=NS, SB=SB, N=300,
                     Kc=32, Kf=16, Kfd=8)
     rays_np, poses_np = gu.make_inputs(spec)
