@@ -98,8 +98,9 @@ def encode_cameras(poses_c2w, focal, c, W, H):
 
 
 # ------------------------------------------------------------------ a11 model/code.py:11-46
-def positional_encoding(x, num_freqs=6, freq_factor=1.5):
-    """[x, sin(f0 x), sin(f0 x + pi/2), sin(f1 x), ...], f_k = freq_factor * 2^k; pi/2 in fp32."""
+def positional_encoding(x, num_freqs=6, freq_factor=1.5, rnd=None):
+    """[x, sin(f0 x), sin(f0 x + pi/2), sin(f1 x), ...], f_k = freq_factor * 2^k; pi/2 in fp32.
+    rnd: optional rounding hook (see resnetfc), applied to the sine features as rnd(t, "sine"); the raw x is not rounded."""
     freqs = freq_factor * 2.0 ** torch.arange(0, num_freqs)
     fr = torch.repeat_interleave(freqs, 2).view(1, -1, 1).to(x.dtype)
     ph = torch.zeros(2 * num_freqs)
@@ -107,6 +108,8 @@ def positional_encoding(x, num_freqs=6, freq_factor=1.5):
     ph = ph.view(1, -1, 1).to(x.dtype)     # the fp32 buffer's value also when a test runs this file in float64
     embed = x.unsqueeze(1).repeat(1, num_freqs * 2, 1)
     embed = torch.sin(torch.addcmul(ph, embed, fr))
+    if rnd is not None:
+        embed = rnd(embed, "sine")
     return torch.cat((x, embed.view(x.shape[0], -1)), dim=-1)
 
 
@@ -151,29 +154,36 @@ def index_latent(uv, latents):
 
 
 # ------------------------------------------------------------------ a13/a14 model/resnetfc.py:53-62,173-236 ; util/util.py:466-476
-def resnetfc(sd, zx, d_latent, NS, P, n_blocks=5, combine_layer=3, combine_type="average"):
-    """sd = state-dict (reference key names).  zx (SB*NS*P, d_latent + d_in) -> (SB*P, d_out)."""
-    lin = lambda x, k: torch.addmm(sd[k + ".bias"], x, sd[k + ".weight"].t())
+def resnetfc(sd, zx, d_latent, NS, P, n_blocks=5, combine_layer=3, combine_type="average", rnd=None):
+    """sd = state-dict (reference key names).  zx (SB*NS*P, d_latent + d_in) -> (SB*P, d_out).
+    rnd: optional rounding hook rnd(tensor, kind) -> tensor for a mixed-precision emulation of the same network
+    (tests/fused_fp64_util.py); None (every caller but that one) leaves the function as the reference wrote it.  Kinds:
+    "weight" every weight matrix, "act" a layer input behind its ReLU, "park" the per-view residual stream in front of the
+    view reduction; point_forward adds "latent" (the interpolated latent vector) and "sine" (the sine features).  Biases,
+    the raw lin_in inputs and the accumulation are never rounded."""
+    q = (lambda t, kind: t) if rnd is None else rnd
+    lin = lambda x, k: torch.addmm(sd[k + ".bias"], x, q(sd[k + ".weight"], "weight").t())
+    act = lambda x: q(torch.relu(x), "act")
     z, x = zx[:, :d_latent], zx[:, d_latent:]
     x = lin(x, "lin_in")
     for b in range(n_blocks):
         if b == combine_layer and NS > 1:
-            x = x.reshape(-1, NS, P, x.shape[-1])
+            x = q(x, "park").reshape(-1, NS, P, x.shape[-1])
             x = x.mean(dim=1) if combine_type == "average" else x.max(dim=1)[0]
             x = x.reshape(-1, x.shape[-1])
         if d_latent > 0 and b < combine_layer:
             x = x + lin(z, f"lin_z.{b}")
-        net = lin(torch.relu(x), f"blocks.{b}.fc_0")
-        dx = lin(torch.relu(net), f"blocks.{b}.fc_1")
+        net = lin(act(x), f"blocks.{b}.fc_0")
+        dx = lin(act(net), f"blocks.{b}.fc_1")
         x = x + dx
-    return lin(torch.relu(x), "lin_out")
+    return lin(act(x), "lin_out")
 
 
 # ------------------------------------------------------------------ a10/a15 model/models.py.backup2:155-282
 def point_forward(sd, cam, latents, xyz, viewdirs, NS, use_code_viewdirs=False,
-                  n_blocks=5, combine_layer=3, combine_type="average", return_stages=False):
+                  n_blocks=5, combine_layer=3, combine_type="average", return_stages=False, rnd=None):
     """xyz, viewdirs (SB,P,3) world space -> (SB,P,4) [sigmoid rgb, relu sigma].
-    cam = (w2c (SB*NS,3,4), focal (1|SB*NS,2), c (1|SB*NS,2)) from encode_cameras."""
+    cam = (w2c (SB*NS,3,4), focal (1|SB*NS,2), c (1|SB*NS,2)) from encode_cameras.  rnd: resnetfc's rounding hook."""
     w2c, focal, c = cam
     SB, P, _ = xyz.shape
     rep = lambda t: t.unsqueeze(1).expand(-1, NS, *t.shape[1:]).reshape(-1, *t.shape[1:])
@@ -182,18 +192,21 @@ def point_forward(sd, cam, latents, xyz, viewdirs, NS, use_code_viewdirs=False,
     x_cam = x_rot + w2c[:, None, :3, 3]
     zf = x_rot.reshape(-1, 3)                                        # normalize_z, use_xyz
     vd = torch.matmul(w2c[:, None, :3, :3], rep(viewdirs.reshape(SB, P, 3, 1))).reshape(-1, 3)
+    hook = {} if rnd is None else dict(rnd=rnd)                      # no hook: the calls are the ones they always were
     if use_code_viewdirs:
-        zf = positional_encoding(torch.cat((zf, vd), dim=1))
+        zf = positional_encoding(torch.cat((zf, vd), dim=1), **hook)
     else:
-        zf = torch.cat((positional_encoding(zf), vd), dim=1)
+        zf = torch.cat((positional_encoding(zf, **hook), vd), dim=1)
     uv = -x_cam[:, :, :2] / x_cam[:, :, 2:]
     uv = uv * (rep(focal.unsqueeze(1)) if focal.shape[0] > 1 else focal.unsqueeze(1))
     uv = uv + (rep(c.unsqueeze(1)) if c.shape[0] > 1 else c.unsqueeze(1))
     lat = index_latent(uv, latents)                                  # (SB*NS, L, P)
     L = lat.shape[1]
     lat = lat.transpose(1, 2).reshape(-1, L)
+    if rnd is not None:
+        lat = rnd(lat, "latent")
     zx = torch.cat((lat, zf), dim=-1)
-    o = resnetfc(sd, zx, L, NS, P, n_blocks, combine_layer, combine_type).reshape(-1, P, 4)
+    o = resnetfc(sd, zx, L, NS, P, n_blocks, combine_layer, combine_type, **hook).reshape(-1, P, 4)
     out = torch.cat([torch.sigmoid(o[..., :3]), torch.relu(o[..., 3:4])], dim=-1).reshape(SB, P, 4)
     if return_stages:
         return out, dict(uv=uv, index_out=lat, mlp_in=zx, mlp_out=o.reshape(-1, 4))

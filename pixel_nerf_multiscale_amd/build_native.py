@@ -25,6 +25,10 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     hdrs = [os.path.join(CSRC, "pnr_common.h"), os.path.join(HERE, "..", "include", "pnr.h")]
     hdrs += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
+    # a library newer than every source and header is current, with or without its object files next to it (a tree copied
+    # without *.o must not recompile everything)
+    if not force and not _newer([os.path.join(CSRC, s) for s in SOURCES] + hdrs, LIB):
+        return LIB
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

@@ -290,7 +290,7 @@ def test_mfma_frame_psnr(prec, floor):
 @pytest.mark.parametrize("prec,floor,floor_self", [("bf16", 50.0, 50.0), ("fp16", 65.0, 65.0)])
 @pytest.mark.parametrize("lat,image,NS", [((256, 8, 8), (128, 128), 1), ((256, 5, 7), (80, 56), 1), ((256, 8, 16), (128, 64), 1),
                                           ((256, 8, 8), (64, 64), 3), ((256, 6, 6), (48, 48), 2), ((256, 16, 16), (128, 128), 1),
-                                          ("multiscale", (64, 64), 2)])
+                                          ("multiscale", (64, 64), 2), ((256, 16, 16), (16, 16), 1)])
 def test_projected_stream_matches_general_path(prec, floor, floor_self, lat, image, NS):
     """One view + one small latent map: the stream carries W_z . Lat (pnr_pack_mlp_projected) and the kernel skips the
     gather.  Same inputs through the projected stream, the general (gather + lin_z) stream and the fp32 path; also a
@@ -306,6 +306,8 @@ def test_projected_stream_matches_general_path(prec, floor, floor_self, lat, ima
     else:
         lats = [lat]
     spec = dict(gu.CASES["full_ns1"]); spec.update(Kc=48, Kf=16, Kfd=8, lat=lats, image=image, seed=41, NS=NS, use_code_viewdirs=cv)
+    if image == (lat[2], lat[1]):      # an image as large as the map: the focal scales with it, the samples land inside the map
+        spec["focal"] = spec["focal"] * image[0] / 128.0
     poses = np.stack([gu.pose_spherical(10.0 + 35.0 * v, -20.0, spec["radius"]) for v in range(NS)])[None]
     W, H = image
     g = torch.Generator().manual_seed(3)
@@ -663,15 +665,29 @@ def _staged_render(net, rend, rays):
     return res
 
 
+def _interior_setup(prec, N=100):
+    """setup() for a spec no fixture holds: a 16 x 16 image over a (256, 16, 16) map (fused_fp64_util.interior_spec), so the
+    rays' samples run over the map's interior with four live taps instead of clamping to a border texel; seeded noise."""
+    from hip_util import build_net, build_renderer
+    import fused_fp64_util as fu
+    import train_fp64_util as tu
+    spec = fu.interior_spec([(256, 16, 16)], N=N, seed=45)
+    rays, poses = gu.make_inputs(spec)
+    net, rend = build_net(spec, poses, "cuda", prec), build_renderer(spec)
+    rend.fixed_noise = {k: v.cuda() for k, v in tu.make_noise(spec, 45).items()}
+    assert fu.interior_fraction(spec, poses, (rays[..., :3] + 2.0 * rays[..., 3:6])) > 0.6
+    return dict(rays=rays, poses=poses), spec, net, rend
+
+
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
-@pytest.mark.parametrize("name", FULL)
+@pytest.mark.parametrize("name", FULL + ["interior_16x16"])
 def test_fused_render_launch_is_bit_identical_to_the_staged_launches(name, prec):
     """pnr_render runs a pass as ONE launch of the MFMA kernel (coarse positions generated in the tile
     prologue, the network, compositing of every finished ray by the workgroup that evaluated it).  Same arithmetic in the
     same order as the stage kernels, so pixels, depths, weights and sample positions are BIT-identical to the staged
     launches — on the reference fixtures (explicit noise tensors) and with in-kernel Philox noise on a ragged ray count."""
     from hip_util import setup
-    fx, spec, net, rend = setup(name, precision=prec)
+    fx, spec, net, rend = _interior_setup(prec) if name == "interior_16x16" else setup(name, precision=prec)
     rend.keep_samples = True
     rays = _dev(fx["rays"])
     for mode in ("fixture noise", "kernel rng"):
@@ -802,7 +818,7 @@ def test_fused_render_launch_several_objects(NS, SB, N):
 
 @pytest.mark.parametrize("prec,floor", [("bf16", 50.0), ("fp16", 65.0)])
 @pytest.mark.parametrize("NS,SB,N,lat", [(1, 2, 700, (256, 8, 8)), (2, 3, 257, (256, 6, 6)), (1, 5, 40, (256, 8, 8)),
-                                          (2, 2, 300, "multiscale")])
+                                          (2, 2, 300, "multiscale"), (1, 2, 200, "interior")])
 def test_projected_stream_several_objects(prec, floor, NS, SB, N, lat):
     """Projected streams for SB > 1: one stream per object (each carries W_z . Lat of ITS views); workgroups are assigned per
     object, so a tile never mixes objects.  Against the general (gather + lin_z) stream and the fp32 path on the same rays;
@@ -811,10 +827,14 @@ def test_projected_stream_several_objects(prec, floor, NS, SB, N, lat):
     cv = False
     if lat == "multiscale":
         lats, cv = [(64, 32, 32), (64, 32, 32), (128, 16, 16), (256, 8, 8)], True
+    elif lat == "interior":        # a 16 x 16 image over a 16 x 16 map: the samples land inside the map (fused_fp64_util.interior_spec)
+        lats = [(256, 16, 16)]
     else:
         lats = [lat]
     spec = dict(gu.CASES["full_ns1"]); spec.update(NS=NS, SB=SB, N=N, Kc=40, Kf=24, Kfd=8, lat=lats, seed=60 + NS + SB,
                                                     use_code_viewdirs=cv)
+    if lat == "interior":
+        spec.update(image=(16, 16), focal=spec["focal"] * 16 / 128.0)
     rays_np, poses = gu.make_inputs(spec)
     rays = torch.from_numpy(rays_np).cuda()
     outs, pts = {}, {}
