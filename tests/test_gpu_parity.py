@@ -730,8 +730,10 @@ def test_rays_generated_inside_the_render_launch_are_bit_identical(name, prec):
 def test_resnetfc_forward_and_encoder_index_are_native_stage_calls(name):
     """ResnetFC.forward (resnetfc.py:173-236) and SpatialEncoder.index (encoder.py:138-205) as module calls backed by
     pnr_resnetfc_forward / pnr_index_latent, against the oracle's restatement of the same two functions: assembled rows
-    with the (views, points) reduction, a flat batch without one, a row count that crosses the 16384-row chunk, and the
-    lookup with per-view and broadcast uv incl. off-image points."""
+    with the (views, points) reduction, a flat batch without one, a row count that crosses the 49152-row chunk (F32_CHUNK of
+    csrc/point_f32.hip) by 7 — on one view, and on two objects of two views, where the views' row blocks of a chunk are not
+    contiguous and resnetfc_f32 gathers them with hipMemcpy2DAsync — and the lookup with per-view and broadcast uv incl.
+    off-image points."""
     import oracle_util as ou
     from hip_util import setup
     from oracle import pixelnerf_oracle as orc
@@ -741,7 +743,7 @@ def test_resnetfc_forward_and_encoder_index_are_native_stage_calls(name):
     sd = {k: v.detach().cpu() for k, v in mlp.state_dict().items()}
     SB, NS = spec["SB"], spec["NS"]
     E = mlp.d_latent + mlp.d_in
-    for P in (7, 16400 if name == "tiny_ns1" else 33):
+    for P in (7, 49152 + 7 if name in ("tiny_ns1", "tiny_sb2_ns2") else 33):
         zx = torch.randn(SB * NS * P, E, generator=g)
         ref = orc.resnetfc(sd, zx, mlp.d_latent, NS, P, n_blocks=mlp.n_blocks, combine_layer=mlp.combine_layer,
                            combine_type=mlp.combine_type)
