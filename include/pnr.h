@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-#define PNR_VERSION 102          /* 0.1.2: pnr_views.uv_scale_{x,y} (opt-in upstream texel mapping); 101: output strides, per-object ray index stride */
+#define PNR_VERSION 102          /* 0.1.2: pnr_views.uv_scale_{x,y} (opt-in upstream texel mapping); 101: output strides, per-object ray index stride.
+                                  * Added since, backward compatible (no bump): the training front end, pnr_train_batch / pnr_rgb_loss / pnr_rgb_loss_bwd */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -231,8 +232,9 @@ int32_t pnr_render(const pnr_params* params, const pnr_mlp* coarse, const pnr_ml
                    const pnr_outputs* outputs, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* ---- training: the same path under autograd, train/train.py:324-346,382-410 ---------- */
-/* Gradient buffers, shaped like the pnr_mlp weights; every non-NULL member is ACCUMULATED into (+=, fp32
- * atomics), so the caller zeroes them (or passes .grad tensors).  NULL members are skipped. */
+/* Gradient buffers, shaped like the pnr_mlp weights; every non-NULL member is ACCUMULATED into (+=: per-split partial
+ * products summed by an ordered reduction, no floating-point atomics — bit-reproducible), so the caller zeroes
+ * them (or passes .grad tensors).  NULL members are skipped. */
 typedef struct pnr_mlp_grads {
     float* lin_in_w;  float* lin_in_b;
     float* lin_z_w[PNR_MAX_BLOCKS];  float* lin_z_b[PNR_MAX_BLOCKS];
@@ -313,6 +315,39 @@ int32_t pnr_render_camera(const pnr_params* params, const pnr_mlp* coarse, const
 int32_t pnr_gen_rays(const float* c2w /* host, 16 floats */, int32_t W, int32_t H, float fx, float fy,
                      float cx, float cy, float z_near, float z_far, int64_t pix0, int64_t n,
                      float* rays_out, void* stream);
+
+/* ---- training front end: the batch and the loss of Trainer.calc_losses (train/train.py:237-373) ---------------------- */
+/* Rays and ground-truth colours of sampled pixels (train.py:280-311, which builds gen_rays of ALL NV views and keeps B rows):
+ * one thread per sampled ray.  pix_inds[o, i] = view * H * W + row * W + col (train.py:298) names a pixel of object o;
+ * rays_out[o, i] = [pose[:3, 3], R . unproj(col, row), z_near, z_far], bit-identical to what pnr_gen_rays writes for that
+ * camera and pixel; rgb_gt_out[o, i] = 0.5 * images[o, view, :, row, col] + 0.5 (bit-identical to torch's images * 0.5 + 0.5).
+ * The indices live on the device, so the kernel is the range check: an index outside [0, NV*H*W) reads nothing and its row of
+ * both outputs is written as NaN.  NV*H*W must be below 2^31. */
+int32_t pnr_train_batch(const float* images,   /* (SB, NV, 3, H, W), in [-1, 1] as the data loader gives them; may be NULL with rgb_gt_out NULL */
+                        const float* poses,    /* (SB, NV, 4, 4) camera-to-world */
+                        const float* focal,    /* (SB, 2): fx, fy */
+                        const float* c,        /* (SB, 2), or NULL = (W/2, H/2) */
+                        int32_t SB, int32_t NV, int32_t W, int32_t H, float z_near, float z_far,
+                        const int64_t* pix_inds, /* (SB, B) */
+                        int64_t B, float* rays_out /* (SB, B, 8) */, float* rgb_gt_out /* (SB, B, 3) or NULL */,
+                        void* stream);
+
+/* torch.nn.MSELoss / L1Loss(reduction="mean") (model/loss.py:99-103) of the coarse and the fine colours, dense (n_rays, 3),
+ * as train.py:338-346 combines them: L = mean over 3*n_rays elements of (x - gt)^2 or |x - gt|;
+ *   losses[0] = lambda_coarse * Lc, losses[1] = lambda_fine * Lf (0 without a fine pass)    — loss_dict "rc", "rf"
+ *   losses[2] = total = losses[0] + losses[1], or Lc (no lambda) when fine_rgb is NULL        — loss_dict "t"
+ * One launch of one workgroup, fixed summation order (csrc/loss.hip), no atomics: the same inputs give the same bits.
+ * n_rays == 0 writes three zeros. */
+int32_t pnr_rgb_loss(const float* coarse_rgb, const float* fine_rgb /* NULL: no fine pass */, const float* rgb_gt,
+                     int64_t n_rays, int32_t use_l1, float lambda_coarse, float lambda_fine,
+                     float* losses /* 3 floats */, void* stream);
+/* Gradient of `total`: d_x = d_total * w * 2 (x - gt) / (3 n_rays), or d_total * w * sign(x - gt) / (3 n_rays) with
+ * sign(0) = 0 for L1; w = the weight the pass has in total (lambda, or 1 for the coarse pass when fine_rgb is NULL).  d_total is
+ * read on the device (a GradScaler scale arrives without a host round trip); a power of two scales every element exactly. */
+int32_t pnr_rgb_loss_bwd(const float* coarse_rgb, const float* fine_rgb, const float* rgb_gt, int64_t n_rays,
+                         int32_t use_l1, float lambda_coarse, float lambda_fine,
+                         const float* d_total /* 1 float; NULL = 1 */,
+                         float* d_coarse_rgb, float* d_fine_rgb /* (n_rays, 3); either may be NULL */, void* stream);
 
 /* Timing hook for bench.py: microseconds between the first and last point-MLP launch of the most recent
  * pnr_render on this thread is NOT kept (no global state); instead the caller brackets calls with

@@ -124,6 +124,9 @@ PROTOTYPES = {
     "pnr_composite_bwd": (_i32, [_fp, _fp, _fp, _i64, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnr_sample_fine_bwd": (_i32, [_fp, _fp, _i64, _i32, _i32, _i32, _f, _fp, _u64, _i64, _fp, _fp, _fp, _fp]),
     "pnr_gen_rays": (_i32, [C.POINTER(C.c_float), _i32, _i32, _f, _f, _f, _f, _f, _f, _i64, _i64, _fp, _fp]),
+    "pnr_train_batch": (_i32, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _f, _f, _fp, _i64, _fp, _fp, _fp]),
+    "pnr_rgb_loss": (_i32, [_fp, _fp, _fp, _i64, _i32, _f, _f, _fp, _fp]),
+    "pnr_rgb_loss_bwd": (_i32, [_fp, _fp, _fp, _i64, _i32, _f, _f, _fp, _fp, _fp, _fp]),
     "pnr_event_create": (_i32, [C.POINTER(C.c_void_p)]),
     "pnr_event_record": (_i32, [_fp, _fp]),
     "pnr_event_elapsed_ms": (_i32, [_fp, _fp, C.POINTER(C.c_float)]),

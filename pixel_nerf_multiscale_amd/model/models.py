@@ -12,7 +12,7 @@ import torch
 from torch.autograd.profiler import record_function
 
 from .. import _native as N
-from ..util import as_conf
+from ..util import as_conf, repeat_interleave
 from .code import PositionalEncoding
 from .encoder import ImageEncoder, SpatialEncoder
 from .resnetfc import ResnetFC
@@ -110,7 +110,9 @@ class PixelNeRFNet(torch.nn.Module):
         rot = poses[:, :3, :3].transpose(1, 2)
         trans = -torch.bmm(rot, poses[:, :3, 3:])
         self.poses = torch.cat((rot, trans), dim=-1).contiguous()
-        self.image_shape = torch.tensor([float(width), float(height)], device=dev)
+        # filled on the device: a host tensor copied over would make every encode() of a training step wait for the stream
+        self.image_shape = torch.full((2,), float(width), device=dev)
+        self.image_shape[1] = float(height)
         focal = torch.as_tensor(focal, dtype=torch.float32, device=dev)
         if focal.dim() == 0:
             focal = focal[None, None].repeat(1, 2)
@@ -411,6 +413,10 @@ def views_from(poses, focal, c, num_views_per_obj, maps, uv_scale=None):
     nv = maps[0].shape[0]
     v.n_views = int(num_views_per_obj)
     v.n_objs = nv // v.n_views
+    # one (fx, fy) / c per OBJECT (a training batch's per-object intrinsics, train/train.py:324-329) -> one per view, as
+    # models.py.backup2:216-221 repeats them
+    per_view = lambda t: repeat_interleave(t, v.n_views) if (v.n_views > 1 and 1 < t.shape[0] == v.n_objs) else t
+    focal, c = per_view(focal), per_view(c)
     for name, t in (("w2c", poses), ("focal", focal), ("c", c)):
         t = N.f32c(t.detach(), dev)
         keep.append(t)

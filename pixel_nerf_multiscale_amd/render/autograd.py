@@ -8,6 +8,7 @@ points (csrc/train_f32.hip) — no PyTorch arithmetic on the per-point data:
   PointMLP      pnr_point_mlp_train_fwd / pnr_point_mlp_bwd    PixelNeRFNet.forward (models.py.backup2:155-282)
   Composite     pnr_composite / pnr_composite_bwd              NeRFRenderer.composite (nerf.py:178-182,223-249)
   SampleFine    pnr_sample_fine / pnr_sample_fine_bwd          sample_fine* + cat + sort (nerf.py:120-161,285-295)
+  RGBLoss       pnr_rgb_loss / pnr_rgb_loss_bwd                the trainer's rgb loss (train.py:338-346, loss.py:99-103)
 
 Gradients reach the MLP weights, the encoder's latent maps (and through them the ResNet trunk, which stays
 a PyTorch module) and — because nerf.py:287-289 does not detach the depth-guided samples — the coarse depth
@@ -203,6 +204,46 @@ class SampleFine(torch.autograd.Function):
                                           None if ctx.g is None else N.ptr(ctx.g), seed, base, N.ptr(z), N.ptr(d_z),
                                           N.ptr(d_depth), N.current_stream(rays.device)), "pnr_sample_fine_bwd")
         return None, None, None, None, d_depth, None, None
+
+
+class RGBLoss(torch.autograd.Function):
+    """(total, stats) = rgb loss of the coarse and (unless None) the fine colours against rgb_gt, all (..., 3):
+    MSELoss / L1Loss(reduction="mean") combined as train/train.py:338-346 does.  total: 0-dim, differentiable in both
+    colour tensors.  stats: the 3-float device buffer [lambda_c Lc, lambda_f Lf, total] (loss_dict rc / rf / t), not
+    differentiable.  Nothing is read back: the incoming gradient is handed to the backward kernel as a device pointer."""
+
+    @staticmethod
+    def forward(ctx, coarse_rgb, fine_rgb, rgb_gt, use_l1, lambda_coarse, lambda_fine):
+        dev = N.same_device(coarse_rgb, fine_rgb, rgb_gt)
+        if coarse_rgb.shape != rgb_gt.shape or coarse_rgb.shape[-1] != 3 or (fine_rgb is not None and fine_rgb.shape != rgb_gt.shape):
+            raise ValueError(f"rgb tensors must share one (..., 3) shape: coarse {tuple(coarse_rgb.shape)}, fine "
+                             f"{None if fine_rgb is None else tuple(fine_rgb.shape)}, gt {tuple(rgb_gt.shape)}")
+        c, g = N.f32c(coarse_rgb.detach()), N.f32c(rgb_gt.detach())
+        f = None if fine_rgb is None else N.f32c(fine_rgb.detach())
+        cfg = (c.numel() // 3, int(bool(use_l1)), float(lambda_coarse), float(lambda_fine))
+        stats = torch.empty(3, device=dev)
+        N.check(N.lib.pnr_rgb_loss(N.ptr(c), N.ptr(f), N.ptr(g), cfg[0], cfg[1], cfg[2], cfg[3], N.ptr(stats),
+                                   N.current_stream(dev)), "pnr_rgb_loss")
+        ctx.cfg = cfg
+        ctx.has_fine = f is not None
+        ctx.save_for_backward(c, g, *([f] if f is not None else []))
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)        # no zero tensor for the stats' absent gradient
+        return stats[2], stats                  # total: a 0-dim view of the stats buffer, no copy
+
+    @staticmethod
+    def backward(ctx, d_total, _d_stats):
+        if d_total is None:
+            return (None,) * 6
+        c, g = ctx.saved_tensors[:2]
+        f = ctx.saved_tensors[2] if ctx.has_fine else None
+        n, use_l1, lc, lf = ctx.cfg
+        d_c = torch.empty_like(c) if ctx.needs_input_grad[0] else None
+        d_f = torch.empty_like(f) if (f is not None and ctx.needs_input_grad[1]) else None
+        d_total = N.f32c(d_total, c.device)
+        N.check(N.lib.pnr_rgb_loss_bwd(N.ptr(c), N.ptr(f), N.ptr(g), n, use_l1, lc, lf, N.ptr(d_total), N.ptr(d_c), N.ptr(d_f),
+                                       N.current_stream(c.device)), "pnr_rgb_loss_bwd")
+        return d_c, d_f, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -164,3 +164,60 @@ def gen_rays_device(pose, width, height, focal, z_near, z_far, c=None, device="c
     N.check(N.lib.pnr_gen_rays(m, int(width), int(height), fx, fy, cx, cy, float(z_near), float(z_far), 0,
                                width * height, N.ptr(out), N.current_stream(dev)), "pnr_gen_rays")
     return out
+
+
+def batched_index_select_nd(t, inds):
+    """t (batch, n, ...), inds (batch, k) long -> (batch, k, ...): row inds[b, j] of t[b] (reference util.py:33-42)."""
+    rows = torch.arange(t.shape[0], device=inds.device)[:, None].expand_as(inds)
+    return t[rows, inds]
+
+
+def bbox_sample(bboxes, num_pix):
+    """num_pix pixels drawn inside the bounding boxes of random views (reference util.py:225-240): bboxes (NV, 4) =
+    cmin, rmin, cmax, rmax on the host -> (num_pix, 3) long rows (view, row, col).  Consumes torch's global CPU generator in
+    the reference's order — randint for the views, rand for the columns, rand for the rows, truncated by .long() — so the
+    same torch.manual_seed gives the same pixels (tests/golden/train_batch.npz)."""
+    view = torch.randint(0, bboxes.shape[0], (num_pix,))
+    box = bboxes[view]
+    col = (torch.rand(num_pix) * (box[:, 2] + 1 - box[:, 0]) + box[:, 0]).long()
+    row = (torch.rand(num_pix) * (box[:, 3] + 1 - box[:, 1]) + box[:, 1]).long()
+    return torch.stack((view, row, col), dim=-1)
+
+
+def upload(t, device):
+    """Host tensor -> device through pinned memory, asynchronously.  A copy from pageable memory makes the host wait until
+    the stream has drained, which would put a bubble into every training step; a device tensor passes through."""
+    if t.is_cuda:
+        return t.to(device)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def train_batch(images, poses, focal, c, pix_inds, z_near, z_far):
+    """Rays and ground-truth colours of sampled pixels, gathered on the GPU by libpnr_hip (pnr_train_batch) in place of
+    gen_rays over every view + indexing (train/train.py:280-311).  images (SB, NV, 3, H, W) in [-1, 1] and poses
+    (SB, NV, 4, 4) c2w on the device; focal (SB,) or (SB, 2) and c None or (SB, 2) as the data loader gives them (host or
+    device); pix_inds (SB, B) long on the device, view * H * W + row * W + col.  -> rays (SB, B, 8), rgb_gt (SB, B, 3) in
+    [0, 1].  An index outside [0, NV*H*W) gives a NaN row (the indices are never read on the host)."""
+    from . import _native as N
+    dev = N.same_device(images, poses, pix_inds)
+    if images.dim() != 5 or images.shape[2] != 3:
+        raise ValueError(f"images must be (SB, NV, 3, H, W), got {tuple(images.shape)}")
+    SB, NV, _, H, W = images.shape
+    if tuple(poses.shape) != (SB, NV, 4, 4):
+        raise ValueError(f"poses must be ({SB}, {NV}, 4, 4), got {tuple(poses.shape)}")
+    if pix_inds.dim() != 2 or pix_inds.shape[0] != SB or pix_inds.dtype != torch.long:
+        raise ValueError(f"pix_inds must be ({SB}, B) int64, got {tuple(pix_inds.shape)} {pix_inds.dtype}")
+    images, poses, pix_inds = N.f32c(images), N.f32c(poses), pix_inds.contiguous()
+    focal = upload(torch.as_tensor(focal, dtype=torch.float32), dev)
+    if focal.dim() <= 1:
+        focal = focal.reshape(-1, 1).expand(-1, 2)
+    focal = focal.expand(SB, 2).contiguous()
+    if c is not None:
+        c = upload(torch.as_tensor(c, dtype=torch.float32), dev).reshape(-1, 2).expand(SB, 2).contiguous()
+    B = pix_inds.shape[1]
+    rays = torch.empty(SB, B, 8, device=dev)
+    rgb_gt = torch.empty(SB, B, 3, device=dev)
+    N.check(N.lib.pnr_train_batch(N.ptr(images), N.ptr(poses), N.ptr(focal), N.ptr(c), SB, NV, W, H, float(z_near),
+                                  float(z_far), pix_inds.data_ptr(), B, N.ptr(rays), N.ptr(rgb_gt), N.current_stream(dev)),
+            "pnr_train_batch")
+    return rays, rgb_gt
