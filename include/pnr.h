@@ -24,7 +24,8 @@ extern "C" {
 #endif
 
 #define PNR_VERSION 102          /* 0.1.2: pnr_views.uv_scale_{x,y} (opt-in upstream texel mapping); 101: output strides, per-object ray index stride.
-                                  * Added since, backward compatible (no bump): the training front end, pnr_train_batch / pnr_rgb_loss / pnr_rgb_loss_bwd */
+                                  * Added since, backward compatible (no bump): the training front end, pnr_train_batch / pnr_rgb_loss / pnr_rgb_loss_bwd;
+                                  * the evaluation back end, pnr_eval_frame / pnr_eval_frame_workspace_bytes */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -348,6 +349,39 @@ int32_t pnr_rgb_loss_bwd(const float* coarse_rgb, const float* fine_rgb, const f
                          int32_t use_l1, float lambda_coarse, float lambda_fine,
                          const float* d_total /* 1 float; NULL = 1 */,
                          float* d_coarse_rgb, float* d_fine_rgb /* (n_rays, 3); either may be NULL */, void* stream);
+
+/* ---- evaluation back end: what eval/eval.py:286-347 does with a rendered frame, on the device ---------------------------- */
+/* One frame, where the render left it: x = clamp(rgb, 0, 1) (eval.py:291-293; a NaN stays a NaN), g = 0.5 * gt + 0.5
+ * (eval.py:318, the bits of torch's images * 0.5 + 0.5), both fp32.
+ *   rgb_u8      (uint8) trunc(x * 255.0f): one fp32 product, then truncation — (all_rgb * 255).astype(np.uint8), eval.py:301;
+ *               the byte of a NaN is 0
+ *   compare_u8  the same quantisation of np.hstack((x, g)) (the reference's write_compare strip)
+ *   depth_norm  (depth - z_near) / (z_far - z_near), eval.py:288-289
+ *   metrics[0]  mean over 3 H W elements of (x - g)^2; PSNR (eval.py:324-328, data_range 1) is 10 log10(1 / metrics[0])
+ *   metrics[1]  mean SSIM (eval.py:329-332: skimage compare_ssim, multichannel, data_range 1, restated from the published
+ *               definition): per channel, on the window centres 3 <= row < H - 3, 3 <= col < W - 3 (whole windows only),
+ *               mu = the 7 x 7 mean, v = the sample (co)variance of the window (divisor 48), C1 = 1e-4, C2 = 9e-4,
+ *               S = ((2 mu_x mu_y + C1)(2 v_xy + C2)) / ((mu_x^2 + mu_y^2 + C1)(v_x + v_y + C2)), averaged over centres and
+ *               channels.  The moments are CENTRED sums, sum (x - mu_x)(y - mu_y), in fp64: a white background keeps
+ *               variances around 1e-7.  A NaN in the render makes both metrics NaN.
+ * Strides in floats per pixel (0 = dense: 3, 1): with 4 / 4 and depth = rgb + 3 the frame is read from the packed (N, 4)
+ * per-ray record of pnr_outputs.rgb_stride, where a sharded frame is gathered.  One launch over 16 x 16 tiles that leaves one
+ * partial pair per tile in `workspace`, then one workgroup that adds them in a fixed order (csrc/eval.hip): no atomics, the
+ * same inputs give the same bits.  Every check below is made before any launch:
+ *   PNR_E_NULL       rgb NULL; compare_u8 or metrics without gt; depth_norm without depth; metrics without workspace
+ *   PNR_E_SHAPE      W < 1, H < 1, W * H >= 2^31 or more than 2^23 tiles; a stride below the record's own width;
+ *                    metrics with min(W, H) < 7; depth_norm with z_far == z_near
+ *   PNR_E_WORKSPACE  metrics with fewer workspace bytes than the size function asks for (16 bytes per tile; 0 for a bad shape) */
+uint64_t pnr_eval_frame_workspace_bytes(int32_t W, int32_t H);
+int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride,       /* rendered (H*W) pixels x 3, UNclamped */
+                       const float* depth, int32_t depth_stride,   /* (H*W), or NULL */
+                       const float* gt,                            /* (3, H, W) planar in [-1, 1] as the data loader gives it, or NULL */
+                       int32_t W, int32_t H, float z_near, float z_far,
+                       uint8_t* rgb_u8,                            /* (H, W, 3), or NULL */
+                       uint8_t* compare_u8,                        /* (H, 2W, 3), or NULL */
+                       float* depth_norm,                          /* (H, W), or NULL */
+                       double* metrics,                            /* 2 doubles, or NULL */
+                       void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* Timing hook for bench.py: microseconds between the first and last point-MLP launch of the most recent
  * pnr_render on this thread is NOT kept (no global state); instead the caller brackets calls with

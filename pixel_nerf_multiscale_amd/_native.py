@@ -127,6 +127,8 @@ PROTOTYPES = {
     "pnr_train_batch": (_i32, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _f, _f, _fp, _i64, _fp, _fp, _fp]),
     "pnr_rgb_loss": (_i32, [_fp, _fp, _fp, _i64, _i32, _f, _f, _fp, _fp]),
     "pnr_rgb_loss_bwd": (_i32, [_fp, _fp, _fp, _i64, _i32, _f, _f, _fp, _fp, _fp, _fp]),
+    "pnr_eval_frame_workspace_bytes": (_u64, [_i32, _i32]),
+    "pnr_eval_frame": (_i32, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _f, _f, _fp, _fp, _fp, _fp, _fp, _u64, _fp]),
     "pnr_event_create": (_i32, [C.POINTER(C.c_void_p)]),
     "pnr_event_record": (_i32, [_fp, _fp]),
     "pnr_event_elapsed_ms": (_i32, [_fp, _fp, C.POINTER(C.c_float)]),

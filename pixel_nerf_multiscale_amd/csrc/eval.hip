@@ -1,0 +1,188 @@
+// The back end of the evaluation loop (reference eval/eval.py:286-347) for ONE rendered frame, where it lies on the device:
+// clamp, the truncating uint8 quantisation of the PNGs (:301), the render | ground-truth strip (write_compare), the
+// normalised depth (:288-289), and the two numbers finish.txt is made of — the mean squared error behind PSNR and the mean
+// SSIM (:324-332, as evalio.ssim restates skimage: uniform 7x7 window, sample covariance, whole windows only, per channel).
+// Latency-bound: a 128 x 128 frame is 64 workgroups; the point is that nothing waits on the host.
+#include "pnr_common.h"
+
+namespace pnr {
+
+constexpr int EV_TILE = 16;                        // pixels per tile edge; one thread per pixel
+constexpr int EV_HALO = 3;                         // (7 - 1) / 2
+constexpr int EV_LDS = EV_TILE + 2 * EV_HALO;      // 22
+constexpr int EV_THREADS = EV_TILE * EV_TILE;      // 256 = 4 waves
+constexpr int EV_WIN = 2 * EV_HALO + 1;            // 7
+
+struct EvalArgs {
+    const float* rgb; const float* depth; const float* gt;
+    int rgb_stride, depth_stride, W, H, tiles_x;
+    float z_near, z_range;
+    uint8_t* rgb_u8; uint8_t* compare_u8; float* depth_norm;
+    double* part;                                  // (tiles, 2): squared-error sum, SSIM sum of the tile; NULL = no metrics
+};
+
+// clamp to [0, 1] that keeps a NaN (fminf / fmaxf would turn it into a bound: the host path's metrics are NaN then)
+__device__ __forceinline__ float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+// (x * 255).astype(uint8) of a clamped value: ONE fp32 product, then truncation ((k / 255) * 255 may land just below k); NaN -> 0
+__device__ __forceinline__ uint8_t quant_u8(float x) { return x == x ? (uint8_t)(int)__fmul_rn(x, 255.0f) : (uint8_t)0; }
+
+// Sum of (a, b) over the workgroup, the same bits in every thread.  Order fixed by the launch shape alone: thread t adds
+// t + 128, then t + 64, .., t + 1.
+__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[EV_THREADS], int tid) {
+    red[0][tid] = a;
+    red[1][tid] = b;
+    __syncthreads();
+    for (int s = EV_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
+        __syncthreads();
+    }
+    a = red[0][0];
+    b = red[1][0];
+}
+
+// One workgroup per 16 x 16 tile.  The tile and a 3-pixel halo of the clamped render x and of the ground truth g = 0.5 gt + 0.5
+// go to LDS (all three channels, 11.6 KB); every thread then owns one pixel: its bytes, its depth, its squared error, and — when
+// the pixel is the centre of a whole window — its SSIM term from the 49 taps around it.  The window arithmetic is fp64: mean
+// first, then CENTRED second moments (sum (x - mx)(y - my)), so a white background with variances around 1e-7 keeps them; the
+// MI355X runs fp64 FMAs at half the fp32 rate, and 2 x 49 taps x 3 channels per pixel are nothing next to the render.
+__global__ void __launch_bounds__(EV_THREADS) k_eval_frame(EvalArgs a) {
+    __shared__ float sx[3][EV_LDS][EV_LDS];
+    __shared__ float sg[3][EV_LDS][EV_LDS];
+    __shared__ double red[2][EV_THREADS];
+    const int tid = threadIdx.x, tx = tid & (EV_TILE - 1), ty = tid / EV_TILE;
+    const int x0 = ((int)blockIdx.x % a.tiles_x) * EV_TILE, y0 = ((int)blockIdx.x / a.tiles_x) * EV_TILE;
+    const int W = a.W, H = a.H;
+    const int64_t HW = (int64_t)W * H;
+
+    for (int i = tid; i < EV_LDS * EV_LDS; i += EV_THREADS) {
+        const int ly = i / EV_LDS, lx = i % EV_LDS;
+        const int gy = y0 - EV_HALO + ly, gx = x0 - EV_HALO + lx;
+        float v[3] = {0.0f, 0.0f, 0.0f}, g[3] = {0.0f, 0.0f, 0.0f};       // outside the image: never part of a whole window
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            const int64_t pix = (int64_t)gy * W + gx;
+            const float* p = a.rgb + pix * a.rgb_stride;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                v[c] = clamp01(p[c]);
+                if (a.gt) g[c] = fmaf(a.gt[c * HW + pix], 0.5f, 0.5f);     // the bits of torch's images * 0.5 + 0.5
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { sx[c][ly][lx] = v[c]; sg[c][ly][lx] = g[c]; }
+    }
+    __syncthreads();
+
+    const int gy = y0 + ty, gx = x0 + tx;
+    const bool inside = gy < H && gx < W;
+    const int cy = ty + EV_HALO, cx = tx + EV_HALO;
+    if (inside) {
+        const int64_t pix = (int64_t)gy * W + gx;
+        if (a.rgb_u8) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.rgb_u8[pix * 3 + c] = quant_u8(sx[c][cy][cx]);
+        }
+        if (a.compare_u8) {                                                // np.hstack((render, ground truth)): rows of 2 W pixels
+            uint8_t* row = a.compare_u8 + (int64_t)gy * W * 6;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                row[(int64_t)gx * 3 + c] = quant_u8(sx[c][cy][cx]);
+                row[((int64_t)W + gx) * 3 + c] = quant_u8(clamp01(sg[c][cy][cx]));
+            }
+        }
+        if (a.depth_norm) a.depth_norm[pix] = __fdiv_rn(__fsub_rn(a.depth[pix * a.depth_stride], a.z_near), a.z_range);
+    }
+    if (!a.part) return;                                                   // uniform over the launch
+
+    double se = 0.0, ss = 0.0;
+    if (inside) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double d = (double)sx[c][cy][cx] - (double)sg[c][cy][cx];
+            se += d * d;
+        }
+        if (gy >= EV_HALO && gy < H - EV_HALO && gx >= EV_HALO && gx < W - EV_HALO) {
+            constexpr double NP = EV_WIN * EV_WIN, C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
+            for (int c = 0; c < 3; ++c) {
+                double mx = 0.0, my = 0.0;
+                for (int dy = 0; dy < EV_WIN; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < EV_WIN; ++dx) { mx += (double)sx[c][ty + dy][tx + dx]; my += (double)sg[c][ty + dy][tx + dx]; }
+                mx /= NP;
+                my /= NP;
+                double vx = 0.0, vy = 0.0, vxy = 0.0;
+                for (int dy = 0; dy < EV_WIN; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < EV_WIN; ++dx) {
+                        const double ex = (double)sx[c][ty + dy][tx + dx] - mx, ey = (double)sg[c][ty + dy][tx + dx] - my;
+                        vx += ex * ex; vy += ey * ey; vxy += ex * ey;
+                    }
+                vx /= NP - 1.0; vy /= NP - 1.0; vxy /= NP - 1.0;
+                ss += ((2.0 * mx * my + C1) * (2.0 * vxy + C2)) / ((mx * mx + my * my + C1) * (vx + vy + C2));
+            }
+        }
+    }
+    block_sum2(se, ss, red, tid);
+    if (tid == 0) { a.part[2 * (int64_t)blockIdx.x] = se; a.part[2 * (int64_t)blockIdx.x + 1] = ss; }
+}
+
+// ONE workgroup: thread t adds the tiles t, t + 256, .. in ascending order, then block_sum2 — no atomics, the same inputs give
+// the same bits.  metrics[0] = mean squared error over 3 H W elements, metrics[1] = mean SSIM over 3 (H - 6)(W - 6) windows.
+__global__ void __launch_bounds__(EV_THREADS) k_eval_finish(const double* __restrict__ part, int tiles, int W, int H,
+                                                            double* __restrict__ metrics) {
+    __shared__ double red[2][EV_THREADS];
+    const int tid = threadIdx.x;
+    double se = 0.0, ss = 0.0;
+    for (int t = tid; t < tiles; t += EV_THREADS) { se += part[2 * (int64_t)t]; ss += part[2 * (int64_t)t + 1]; }
+    block_sum2(se, ss, red, tid);
+    if (tid == 0) {
+        metrics[0] = se / (3.0 * (double)W * (double)H);
+        metrics[1] = ss / (3.0 * (double)(W - 2 * EV_HALO) * (double)(H - 2 * EV_HALO));
+    }
+}
+
+static inline int64_t eval_tiles(int32_t W, int32_t H) {
+    return (int64_t)((W + EV_TILE - 1) / EV_TILE) * ((H + EV_TILE - 1) / EV_TILE);
+}
+constexpr int64_t EV_MAX_TILES = (int64_t)1 << 23;        // 2^23 workgroups of 256 threads: a launch stays below 2^32 threads
+
+}  // namespace pnr
+
+using namespace pnr;
+
+extern "C" uint64_t pnr_eval_frame_workspace_bytes(int32_t W, int32_t H) {
+    if (W < 1 || H < 1 || (int64_t)W * H >= ((int64_t)1 << 31)) return 0;
+    return (uint64_t)eval_tiles(W, H) * 2 * sizeof(double);
+}
+
+extern "C" int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride, const float* depth, int32_t depth_stride, const float* gt,
+                                  int32_t W, int32_t H, float z_near, float z_far, uint8_t* rgb_u8, uint8_t* compare_u8,
+                                  float* depth_norm, double* metrics, void* workspace, uint64_t workspace_bytes, void* stream) {
+    if (!rgb) return PNR_E_NULL;
+    if ((compare_u8 || metrics) && !gt) return PNR_E_NULL;
+    if (depth_norm && !depth) return PNR_E_NULL;
+    if (metrics && !workspace) return PNR_E_NULL;
+    if (W < 1 || H < 1 || (int64_t)W * H >= ((int64_t)1 << 31)) return PNR_E_SHAPE;
+    if (rgb_stride == 0) rgb_stride = 3;
+    if (depth_stride == 0) depth_stride = 1;
+    if (rgb_stride < 3 || depth_stride < 1) return PNR_E_SHAPE;
+    if (metrics && (W < EV_WIN || H < EV_WIN)) return PNR_E_SHAPE;
+    if (depth_norm && z_far == z_near) return PNR_E_SHAPE;
+    const int64_t tiles = eval_tiles(W, H);
+    if (tiles > EV_MAX_TILES) return PNR_E_SHAPE;
+    if (metrics && workspace_bytes < pnr_eval_frame_workspace_bytes(W, H)) return PNR_E_WORKSPACE;
+    if (!rgb_u8 && !compare_u8 && !depth_norm && !metrics) return PNR_OK;
+    EvalArgs a;
+    a.rgb = rgb; a.depth = depth; a.gt = gt;
+    a.rgb_stride = rgb_stride; a.depth_stride = depth_stride; a.W = W; a.H = H; a.tiles_x = (W + EV_TILE - 1) / EV_TILE;
+    a.z_near = z_near; a.z_range = z_far - z_near;
+    a.rgb_u8 = rgb_u8; a.compare_u8 = compare_u8; a.depth_norm = depth_norm;
+    a.part = metrics ? (double*)workspace : nullptr;
+    hipLaunchKernelGGL(k_eval_frame, dim3((unsigned)tiles), dim3(EV_THREADS), 0, (hipStream_t)stream, a);
+    PNR_LAUNCH_CHECK();
+    if (metrics) {
+        hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(EV_THREADS), 0, (hipStream_t)stream, (const double*)workspace, (int)tiles, W,
+                           H, metrics);
+        PNR_LAUNCH_CHECK();
+    }
+    return PNR_OK;
+}

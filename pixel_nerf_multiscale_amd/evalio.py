@@ -1,6 +1,7 @@
 """
 On-disk / wire formats around the render path, so an evaluation driver built on this package reads
-and writes what the reference's eval scripts do.  Pure host-side parsing and arithmetic.
+and writes what the reference's eval scripts do.  Parsing and arithmetic on the host; evaluate(metrics="device") leaves the
+per-frame work (clamp, quantisation, PSNR / SSIM sums, normalised depth) to the HIP back end, util.eval_frame.
 
 * finish.txt resume log      reference eval/eval.py:113-133,360-362   one line per object: "<name> <psnr> <ssim> <cnt>"
 * source-view look-up table   reference eval/eval.py:156-165           viewlist/src_*.txt: "<cat> <obj> <view> [<view> ...]"
@@ -141,7 +142,7 @@ def write_png(path, rgb_u8):
 def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None, eval_view_list=None,
              include_src=False, scale=1.0, multicat=False, gpu_id=None, ray_batch_size=50000, no_compare_gt=False,
              write_compare=False, write_images=True, max_objects=50, z_near=None, z_far=None,
-             verbose=True, seed=None):
+             verbose=True, seed=None, metrics="host", write_depth=False):
     """The per-object evaluation loop of the reference (eval/eval.py:186-362) on this package's renderer.
 
     dataset: a sequence of per-object dicts as the reference's datasets yield them (unbatched): "path", "images"
@@ -165,9 +166,25 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
     Deliberate differences: the rays of all target views are not concatenated and re-split (:250-267) — a view is the unit;
     the random jitter is keyed by (seed, ray): one base seed per call (`seed`, else drawn from torch's generator on rank 0
     and broadcast) and a seed derived per (object, view), so neither the chunk size, nor the number of ranks, nor a resume changes a pixel; SSIM is this module's restatement
-    (skimage is not importable here: parity unpinned); depth EXR / colour-mapped depth outputs (:303-316) are not written."""
+    (skimage is not importable here: parity unpinned); depth EXR / colour-mapped depth outputs (:303-316) are not written
+    (they need cv2, which this package does not depend on).
+
+    write_depth=True writes "<obj>/<view:06>_depth.npy" instead: float32 (H, W), (depth - z_near) / (z_far - z_near)
+    (:288-289), with either back end.
+
+    metrics="host" (the default) is the reference's recipe: every frame is copied to the host as fp32 and numpy / scipy do
+    the rest.  metrics="device": util.eval_frame (pnr_eval_frame) runs on each frame where the render left it — the object's
+    ground-truth views are uploaded once, the per-view (mse, ssim) pairs collect in one (n_views, 2) fp64 device buffer, and
+    only what will be written (uint8 frames, compare strips, normalised depth: 3 bytes per pixel instead of 16) travels to
+    pinned host buffers, asynchronously; the host waits ONCE per object, before it writes that object's files and its
+    finish.txt line.  PSNR is 10 log10(1 / mse) on the host in fp64.  Under a process group every rank computes the metrics
+    (the return value is the same everywhere) and rank 0 alone copies bytes out and writes.  A ground truth whose size differs
+    from the render's (scale != 1 with comparison) is a ValueError: there is no resampling on the device."""
+    import math
     import torch.distributed as dist
     from . import util
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
     dev = net.poses.device
     z_near = float(getattr(dataset, "z_near", None) if z_near is None else z_near)
     z_far = float(getattr(dataset, "z_far", None) if z_far is None else z_far)
@@ -210,6 +227,14 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
         # and a rank of a one-process-per-GPU job has exactly one
         from .render.nerf import _ShardedRenderWrapper
         render_par = _ShardedRenderWrapper(net, renderer, simple_output=True).eval()
+    pin = {}
+
+    def pinned(name, shape, dtype):
+        # metrics="device": the pinned host buffers of an object's outputs, kept for the next object of the same shape
+        t = pin.get(name)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = pin[name] = torch.empty(shape, dtype=dtype, pin_memory=True)
+        return t
     was_training = net.training
     net.eval()
     try:
@@ -235,6 +260,9 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
                         import warnings
                         warnings.warn(f"Inexact scaling, please check {scale} times ({H}, {W}) is integral")
                     H, W = Ht, Wt
+                if metrics == "device" and not no_compare_gt and (H, W) != tuple(images.shape[-2:]):
+                    raise ValueError(f"metrics='device' compares a {H} x {W} render with {tuple(images.shape[-2:])} ground truth: "
+                                     "use scale=1 or no_compare_gt")
                 src = viewlist[cat_name + "/" + obj_base] if use_lut else fixed_source
                 src_mask = torch.zeros(NV, dtype=torch.bool)
                 src_mask[src] = True
@@ -265,52 +293,108 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
                             dist.broadcast(h, src=0)
                             m.copy_(h)
                     net.encoder.set_latents(maps)
-                frames, pending = [], None
-                for vi in novel.tolist():
+
+                def render_view(vi):
                     # keyed by (object, view), not by a running count: a resumed run draws what the uninterrupted run drew
                     view_seed = frame_seed(frame_seed(base_seed, obj_idx), vi)
                     if render_par is None:
                         keep_seed, renderer.forced_seed = renderer.forced_seed, view_seed
                         try:
-                            rgb, depth = renderer.render_image(net, poses[vi], W, H, focal * scale, z_near, z_far,
-                                                               c=None if c is None else c * scale)
+                            return renderer.render_image(net, poses[vi], W, H, focal * scale, z_near, z_far,
+                                                         c=None if c is None else c * scale)
                         finally:
                             renderer.forced_seed = keep_seed
-                    else:
-                        rays = util.gen_rays_device(poses[vi], W, H, focal * scale, z_near, z_far,
-                                                    c=None if c is None else c * scale, device=dev)
-                        parts, at = [], 0
-                        for r in torch.split(rays, ray_batch_size, dim=0):
-                            parts.append(render_par(r[None], ray_index_base=at, seed=view_seed))
-                            at += r.shape[0]
-                        rgb = torch.cat([p[0][0] for p in parts], 0).reshape(H, W, 3)
-                        depth = torch.cat([p[1][0] for p in parts], 0).reshape(H, W)
-                    nxt = renderer.frame_to_host_async(rgb, depth)          # D2H overlaps the next view's render
+                    rays = util.gen_rays_device(poses[vi], W, H, focal * scale, z_near, z_far,
+                                                c=None if c is None else c * scale, device=dev)
+                    parts, at = [], 0
+                    for r in torch.split(rays, ray_batch_size, dim=0):
+                        parts.append(render_par(r[None], ray_index_base=at, seed=view_seed))
+                        at += r.shape[0]
+                    return (torch.cat([p[0][0] for p in parts], 0).reshape(H, W, 3),
+                            torch.cat([p[1][0] for p in parts], 0).reshape(H, W))
+
+                obj_out = os.path.join(output_dir, obj_name) if writes_files else None
+                if metrics == "device":
+                    views = novel.tolist()
+                    n_gen = len(views)
+                    compare = not no_compare_gt and n_gen > 0
+                    want_u8, want_cmp = writes_files and write_images, writes_files and write_compare and compare
+                    want_dn = writes_files and write_depth
+                    gt_dev = util.upload(images[tgt_mask].float().contiguous(), dev) if compare else None
+                    pairs = torch.empty(n_gen, 2, dtype=torch.float64, device=dev) if compare else None
+                    u8_h = pinned("u8", (n_gen, H, W, 3), torch.uint8) if want_u8 else None
+                    cmp_h = pinned("cmp", (n_gen, H, 2 * W, 3), torch.uint8) if want_cmp else None
+                    dn_h = pinned("dn", (n_gen, H, W), torch.float32) if want_dn else None
+                    for i, vi in enumerate(views):
+                        rgb, depth = render_view(vi)
+                        u8, cmp, dn, _ = util.eval_frame(rgb, depth if want_dn else None, gt_dev[i] if compare else None,
+                                                         z_near=z_near, z_far=z_far, want_u8=want_u8, want_compare=want_cmp,
+                                                         want_depth=want_dn, want_metrics=compare,
+                                                         metrics_out=pairs[i] if compare else None)
+                        for dst, src_t in ((u8_h, u8), (cmp_h, cmp), (dn_h, dn)):
+                            if dst is not None:
+                                dst[i].copy_(src_t, non_blocking=True)
+                    pairs_h = None
+                    if compare:
+                        pairs_h = pinned("pairs", (n_gen, 2), torch.float64)
+                        pairs_h.copy_(pairs, non_blocking=True)
+                    if n_gen:
+                        done = torch.cuda.Event()
+                        done.record(torch.cuda.current_stream(dev))
+                        done.synchronize()                                  # the one wait of this object
+                    if writes_files and n_gen and (want_u8 or want_cmp or want_dn):
+                        os.makedirs(obj_out, exist_ok=True)
+                    curr_psnr = curr_ssim = 0.0
+                    for i, vi in enumerate(views):
+                        if want_u8:
+                            write_png(os.path.join(obj_out, "{:06}.png".format(vi)), u8_h[i].numpy())
+                        if want_dn:
+                            np.save(os.path.join(obj_out, "{:06}_depth.npy".format(vi)), dn_h[i].numpy())
+                        if compare:
+                            mse, s = (float(x) for x in pairs_h[i])
+                            curr_ssim += s
+                            curr_psnr += float("inf") if mse == 0.0 else 10.0 * math.log10(1.0 / mse) if mse > 0.0 else float("nan")
+                            if want_cmp:
+                                write_png(os.path.join(obj_out, "{:06}_compare.png".format(vi)), cmp_h[i].numpy())
+                    if compare:
+                        curr_psnr /= n_gen
+                        curr_ssim /= n_gen
+                else:
+                    frames, depths, pending = [], [], None
+                    for vi in novel.tolist():
+                        rgb, depth = render_view(vi)
+                        nxt = renderer.frame_to_host_async(rgb, depth)          # D2H overlaps the next view's render
+                        if pending is not None:
+                            pending[2].synchronize()
+                            frames.append(pending[0])
+                            depths.append(pending[1])
+                        pending = nxt
                     if pending is not None:
                         pending[2].synchronize()
                         frames.append(pending[0])
-                    pending = nxt
-                if pending is not None:
-                    pending[2].synchronize()
-                    frames.append(pending[0])
-                all_rgb = torch.clamp(torch.stack(frames), 0.0, 1.0).numpy() if frames else np.zeros((0, H, W, 3), np.float32)
-                n_gen = len(frames)
-                if writes_files and write_images:
-                    obj_out = os.path.join(output_dir, obj_name)
-                    os.makedirs(obj_out, exist_ok=True)
-                    for i in range(n_gen):
-                        write_png(os.path.join(obj_out, "{:06}.png".format(int(novel[i]))), quantize_uint8(all_rgb[i]))
-                curr_psnr = curr_ssim = 0.0
-                if not no_compare_gt and n_gen:
-                    gt = (images * 0.5 + 0.5)[tgt_mask].permute(0, 2, 3, 1).contiguous().numpy()
-                    for i in range(n_gen):
-                        curr_ssim += ssim(all_rgb[i], gt[i], data_range=1)
-                        curr_psnr += psnr(all_rgb[i], gt[i], data_range=1)
-                        if writes_files and write_compare:
-                            write_png(os.path.join(output_dir, obj_name, "{:06}_compare.png".format(int(novel[i]))),
-                                      quantize_uint8(np.hstack((all_rgb[i], gt[i]))))
-                    curr_psnr /= n_gen
-                    curr_ssim /= n_gen
+                        depths.append(pending[1])
+                    all_rgb = torch.clamp(torch.stack(frames), 0.0, 1.0).numpy() if frames else np.zeros((0, H, W, 3), np.float32)
+                    n_gen = len(frames)
+                    if writes_files and write_images:
+                        os.makedirs(obj_out, exist_ok=True)
+                        for i in range(n_gen):
+                            write_png(os.path.join(obj_out, "{:06}.png".format(int(novel[i]))), quantize_uint8(all_rgb[i]))
+                    if writes_files and write_depth and n_gen:
+                        os.makedirs(obj_out, exist_ok=True)
+                        all_depth = ((torch.stack(depths) - z_near) / (z_far - z_near)).numpy()       # eval.py:288-289
+                        for i in range(n_gen):
+                            np.save(os.path.join(obj_out, "{:06}_depth.npy".format(int(novel[i]))), all_depth[i])
+                    curr_psnr = curr_ssim = 0.0
+                    if not no_compare_gt and n_gen:
+                        gt = (images * 0.5 + 0.5)[tgt_mask].permute(0, 2, 3, 1).contiguous().numpy()
+                        for i in range(n_gen):
+                            curr_ssim += ssim(all_rgb[i], gt[i], data_range=1)
+                            curr_psnr += psnr(all_rgb[i], gt[i], data_range=1)
+                            if writes_files and write_compare:
+                                write_png(os.path.join(output_dir, obj_name, "{:06}_compare.png".format(int(novel[i]))),
+                                          quantize_uint8(np.hstack((all_rgb[i], gt[i]))))
+                        curr_psnr /= n_gen
+                        curr_ssim /= n_gen
                 total_psnr += curr_psnr
                 total_ssim += curr_ssim
                 cnt += 1

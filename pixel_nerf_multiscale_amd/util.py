@@ -221,3 +221,63 @@ def train_batch(images, poses, focal, c, pix_inds, z_near, z_far):
                                   float(z_far), pix_inds.data_ptr(), B, N.ptr(rays), N.ptr(rgb_gt), N.current_stream(dev)),
             "pnr_train_batch")
     return rays, rgb_gt
+
+
+def _pixel_stride(t, H, W, last, name):
+    """Floats per pixel of a frame that is dense or a regular view into a per-pixel record (row-major pixels, unit stride
+    inside the pixel): (H, W, 3) with strides (W s, s, 1), or (H, W) with strides (W s, s)."""
+    want = (H, W, last) if last else (H, W)
+    if tuple(t.shape) != want or t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32 {want}, got {t.dtype} {tuple(t.shape)}")
+    if t.is_contiguous():
+        return max(last, 1)
+    st = t.stride()
+    s = st[1]
+    if s < max(last, 1) or (last and st[2] != 1) or (H > 1 and st[0] != W * s):
+        raise ValueError(f"{name} must be dense or a view into a per-pixel record, got strides {st}")
+    return s
+
+
+def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True, want_compare=False, want_depth=False,
+               want_metrics=True, metrics_out=None):
+    """What the evaluation loop does with a rendered frame (eval/eval.py:286-347), on the GPU by libpnr_hip (pnr_eval_frame):
+    rgb (H, W, 3) UNclamped, depth (H, W), both float32, dense or views into the packed (H*W, 4) per-ray record; gt (3, H, W)
+    in [-1, 1] as the data loader gives it.  -> (rgb_u8 (H, W, 3) uint8, compare_u8 (H, 2W, 3) uint8, depth_norm (H, W)
+    float32, metrics (2,) float64 = [mean squared error, mean SSIM]) on the device, None for what was not asked for.
+    metrics_out: a contiguous (2,) float64 device tensor to write the pair into (one row of a per-object buffer).  Nothing
+    here waits for the device; PSNR = 10 log10(1 / metrics[0]) is the caller's, on the host."""
+    from . import _native as N
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"rgb must be (H, W, 3), got {tuple(rgb.shape)}")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    if (want_compare or want_metrics) and gt is None:
+        raise ValueError("want_compare / want_metrics need the ground truth gt")
+    if want_depth and depth is None:
+        raise ValueError("want_depth needs depth")
+    if not want_depth:
+        depth = None
+    if not (want_compare or want_metrics):
+        gt = None
+    dev = N.same_device(rgb, depth, gt, metrics_out)
+    rs = _pixel_stride(rgb, H, W, 3, "rgb")
+    ds = 0 if depth is None else _pixel_stride(depth, H, W, 0, "depth")
+    if gt is not None:
+        if tuple(gt.shape) != (3, H, W) or gt.dtype != torch.float32:
+            raise ValueError(f"gt must be float32 (3, {H}, {W}), got {gt.dtype} {tuple(gt.shape)}")
+        gt = gt.contiguous()
+    rgb_u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if want_u8 else None
+    compare_u8 = torch.empty(H, 2 * W, 3, dtype=torch.uint8, device=dev) if want_compare else None
+    depth_norm = torch.empty(H, W, dtype=torch.float32, device=dev) if want_depth else None
+    metrics = ws = None
+    nbytes = 0
+    if want_metrics:
+        metrics = torch.empty(2, dtype=torch.float64, device=dev) if metrics_out is None else metrics_out
+        if tuple(metrics.shape) != (2,) or metrics.dtype != torch.float64 or not metrics.is_contiguous():
+            raise ValueError(f"metrics_out must be a contiguous float64 (2,), got {metrics.dtype} {tuple(metrics.shape)}")
+        nbytes = int(N.lib.pnr_eval_frame_workspace_bytes(W, H))
+        ws = torch.empty(max(nbytes, 16) // 8, dtype=torch.float64, device=dev)
+    dp = lambda t: None if t is None else t.data_ptr()
+    N.check(N.lib.pnr_eval_frame(rgb.data_ptr(), rs, dp(depth), ds, dp(gt), W, H, float(z_near), float(z_far), dp(rgb_u8),
+                                 dp(compare_u8), dp(depth_norm), dp(metrics), dp(ws), nbytes, N.current_stream(dev)),
+            "pnr_eval_frame")
+    return rgb_u8, compare_u8, depth_norm, metrics
