@@ -25,7 +25,8 @@ extern "C" {
 
 #define PNR_VERSION 102          /* 0.1.2: pnr_views.uv_scale_{x,y} (opt-in upstream texel mapping); 101: output strides, per-object ray index stride.
                                   * Added since, backward compatible (no bump): the training front end, pnr_train_batch / pnr_rgb_loss / pnr_rgb_loss_bwd;
-                                  * the evaluation back end, pnr_eval_frame / pnr_eval_frame_workspace_bytes */
+                                  * the evaluation back end, pnr_eval_frame / pnr_eval_frame_workspace_bytes; mesh extraction,
+                                  * pnr_grid_points / pnr_mc_workspace_bytes / pnr_mc_count / pnr_mc_emit */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -382,6 +383,45 @@ int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride,       /* rendered (
                        float* depth_norm,                          /* (H, W), or NULL */
                        double* metrics,                            /* 2 doubles, or NULL */
                        void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* Mesh extraction (util/recon.py: marching_cubes, with util.gen_grid util.py:98-115 and PyMCubes behind it), csrc/mesh.hip.
+ *
+ * pnr_grid_points writes points [first, first + count) of the ij-indexed grid gen_grid(*zip(c1, c2, reso), ij_indexing=True):
+ * linear index (i ny + j) nz + k, coordinate = np.linspace(lo, hi, n, dtype=float32)[index] bit for bit (step = (hi - lo) /
+ * (n - 1) in fp64, index * step + lo in fp64 unfused, the last sample hi itself, ONE rounding to fp32).  With fake_viewdirs it
+ * also writes -p / |p| in fp32 (recon.py:54); a point of length 0 gets (0, 0, 0) where the reference's 0 / 0 is NaN.  c1, c2,
+ * reso are HOST arrays of 3 (like c2w of pnr_gen_rays); xyz_out / viewdirs_out (count, 3) on the device.
+ *   PNR_E_NULL   c1, c2, reso or xyz_out NULL; fake_viewdirs without viewdirs_out
+ *   PNR_E_SHAPE  an axis < 1, 2^31 points or more, first / count negative or past the grid's end */
+int32_t pnr_grid_points(const double* c1, const double* c2, const int32_t* reso, int64_t first, int64_t count,
+                        int32_t fake_viewdirs, float* xyz_out, float* viewdirs_out, void* stream);
+
+/* Marching cubes over an (nx, ny, nz) fp32 field, element p = (i ny + j) nz + k read at field[p * stride]: stride 4 and
+ * field = out + 3 consume the sigma column of pnr_point_mlp's (N, 4) output where it lies.  Output sizes depend on the data,
+ * so there are two calls and ONE host read between them: pnr_mc_count leaves the number of vertices and of triangles in
+ * counts[0], counts[1] (device int64) and the offsets in `workspace`; the caller reads the counts, allocates, and calls
+ * pnr_mc_emit with the SAME field, iso and workspace.  pnr_mc_emit guards every store against the n_vertices / n_triangles it
+ * is given.
+ *   inside      a grid point is inside iff (double)f >= iso; a NaN is outside
+ *   vertices    one per grid edge whose two ends differ, owned by the edge's lower grid point; numbered in linear grid-point
+ *               order, then by axis 0, 1, 2.  Index coordinate along the edge's axis a + t, t = (iso - fa) / (fb - fa) in fp64
+ *               from the widened fp32 values; output = v * scale + origin per axis, two separately rounded fp64 operations
+ *               (numpy's `vertices *= s; vertices + c1`).  origin, scale: HOST arrays of 3 doubles.
+ *   triangles   per cell by the case table csrc/mc_tables.h (derived by tools/gen_mc_tables.py), ordered by linear cell index,
+ *               then in table order; normals point from inside to outside, so a closed surface around an f >= iso region
+ *               has positive signed volume.  (V, 3) fp64 vertices, (T, 3) int32 triangles, both on the device.
+ * Integer scans in a fixed order, no atomics: the result equals a sequential walk index for index.  Every check is made
+ * before any launch:
+ *   PNR_E_NULL       field, workspace, counts, origin or scale NULL; vertices / triangles NULL with a count above 0
+ *   PNR_E_SHAPE      an axis < 2, nx ny nz > 2^28 (5 triangles per cell stay inside int32), stride < 1, a negative count
+ *   PNR_E_WORKSPACE  fewer workspace bytes than pnr_mc_workspace_bytes (about 10 per grid point; 0 for a bad shape)
+ *   PNR_E_ALIGN      workspace not 16-byte aligned */
+uint64_t pnr_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int32_t pnr_mc_count(const float* field, int32_t stride, int32_t nx, int32_t ny, int32_t nz, double iso,
+                     void* workspace, uint64_t workspace_bytes, int64_t* counts, void* stream);
+int32_t pnr_mc_emit(const float* field, int32_t stride, int32_t nx, int32_t ny, int32_t nz, double iso,
+                    const double* origin, const double* scale, const void* workspace, uint64_t workspace_bytes,
+                    int64_t n_vertices, int64_t n_triangles, double* vertices, int32_t* triangles, void* stream);
 
 /* Timing hook for bench.py: microseconds between the first and last point-MLP launch of the most recent
  * pnr_render on this thread is NOT kept (no global state); instead the caller brackets calls with

@@ -129,6 +129,11 @@ PROTOTYPES = {
     "pnr_rgb_loss_bwd": (_i32, [_fp, _fp, _fp, _i64, _i32, _f, _f, _fp, _fp, _fp, _fp]),
     "pnr_eval_frame_workspace_bytes": (_u64, [_i32, _i32]),
     "pnr_eval_frame": (_i32, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _f, _f, _fp, _fp, _fp, _fp, _fp, _u64, _fp]),
+    "pnr_grid_points": (_i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _i64, _i64, _i32, _fp, _fp, _fp]),
+    "pnr_mc_workspace_bytes": (_u64, [_i32, _i32, _i32]),
+    "pnr_mc_count": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, _fp, _u64, _fp, _fp]),
+    "pnr_mc_emit": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _fp, _u64,
+                           _i64, _i64, _fp, _fp, _fp]),
     "pnr_event_create": (_i32, [C.POINTER(C.c_void_p)]),
     "pnr_event_record": (_i32, [_fp, _fp]),
     "pnr_event_elapsed_ms": (_i32, [_fp, _fp, C.POINTER(C.c_float)]),

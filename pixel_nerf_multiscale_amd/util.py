@@ -166,6 +166,35 @@ def gen_rays_device(pose, width, height, focal, z_near, z_far, c=None, device="c
     return out
 
 
+def gen_grid(*args, ij_indexing=False):
+    """Grid points of len(args) axes, each arg (lo, hi, size) sampled at np.linspace(lo, hi, size) in fp32 ->
+    (prod sizes, len(args)) float32 on the host (reference util.py:98-115).  ij_indexing=True: the first axis varies
+    slowest, linear index (i ny + j) nz + k; False: numpy's "xy" meshgrid order, the reference's default."""
+    axes = [np.linspace(lo, hi, int(size), dtype=np.float32) for lo, hi, size in args]
+    mesh = np.meshgrid(*axes, indexing="ij" if ij_indexing else "xy")
+    return torch.from_numpy(np.stack([m.reshape(-1) for m in mesh], axis=-1))
+
+
+def gen_grid_device(c1, c2, reso, first=0, count=None, fake_viewdirs=False, device="cuda"):
+    """Points [first, first + count) of gen_grid(*zip(c1, c2, reso), ij_indexing=True), written on the GPU by libpnr_hip
+    (pnr_grid_points) with the bits of the host version -> xyz (count, 3) [, viewdirs (count, 3) = -p / |p|, the fake view
+    directions of recon.marching_cubes; (0, 0, 0) for a point of length 0] on `device`."""
+    import ctypes as C
+    from . import _native as N
+    if len(c1) != 3 or len(c2) != 3 or len(reso) != 3:
+        raise ValueError("c1, c2 and reso must have 3 entries each")
+    reso = [int(r) for r in reso]
+    n = reso[0] * reso[1] * reso[2]
+    count = n - int(first) if count is None else int(count)
+    dev = torch.device(device)
+    xyz = torch.empty(max(count, 0), 3, device=dev, dtype=torch.float32)
+    dirs = torch.empty_like(xyz) if fake_viewdirs else None
+    N.check(N.lib.pnr_grid_points((C.c_double * 3)(*[float(v) for v in c1]), (C.c_double * 3)(*[float(v) for v in c2]),
+                                  (C.c_int32 * 3)(*reso), int(first), count, int(bool(fake_viewdirs)), xyz.data_ptr(),
+                                  None if dirs is None else dirs.data_ptr(), N.current_stream(dev)), "pnr_grid_points")
+    return (xyz, dirs) if fake_viewdirs else xyz
+
+
 def batched_index_select_nd(t, inds):
     """t (batch, n, ...), inds (batch, k) long -> (batch, k, ...): row inds[b, j] of t[b] (reference util.py:33-42)."""
     rows = torch.arange(t.shape[0], device=inds.device)[:, None].expand_as(inds)
