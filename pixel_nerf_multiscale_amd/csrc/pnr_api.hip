@@ -39,8 +39,6 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
 
 using namespace pnr;
 
-static inline uint64_t align256(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
-
 extern "C" int32_t pnr_version(void) { return PNR_VERSION; }
 
 extern "C" const char* pnr_error_string(int32_t code) {
@@ -75,11 +73,11 @@ static int32_t check_model(const pnr_params* prm, const pnr_mlp* mlp, const pnr_
         L += vw->lat_c[i];
     }
     if (L != mlp->d_latent) return PNR_E_SHAPE;
-    int n_lin_z = mlp->combine_layer < mlp->n_blocks ? mlp->combine_layer : mlp->n_blocks;
-    if (n_lin_z < 0) return PNR_E_SHAPE;
+    const int nz = n_lin_z(mlp);
+    if (nz < 0) return PNR_E_SHAPE;
     for (int b = 0; b < mlp->n_blocks; ++b) {
         if (!mlp->fc0_w[b] || !mlp->fc0_b[b] || !mlp->fc1_w[b] || !mlp->fc1_b[b]) return PNR_E_NULL;
-        if (b < n_lin_z && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return PNR_E_NULL;
+        if (b < nz && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return PNR_E_NULL;
     }
     if (vw->n_views > 1 && mlp->combine_layer >= mlp->n_blocks) return PNR_E_UNSUPPORTED;
     if (prm->precision != PNR_F32 && prm->precision != PNR_BF16 && prm->precision != PNR_F16 && prm->precision != PNR_BF16X3)
@@ -99,6 +97,26 @@ static int32_t point_dispatch(const pnr_params* prm, const pnr_mlp* mlp, const p
     return point_mfma(prm, mlp, vw, src, n_points, pts_per_obj, out, ws, ws_bytes, s);
 }
 
+// The point source of a call (rays + z, or xyz + viewdirs) and its sizes, after check_model.  need_f32_maps: the caller reads
+// the fp32 latent maps whatever the precision (the training path).
+static int32_t point_source(const pnr_views* views, const float* rays, const float* z, int32_t K, const float* xyz,
+                            const float* viewdirs, int64_t n_points, int64_t points_per_obj, bool need_f32_maps, PointSrc* src) {
+    if (need_f32_maps)
+        for (int i = 0; i < views->n_levels; ++i)
+            if (!views->latent[i]) return PNR_E_NULL;
+    *src = PointSrc{};
+    if (rays) {
+        if (!z || K <= 0) return PNR_E_NULL;
+        src->rays = rays; src->z = z; src->K = K;
+        if (n_points % K != 0) return PNR_E_SHAPE;
+    } else {
+        if (!xyz || !viewdirs) return PNR_E_NULL;
+        src->xyz = xyz; src->dirs = viewdirs; src->K = 1;
+    }
+    if (n_points < 0 || points_per_obj <= 0 || n_points != points_per_obj * views->n_objs) return PNR_E_SHAPE;
+    return PNR_OK;
+}
+
 extern "C" int32_t pnr_point_mlp(const pnr_params* params, const pnr_mlp* mlp, const pnr_views* views,
                                  const float* rays, const float* z, int32_t K, const float* xyz,
                                  const float* viewdirs, int64_t n_points, int64_t points_per_obj, float* out,
@@ -107,16 +125,9 @@ extern "C" int32_t pnr_point_mlp(const pnr_params* params, const pnr_mlp* mlp, c
     if (rc) return rc;
     if (!out) return PNR_E_NULL;
     if (((uintptr_t)out & 15) != 0) return PNR_E_ALIGN;
-    PointSrc src{};
-    if (rays) {
-        if (!z || K <= 0) return PNR_E_NULL;
-        src.rays = rays; src.z = z; src.K = K;
-        if (n_points % K != 0) return PNR_E_SHAPE;
-    } else {
-        if (!xyz || !viewdirs) return PNR_E_NULL;
-        src.xyz = xyz; src.dirs = viewdirs; src.K = 1;
-    }
-    if (n_points < 0 || points_per_obj <= 0 || n_points != points_per_obj * views->n_objs) return PNR_E_SHAPE;
+    PointSrc src;
+    rc = point_source(views, rays, z, K, xyz, viewdirs, n_points, points_per_obj, false, &src);
+    if (rc) return rc;
     if (!workspace && n_points > 0) return PNR_E_NULL;
     return point_dispatch(params, mlp, views, src, n_points, points_per_obj, out, workspace, workspace_bytes,
                           (hipStream_t)stream);
@@ -128,10 +139,10 @@ static int32_t check_mlp_f32(const pnr_mlp* mlp) {
     if (mlp->d_in <= 0 || mlp->d_latent < 0 || mlp->d_hidden <= 0 || mlp->d_out <= 0 || mlp->n_blocks < 0 ||
         mlp->n_blocks > PNR_MAX_BLOCKS) return PNR_E_SHAPE;
     if (!mlp->lin_in_w || !mlp->lin_in_b || !mlp->lin_out_w || !mlp->lin_out_b) return PNR_E_NULL;
-    const int n_lin_z = mlp->combine_layer < mlp->n_blocks ? mlp->combine_layer : mlp->n_blocks;
+    const int nz = n_lin_z(mlp);
     for (int b = 0; b < mlp->n_blocks; ++b) {
         if (!mlp->fc0_w[b] || !mlp->fc0_b[b] || !mlp->fc1_w[b] || !mlp->fc1_b[b]) return PNR_E_NULL;
-        if (mlp->d_latent > 0 && b < n_lin_z && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return PNR_E_NULL;
+        if (mlp->d_latent > 0 && b < nz && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return PNR_E_NULL;
     }
     return PNR_OK;
 }
@@ -171,19 +182,7 @@ static int32_t point_args(const pnr_params* params, const pnr_mlp* mlp, const pn
                           int64_t points_per_obj, PointSrc* src) {
     int32_t rc = check_model(params, mlp, views);
     if (rc) return rc;
-    for (int i = 0; i < views->n_levels; ++i)
-        if (!views->latent[i]) return PNR_E_NULL;      // the training path reads the fp32 maps
-    *src = PointSrc{};
-    if (rays) {
-        if (!z || K <= 0) return PNR_E_NULL;
-        src->rays = rays; src->z = z; src->K = K;
-        if (n_points % K != 0) return PNR_E_SHAPE;
-    } else {
-        if (!xyz || !viewdirs) return PNR_E_NULL;
-        src->xyz = xyz; src->dirs = viewdirs; src->K = 1;
-    }
-    if (n_points < 0 || points_per_obj <= 0 || n_points != points_per_obj * views->n_objs) return PNR_E_SHAPE;
-    return PNR_OK;
+    return point_source(views, rays, z, K, xyz, viewdirs, n_points, points_per_obj, true, src);
 }
 
 extern "C" uint64_t pnr_train_tape_bytes(const pnr_mlp* mlp, const pnr_views* views, int64_t n_points) {
@@ -238,16 +237,16 @@ struct RenderWs { uint64_t zc, zf, rgbs, w, rgb, depth, rays, point, total; };
 static RenderWs carve(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, int64_t n, const pnr_mlp* fine = nullptr) {
     RenderWs r;
     uint64_t Kc = prm->n_coarse, Kt = (uint64_t)prm->n_coarse + prm->n_fine, off = 0;
-    r.zc = off; off += align256(n * Kc * 4);
-    r.zf = off; off += align256(n * Kt * 4);
-    r.rgbs = off; off += align256(n * Kt * 16);
-    r.w = off; off += align256(n * Kt * 4);
-    r.rgb = off; off += align256(n * 12);
-    r.depth = off; off += align256(n * 4);
-    r.rays = off; off += align256(n * 32);          // pnr_render_camera on the fp32 path materialises its rays here
+    r.zc = off; off += round_up_256(n * Kc * 4);
+    r.zf = off; off += round_up_256(n * Kt * 4);
+    r.rgbs = off; off += round_up_256(n * Kt * 16);
+    r.w = off; off += round_up_256(n * Kt * 4);
+    r.rgb = off; off += round_up_256(n * 12);
+    r.depth = off; off += round_up_256(n * 4);
+    r.rays = off; off += round_up_256(n * 32);          // pnr_render_camera on the fp32 path materialises its rays here
     uint64_t pw = point_workspace_bytes(prm, mlp, vw);
     if (fine) { uint64_t pf = point_workspace_bytes(prm, fine, vw); if (pf > pw) pw = pf; }
-    r.point = off; off += align256(pw);
+    r.point = off; off += round_up_256(pw);
     r.total = off + 256;
     return r;
 }
@@ -274,7 +273,7 @@ static int32_t render_impl(const pnr_params* params, const pnr_mlp* coarse, cons
     if (!workspace) return PNR_E_NULL;
     RenderWs cw = carve(params, coarse, views, n_rays, params->n_fine > 0 ? fine : nullptr);
     if (workspace_bytes < cw.total) return PNR_E_WORKSPACE;     // pnr_workspace_bytes of BOTH MLPs, the larger one
-    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    char* base = (char*)round_up_256(workspace);
     hipStream_t s = (hipStream_t)stream;
     const int Kc = params->n_coarse, Kf = params->n_fine, Kfd = params->n_fine_depth, Kt = Kc + Kf;
     float* zc = outputs->z_coarse ? outputs->z_coarse : (float*)(base + cw.zc);

@@ -22,6 +22,15 @@
 
 namespace pnr {
 
+// ---------------------------------------------------------------- host-side sizes shared by the point paths
+// row stride of the assembled [z | x] feature rows: 16-byte rows for the GEMMs' vector loads
+inline int feature_stride(const pnr_mlp* mlp) { return (mlp->d_latent + mlp->d_in + 3) & ~3; }
+// blocks that add lin_z(z): those in front of the view reduction
+inline int n_lin_z(const pnr_mlp* mlp) { return mlp->combine_layer < mlp->n_blocks ? mlp->combine_layer : mlp->n_blocks; }
+// workspace pieces start on 256-byte boundaries
+inline uint64_t round_up_256(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
+template <typename T> inline T* round_up_256(T* p) { return (T*)round_up_256((uint64_t)(uintptr_t)p); }
+
 // ---------------------------------------------------------------- counter-based RNG (Philox4x32-10)
 // Keyed by (seed, global ray index, draw id); the same ray gets the same draws on any GPU / any
 // sharding, so an N-GPU frame is bit-identical to the 1-GPU frame.

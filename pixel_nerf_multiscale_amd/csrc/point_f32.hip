@@ -22,7 +22,7 @@ static int32_t linear(const float* X, int ldx, const float* W, const float* b, f
 static const int F32_CHUNK = 49152;
 
 uint64_t point_f32_workspace_bytes(const pnr_mlp* mlp, const pnr_views* vw) {
-    uint64_t per_pt = (uint64_t)vw->n_views * (((mlp->d_latent + mlp->d_in + 3) & ~3) + 2ull * mlp->d_hidden) + 4;
+    uint64_t per_pt = (uint64_t)vw->n_views * (feature_stride(mlp) + 2ull * mlp->d_hidden) + 4;
     return per_pt * F32_CHUNK * sizeof(float) + 512 + latent_cl_bytes(*vw);      // + the channels-last latent copies of a call
 }
 
@@ -30,7 +30,7 @@ uint64_t point_f32_workspace_bytes(const pnr_mlp* mlp, const pnr_views* vw) {
 // lin_in, per block [view reduction at combine_layer] + lin_z + fc_0 / fc_1, lin_out -> o (CH, d_out), no activation.
 static int32_t chain_f32(const pnr_mlp* mlp, const float* zx, int E, int CH, int NS, float* x, float* h, float* o, hipStream_t s) {
     const int L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden;
-    const int n_lin_z = mlp->combine_layer < mlp->n_blocks ? mlp->combine_layer : mlp->n_blocks;
+    const int nz = n_lin_z(mlp);
     int M = CH * NS;
     int32_t rc;
     if ((rc = linear<false, false>(zx + L, E, mlp->lin_in_w, mlp->lin_in_b, x, H, M, H, Din, s))) return rc;
@@ -42,7 +42,7 @@ static int32_t chain_f32(const pnr_mlp* mlp, const float* zx, int E, int CH, int
             PNR_LAUNCH_CHECK();
             M = CH;
         }
-        if (L > 0 && b < n_lin_z)
+        if (L > 0 && b < nz)
             if ((rc = linear<false, true>(zx, E, mlp->lin_z_w[b], mlp->lin_z_b[b], x, H, M, H, L, s))) return rc;
         if ((rc = linear<true, false>(x, H, mlp->fc0_w[b], mlp->fc0_b[b], h, H, M, H, H, s))) return rc;
         if ((rc = linear<true, true>(h, H, mlp->fc1_w[b], mlp->fc1_b[b], x, H, M, H, H, s))) return rc;
@@ -56,13 +56,13 @@ int32_t point_f32(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
     if (ws_bytes < point_f32_workspace_bytes(mlp, vw)) return PNR_E_WORKSPACE;
     if (mlp->d_out != 4) return PNR_E_SHAPE;
     const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden;
-    const int E = (L + Din + 3) & ~3;              // row stride of zx: 16-byte rows for the GEMM's vector loads
-    float* zx = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const int E = feature_stride(mlp);
+    float* zx = (float*)round_up_256(workspace);
     float* x = zx + (size_t)F32_CHUNK * NS * E;
     float* h = x + (size_t)F32_CHUNK * NS * H;
     float* o4 = h + (size_t)F32_CHUNK * NS * H;
     // channels-last copies of the maps, once per call (a frame is many chunks): the feature build then reads whole rows
-    void* cl_base = (void*)(((uintptr_t)(o4 + (size_t)F32_CHUNK * 4) + 255) & ~(uintptr_t)255);
+    void* cl_base = round_up_256(o4 + (size_t)F32_CHUNK * 4);
     const LatCL cl = (L > 0 && n_points >= 4096) ? latent_cl_build(*vw, cl_base, s) : LatCL{};
     PNR_LAUNCH_CHECK();
     for (int64_t g0 = 0; g0 < n_points; g0 += F32_CHUNK) {
@@ -86,7 +86,7 @@ int32_t resnetfc_f32(const pnr_mlp* mlp, const float* zx, int64_t outer, int NS,
                      uint64_t ws_bytes, hipStream_t s) {
     if (ws_bytes < resnetfc_f32_workspace_bytes(mlp, NS)) return PNR_E_WORKSPACE;
     const int H = mlp->d_hidden, E = mlp->d_latent + mlp->d_in;
-    float* zc = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* zc = (float*)round_up_256(workspace);
     float* x = zc + (size_t)F32_CHUNK * NS * E;
     float* h = x + (size_t)F32_CHUNK * NS * H;
     for (int64_t o = 0; o < outer; ++o)

@@ -9,6 +9,8 @@
 // Layer math (resnetfc.py:53-62,173-236):  x = lin_in(code); per block b: [combine views at
 // b == combine_layer]; xin = x + lin_z_b(z); h = fc_0(relu(xin)); x = xin + fc_1(relu(h));
 // out = lin_out(relu(x)); rgb = sigmoid, sigma = relu.
+#include <type_traits>
+
 #include "f32_kernels.h"
 
 namespace pnr {
@@ -1811,8 +1813,23 @@ static __global__ void __launch_bounds__(256) k_sample_fine_bwd(
     if (lane == 0) d_depth[ray] = acc;
 }
 
+
 // ------------------------------------------------------------------ host side
+// Operands of the dispatchers below.  Mat: a row-major matrix named once — its fp32 form, its bf16 twin (either may be NULL; both
+// NULL: no such operand) and the leading dimension the two share.  Activations, the relu mask, the residual and the result are
+// all Mats; only the bf16-product kernels read or write a b16 form (the 16-bit tape's).
+struct Mat { const float* f32; const uint16_t* b16; int ld; };
+static constexpr Mat NO_MAT{nullptr, nullptr, 0};
+static inline Mat f32_mat(const float* p, int ld) { return Mat{p, nullptr, ld}; }
+static inline Mat f32_only(const Mat& m) { return f32_mat(m.f32, m.ld); }
+// Weight: W as nn.Linear stores it + this step's copies laid out (N, K) for THE product it is passed to (W itself for
+// y = x W^T, W^T for dX = dY W): nk16 as bf16 — with a bf16 activations operand the GEMM then runs on k_hgemm_dma — and nk32 as
+// fp32, the row-contiguous operand k_sgemm_dma wants for a dX product.  NULL when the shapes do not suit those kernels.
+struct Weight { const float* f32; int ld; const uint16_t* nk16; const float* nk32; };
+static inline Weight plain_weight(const float* w, int ld) { return Weight{w, ld, nullptr, nullptr}; }
+
 struct Tape {
+    int H, L, E;                     // d_hidden, d_latent, row stride of zx
     float* zx;                       // (NS*P, E)
     float* A[PNR_MAX_BLOCKS + 1];    // block inputs after lin_z; A[n_blocks] = input of lin_out
     float* h[PNR_MAX_BLOCKS];        // fc_0 outputs (pre-activation)
@@ -1822,8 +1839,7 @@ struct Tape {
     uint64_t total;
     // 16-bit tape (train_precision = "bf16"): the block inputs and fc_0 outputs are kept as bf16 — exactly the values the
     // bf16-product GEMMs stage anyway, so gradients are bit-identical to the fp32 tape's — and the fp32 residual stream the
-    // forward keeps adding to lives in two ping-pong buffers; A[n_blocks] (the head's input, read by non-MFMA kernels) is
-    // the buffer the forward finished in.
+    // forward keeps adding to lives in two ping-pong buffers (stream()).
     bool h16;
     uint16_t* A16[PNR_MAX_BLOCKS + 1];
     uint16_t* h16p[PNR_MAX_BLOCKS];
@@ -1842,11 +1858,23 @@ struct Tape {
     float* Wt32[2 * PNR_MAX_BLOCKS];
     float* Wzt32[PNR_MAX_BLOCKS];
     void* lat_cl;                        // channels-last fp32 copies of the latent maps for the feature build (latent_cl_build)
+
+    // the fp32 residual stream entering block b (b = n_blocks: entering lin_out, read by non-MFMA kernels): its tape slot, or
+    // on the 16-bit tape the ping-pong buffer of that block — every block writes the other one
+    float* stream(int b) const { return h16 ? xw[b & 1] : A[b]; }
+    // what the tape keeps of a block, in whichever form it keeps it: the block's input and fc_0's output (GEMM operands in
+    // the forward, operands and relu masks in the backward), and the latent columns of zx (lin_z's operand)
+    Mat block_in(int b) const { return Mat{A[b], A16[b], H}; }
+    Mat hidden(int b) const { return Mat{h[b], h16p[b], H}; }
+    Mat z() const { return z16 ? Mat{nullptr, z16, L} : f32_mat(zx, E); }
+    // a hidden weight (i = 2 b: fc_0, 2 b + 1: fc_1) / lin_z of block b with the step's copies for y = x W^T and for dX = dY W
+    Weight hidden_w(const float* w, int i) const { return Weight{w, H, Wb[i], nullptr}; }
+    Weight hidden_w_dx(const float* w, int i) const { return Weight{w, H, Wt[i], Wt32[i]}; }
+    Weight lin_z_w(const float* w, int b) const { return Weight{w, L, Wz[b], nullptr}; }
+    Weight lin_z_w_dx(const float* w, int b) const { return Weight{w, L, Wzt[b], Wzt32[b]}; }
 };
 static inline bool dma_gemm_ok(const pnr_mlp* mlp) { return mlp->d_hidden % 128 == 0; }
 static inline bool dma_lin_z_ok(const pnr_mlp* mlp) { return dma_gemm_ok(mlp) && mlp->d_latent > 0 && mlp->d_latent % 128 == 0; }
-
-static inline uint64_t a256(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
 
 // the bf16-product mode keeps a 16-bit tape when every hidden GEMM takes the bf16 MFMA kernel (d_hidden a multiple of 32)
 static bool tape_is_16bit(const pnr_params* prm, const pnr_mlp* mlp) {
@@ -1856,12 +1884,13 @@ static bool tape_is_16bit(const pnr_params* prm, const pnr_mlp* mlp) {
 static Tape carve_tape(const pnr_mlp* mlp, const pnr_views* vw, int64_t P, void* base, bool h16 = false) {
     Tape t{};
     t.h16 = h16;
-    const int NS = vw->n_views, H = mlp->d_hidden, E = (mlp->d_latent + mlp->d_in + 3) & ~3;   // padded row stride
-    uint8_t* p = (uint8_t*)(((uintptr_t)base + 255) & ~(uintptr_t)255);
+    t.H = mlp->d_hidden; t.L = mlp->d_latent; t.E = feature_stride(mlp);
+    const int NS = vw->n_views, H = t.H, L = t.L, nz = n_lin_z(mlp);
+    uint8_t* p = (uint8_t*)round_up_256(base);
     uint64_t off = 0;
-    auto take = [&](uint64_t floats) { float* r = (float*)(p + off); off += a256(floats * 4); return r; };
-    auto take16 = [&](uint64_t halves) { uint16_t* r = (uint16_t*)(p + off); off += a256(halves * 2); return r; };
-    t.zx = take((uint64_t)NS * P * E);
+    auto take = [&](uint64_t floats) { float* r = (float*)(p + off); off += round_up_256(floats * 4); return r; };
+    auto take16 = [&](uint64_t halves) { uint16_t* r = (uint16_t*)(p + off); off += round_up_256(halves * 2); return r; };
+    t.zx = take((uint64_t)NS * P * t.E);
     if (h16) {
         t.xw[0] = take((uint64_t)NS * P * H);
         t.xw[1] = take((uint64_t)NS * P * H);
@@ -1880,18 +1909,15 @@ static Tape carve_tape(const pnr_mlp* mlp, const pnr_views* vw, int64_t P, void*
     t.o4 = take((uint64_t)P * 4);
     if (h16 && dma_gemm_ok(mlp))
         for (int i = 0; i < 2 * mlp->n_blocks; ++i) { t.Wb[i] = take16((uint64_t)H * H); t.Wt[i] = take16((uint64_t)H * H); }
-    if (mlp->d_latent > 0) { t.lat_cl = (void*)(p + off); off += latent_cl_bytes(*vw); }
+    if (L > 0) { t.lat_cl = (void*)(p + off); off += latent_cl_bytes(*vw); }
     if (!h16 && H % 16 == 0) {
         for (int i = 0; i < 2 * mlp->n_blocks; ++i) t.Wt32[i] = take((uint64_t)H * H);
-        if (mlp->d_latent > 0 && mlp->d_latent % 4 == 0) {
-            const int nz_ = mlp->combine_layer < mlp->n_blocks ? mlp->combine_layer : mlp->n_blocks;
-            for (int b = 0; b < nz_; ++b) t.Wzt32[b] = take((uint64_t)H * mlp->d_latent);
-        }
+        if (L > 0 && L % 4 == 0)
+            for (int b = 0; b < nz; ++b) t.Wzt32[b] = take((uint64_t)H * L);
     }
     if (h16 && dma_lin_z_ok(mlp)) {
-        t.z16 = take16((uint64_t)NS * P * mlp->d_latent);
-        const int nz_ = mlp->combine_layer < mlp->n_blocks ? mlp->combine_layer : mlp->n_blocks;
-        for (int b = 0; b < nz_; ++b) { t.Wz[b] = take16((uint64_t)H * mlp->d_latent); t.Wzt[b] = take16((uint64_t)H * mlp->d_latent); }
+        t.z16 = take16((uint64_t)NS * P * L);
+        for (int b = 0; b < nz; ++b) { t.Wz[b] = take16((uint64_t)H * L); t.Wzt[b] = take16((uint64_t)H * L); }
     }
     t.total = off + 256;
     return t;
@@ -1953,9 +1979,9 @@ static uint64_t latent_q_bytes(const pnr_views* vw) {
     return n * 8 + 256;
 }
 uint64_t train_bwd_workspace_bytes(const pnr_mlp* mlp, const pnr_views* vw, int64_t P) {
-    const uint64_t NS = vw->n_views, H = mlp->d_hidden, E = (mlp->d_latent + mlp->d_in + 3) & ~3;
-    return a256(NS * P * H * 4) * 3 + a256(NS * P * E * 4) + a256((uint64_t)P * 16) + a256(det_ws_floats(mlp) * 4) +
-           a256(latent_part_bytes(vw, P)) + a256(latent_q_bytes(vw)) + 256;
+    const uint64_t NS = vw->n_views, H = mlp->d_hidden, E = feature_stride(mlp);
+    return round_up_256(NS * P * H * 4) * 3 + round_up_256(NS * P * E * 4) + round_up_256((uint64_t)P * 16) +
+           round_up_256(det_ws_floats(mlp) * 4) + round_up_256(latent_part_bytes(vw, P)) + round_up_256(latent_q_bytes(vw)) + 256;
 }
 
 static inline int vec_flags(const float* A, int lda, const float* B, int ldb) {
@@ -1964,126 +1990,118 @@ static inline int vec_flags(const float* A, int lda, const float* B, int ldb) {
 
 static inline bool al16(const void* p, int ld) { return ((uintptr_t)p & 15) == 0 && ld % 4 == 0; }
 
-// 16-bit-tape forms of a bf16-product GEMM: X16 (the activations operand as bf16, instead of X), Mk16 (the relu mask as bf16,
-// instead of Mk), Y16 (a bf16 copy of the result; Y may then be NULL).  Only the bf16 MFMA kernel takes them.
-// W16 (with X16): a bf16 copy of the weight operand laid out (N, K) for THIS product (Tape.Wb for y = x W^T, Tape.Wt for
-// dX = dY W) — the GEMM then runs on k_hgemm_dma.
-struct G16 { const uint16_t* X16; const uint16_t* Mk16; uint16_t* Y16; const uint16_t* W16 = nullptr; };
-
-// What a dispatcher below launched (gemm16 / gemm / head_dx / grad_w), for pnr_debug_linear only: production calls pass no record,
-// so the dispatch costs one pointer test per launch.  id: PNR_DBG_K_* of the launch site; epi: PNR_DBG_EPI_* of a tile kernel's
+// What a dispatcher below launched (gemm / head_dx / grad_w), for pnr_debug_linear only: production calls pass no record, so the
+// dispatch costs one pointer test per launch.  id: PNR_DBG_K_* of the launch site; epi: PNR_DBG_EPI_* of a tile kernel's
 // epilogue (evaluated with the kernel's own arguments); splits / rows / reduce: the row slicing of a weight gradient.
 struct DbgSite { int id, epi, splits, rows, reduce; };
-#define PNR_SITE(d, k) do { if (d) (d)->id = (k); } while (0)
-static int epilogue_form(bool lds_kernel, const float* bias, const float* R, int ldr, const void* Mk, int ldm, bool m16, const float* C,
-                         int ldc, const uint16_t* C16, int ldc16, int N) {
-    if (lds_kernel && tile_epilogue_ok(bias, R, ldr, Mk, ldm, m16, C, ldc, C16, ldc16, N))
-        return tile_epilogue_c16_only(m16, R, Mk, ldm, C, C16, ldc16, N) ? PNR_DBG_EPI_LDS_C16 : PNR_DBG_EPI_LDS;
-    return mgemm_vec_ok(bias, R, ldr, Mk, ldm, m16, C, ldc, C16, ldc16, 0) ? PNR_DBG_EPI_REG_VEC : PNR_DBG_EPI_REG_ELEM;
+// a tile kernel's epilogue arguments, and which epilogue it has: mgemm_epilogue (registers), or tile_epilogue_lds where it qualifies
+struct EpiArgs {
+    const float* bias; const float* R; int ldr; const void* Mk; int ldm; bool m16; const float* C; int ldc; const uint16_t* C16; int ldc16; int N;
+};
+enum EpiKind { EPI_NOT_TILE, EPI_REG, EPI_LDS };
+static int epilogue_form(bool lds_kernel, const EpiArgs& e) {
+    if (lds_kernel && tile_epilogue_ok(e.bias, e.R, e.ldr, e.Mk, e.ldm, e.m16, e.C, e.ldc, e.C16, e.ldc16, e.N))
+        return tile_epilogue_c16_only(e.m16, e.R, e.Mk, e.ldm, e.C, e.C16, e.ldc16, e.N) ? PNR_DBG_EPI_LDS_C16 : PNR_DBG_EPI_LDS;
+    return mgemm_vec_ok(e.bias, e.R, e.ldr, e.Mk, e.ldm, e.m16, e.C, e.ldc, e.C16, e.ldc16, 0) ? PNR_DBG_EPI_REG_VEC : PNR_DBG_EPI_REG_ELEM;
 }
-#define PNR_EPI(d, ...) do { if (d) (d)->epi = epilogue_form(__VA_ARGS__); } while (0)
 
+// The tail every candidate of a dispatcher shares: the debug record, the launch, the launch check.
+template <class Launch>
+static int32_t launch_site(DbgSite* dbg, int id, EpiKind kind, const EpiArgs* e, Launch&& launch) {
+    if (dbg) {
+        dbg->id = id;
+        if (kind != EPI_NOT_TILE) dbg->epi = epilogue_form(kind == EPI_LDS, *e);
+    }
+    launch();
+    PNR_LAUNCH_CHECK();
+    return PNR_OK;
+}
+
+// Runtime booleans -> template flags: f(std::bool_constant<flag>{}...), so a launch picks its kernel instantiation with flag()
+template <class F> static inline void with_flags(F&& f) { f(); }
+template <class F, class... Rest> static inline void with_flags(F&& f, bool flag, Rest... rest) {
+    if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// Y (M, N) = res + mask( act(x) op(W) + b ): the forward (TRANS_W = false: y = x W^T) and dX (TRANS_W = true: dX = dY W) products
+// of the taped step; the first candidate whose predicate holds is launched.  b, res, mask may be absent; res may alias y.
+// mode: 0 = fp32 MFMA, 1 = bf16 MFMA, 3 = bf16x3 split (fp32-class) products on fp32 operands, or PNR_DBG_MODE_TAPE16: the
+// 16-bit-tape forms of a bf16 product (pnr.h: gemm16) — x.b16 (the activations as bf16, instead of x.f32), mask.b16 (the relu
+// mask as bf16, instead of mask.f32), y.b16 (a bf16 copy of the result; y.f32 may then be NULL) and w.nk16.  Only that mode
+// reads or writes a b16 form; only the fp32-product dX reads w.nk32.
 template <bool RELU_X, bool TRANS_W>
-static int32_t gemm16(const G16& g, const float* X, int ldx, const float* W, int ldw, const float* b, const float* R, int ldr,
-                      const float* Mk, int ldm, float* Y, int ldy, int64_t M, int N, int K, hipStream_t s, DbgSite* dbg = nullptr) {
+static int32_t gemm(const Mat& x, const Weight& w, const float* b, const Mat& res, const Mat& mask, const Mat& y, int64_t M, int N, int K,
+                    int mode, hipStream_t s, DbgSite* dbg = nullptr) {
     if (M == 0) return PNR_OK;
-    if (!(N >= 32 && K >= 32 && K % 32 == 0 && N % 4 == 0 && al16(W, ldw))) return PNR_E_UNSUPPORTED;
-    const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
-    if (g.X16 && g.W16 && K % 64 == 0 && ldx % 8 == 0 && ((uintptr_t)g.X16 & 15) == 0 && ((uintptr_t)g.W16 & 15) == 0 && !(Mk && !g.Mk16)) {
+    const float* X = x.f32; const float* W = w.f32; const float* R = res.f32; const float* Mk = mask.f32;
+    float* Y = const_cast<float*>(y.f32);
+    const int ldx = x.ld, ldw = w.ld, ldr = res.ld, ldm = mask.ld, ldy = y.ld;
+    const dim3 tiles = mgemm_grid((M + 127) / 128, (N + 127) / 128), blk(256);       // of the 128 x 128 tile kernels
+    if (mode == PNR_DBG_MODE_TAPE16) {
+        const uint16_t* X16 = x.b16; const uint16_t* Mk16 = mask.b16; const uint16_t* W16 = w.nk16;
+        uint16_t* Y16 = const_cast<uint16_t*>(y.b16);
+        if (!(N >= 32 && K >= 32 && K % 32 == 0 && N % 4 == 0 && al16(W, ldw))) return PNR_E_UNSUPPORTED;
+        const void* Xp = X16 ? (const void*)X16 : (const void*)X;
+        const void* Mp = Mk16 ? (const void*)Mk16 : (const void*)Mk;
+        const EpiArgs e{b, R, ldr, Mp, ldm, Mk16 != nullptr, Y, ldy, Y16, ldy, N};
         // both operands bf16 and row-contiguous in the reduction index: the LDS-DMA k-loop (W16 is (N, K), leading dimension K)
-        const void* Mp16 = (const void*)g.Mk16;
-        PNR_SITE(dbg, g.Mk16 ? PNR_DBG_K_HGEMM_DMA_M16 : PNR_DBG_K_HGEMM_DMA);
-        PNR_EPI(dbg, true, b, R, ldr, Mp16, ldm, g.Mk16 != nullptr, Y, ldy, g.Y16, ldy, N);
-        if (g.Mk16)
-            hipLaunchKernelGGL((k_hgemm_dma<RELU_X, true>), grid, dim3(256), 0, s, g.X16, ldx, g.W16, K, b, R, ldr, Mp16, ldm, Y, ldy,
-                               g.Y16, ldy, (int)M, N, K);
-        else
-            hipLaunchKernelGGL((k_hgemm_dma<RELU_X, false>), grid, dim3(256), 0, s, g.X16, ldx, g.W16, K, b, R, ldr, (const void*)nullptr,
-                               ldm, Y, ldy, g.Y16, ldy, (int)M, N, K);
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
+        if (X16 && W16 && K % 64 == 0 && ldx % 8 == 0 && ((uintptr_t)X16 & 15) == 0 && ((uintptr_t)W16 & 15) == 0 && !(Mk && !Mk16))
+            return launch_site(dbg, Mk16 ? PNR_DBG_K_HGEMM_DMA_M16 : PNR_DBG_K_HGEMM_DMA, EPI_LDS, &e, [&] {
+                with_flags([&](auto m16) {
+                    hipLaunchKernelGGL((k_hgemm_dma<RELU_X, m16()>), tiles, blk, 0, s, X16, ldx, W16, K, b, R, ldr, Mp, ldm, Y, ldy, Y16, ldy,
+                                       (int)M, N, K);
+                }, Mk16 != nullptr);
+            });
+        return launch_site(dbg, X16 ? (Mk16 ? PNR_DBG_K_MGEMM_BF16_A16_M16 : PNR_DBG_K_MGEMM_BF16_A16)
+                                    : (Mk16 ? PNR_DBG_K_MGEMM_BF16_M16 : PNR_DBG_K_MGEMM_BF16_G16), EPI_REG, &e, [&] {
+            with_flags([&](auto a16, auto m16) {
+                hipLaunchKernelGGL((k_mgemm_bf16<true, !TRANS_W, RELU_X, false, false, a16(), false, m16()>), tiles, blk, 0, s, Xp, ldx,
+                                   (const void*)W, ldw, b, R, ldr, Mp, ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0, (size_t)0, (size_t)0,
+                                   Y16, ldy);
+            }, X16 != nullptr, Mk16 != nullptr);
+        });
     }
-    const void* Xp = g.X16 ? (const void*)g.X16 : (const void*)X;
-    const void* Mp = g.Mk16 ? (const void*)g.Mk16 : (const void*)Mk;
-#define PNR_G16_LAUNCH(A16, M16)                                                                                       \
-    hipLaunchKernelGGL((k_mgemm_bf16<true, !TRANS_W, RELU_X, false, false, A16, false, M16>), grid, dim3(256), 0, s, Xp, ldx, \
-                       (const void*)W, ldw, b, R, ldr, Mp, ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0, (size_t)0,    \
-                       (size_t)0, g.Y16, ldy)
-    PNR_SITE(dbg, g.X16 ? (g.Mk16 ? PNR_DBG_K_MGEMM_BF16_A16_M16 : PNR_DBG_K_MGEMM_BF16_A16)
-                        : (g.Mk16 ? PNR_DBG_K_MGEMM_BF16_M16 : PNR_DBG_K_MGEMM_BF16_G16));
-    PNR_EPI(dbg, false, b, R, ldr, Mp, ldm, g.Mk16 != nullptr, Y, ldy, g.Y16, ldy, N);
-    if (g.X16 && g.Mk16) PNR_G16_LAUNCH(true, true);
-    else if (g.X16) PNR_G16_LAUNCH(true, false);
-    else if (g.Mk16) PNR_G16_LAUNCH(false, true);
-    else PNR_G16_LAUNCH(false, false);
-#undef PNR_G16_LAUNCH
-    PNR_LAUNCH_CHECK();
-    return PNR_OK;
-}
-
-// Wt (TRANS_W products with fp32 arithmetic only): W^T as an (N, K) row-major copy — the product then runs on k_sgemm_dma
-template <bool RELU_X, bool TRANS_W>
-static int32_t gemm(const float* X, int ldx, const float* W, int ldw, const float* b, const float* R, int ldr,
-                    const float* Mk, int ldm, float* Y, int ldy, int64_t M, int N, int K, hipStream_t s, int half = 0,
-                    const float* Wt = nullptr, DbgSite* dbg = nullptr) {
-    if (M == 0) return PNR_OK;
-    if (TRANS_W && Wt && !half && N >= 32 && K >= 64 && K % 16 == 0 && al16(X, ldx) && ((uintptr_t)Wt & 15) == 0) {
-        const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
-        PNR_SITE(dbg, PNR_DBG_K_SGEMM_DMA_WT);
-        PNR_EPI(dbg, true, b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N);
-        hipLaunchKernelGGL((k_sgemm_dma<RELU_X>), grid, dim3(256), 0, s, X, ldx, Wt, K, b, R, ldr, Mk, ldm, Y, ldy, (int)M, N, K);
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
-    }
-    if (half && N >= 32 && K >= 32 && K % 32 == 0 && N % 4 == 0 && al16(X, ldx) && al16(W, ldw)) {
-        const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
-        PNR_SITE(dbg, half == 3 ? PNR_DBG_K_MGEMM_BF16X3 : PNR_DBG_K_MGEMM_BF16);
-        PNR_EPI(dbg, false, b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N);
-        if (half == 3)
-            hipLaunchKernelGGL((k_mgemm_bf16x3<true, !TRANS_W, RELU_X, false, false>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R,
-                               ldr, Mk, ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0);
-        else
-            hipLaunchKernelGGL((k_mgemm_bf16<true, !TRANS_W, RELU_X, false, false>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R,
-                               ldr, Mk, ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0);
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
-    }
-    if (!TRANS_W && !half && N >= 32 && K >= 64 && K % 16 == 0 && al16(X, ldx) && al16(W, ldw)) {
-        // fp32 products, activations x weights as stored: both operands row-contiguous in the reduction index -> LDS-DMA k-loop
-        const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
-        PNR_SITE(dbg, PNR_DBG_K_SGEMM_DMA);
-        PNR_EPI(dbg, true, b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N);
-        hipLaunchKernelGGL((k_sgemm_dma<RELU_X>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R, ldr, Mk, ldm, Y, ldy, (int)M, N, K);
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
-    }
-    if (N >= 32 && K >= 16) {       // MFMA tile kernel; the skinny heads (N = 4, K = 4) stay on the FMA kernel
-        const dim3 grid = mgemm_grid((M + 127) / 128, (N + 127) / 128);
-        PNR_SITE(dbg, PNR_DBG_K_MGEMM_F32);
-        PNR_EPI(dbg, false, b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N);
-        hipLaunchKernelGGL((k_mgemm_f32<true, !TRANS_W, RELU_X, false, false>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R, ldr,
-                           Mk, ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0, vec_flags(X, ldx, W, ldw));
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
-    }
-    if (!TRANS_W && N == 4 && !R && !Mk && (K == 256 || K == 512) && al16(X, ldx) && al16(W, ldw) && al16(Y, ldy)) {
-        // the output head (lin_out, d_out = 4)
-        int64_t blocks = (M + 15) / 16;
-        if (blocks > 2048) blocks = 2048;
-        PNR_SITE(dbg, K == 512 ? PNR_DBG_K_LINEAR_HEAD_512 : PNR_DBG_K_LINEAR_HEAD_256);
-        if (K == 512)
-            hipLaunchKernelGGL((k_linear_head<RELU_X, 2>), dim3((unsigned)blocks), dim3(256), 0, s, X, ldx, W, ldw, b, Y, ldy, (int)M);
-        else
-            hipLaunchKernelGGL((k_linear_head<RELU_X, 1>), dim3((unsigned)blocks), dim3(256), 0, s, X, ldx, W, ldw, b, Y, ldy, (int)M);
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
-    }
-    dim3 grid((unsigned)((M + 63) / 64), (N + 63) / 64);
-    PNR_SITE(dbg, PNR_DBG_K_GEMM_F32);
-    hipLaunchKernelGGL((k_gemm_f32<RELU_X, TRANS_W>), grid, dim3(256), 0, s, X, ldx, W, ldw, b, R, ldr, Mk, ldm, Y,
-                       ldy, (int)M, N, K);
-    PNR_LAUNCH_CHECK();
-    return PNR_OK;
+    const int half = mode;
+    const EpiArgs e{b, R, ldr, Mk, ldm, false, Y, ldy, nullptr, 0, N};
+    // fp32 dX with W^T as an (N, K) row-major copy: both operands row-contiguous in the reduction index -> LDS-DMA k-loop
+    if (TRANS_W && w.nk32 && !half && N >= 32 && K >= 64 && K % 16 == 0 && al16(X, ldx) && ((uintptr_t)w.nk32 & 15) == 0)
+        return launch_site(dbg, PNR_DBG_K_SGEMM_DMA_WT, EPI_LDS, &e, [&] {
+            hipLaunchKernelGGL((k_sgemm_dma<RELU_X>), tiles, blk, 0, s, X, ldx, w.nk32, K, b, R, ldr, Mk, ldm, Y, ldy, (int)M, N, K);
+        });
+    if (half && N >= 32 && K >= 32 && K % 32 == 0 && N % 4 == 0 && al16(X, ldx) && al16(W, ldw))
+        return launch_site(dbg, half == 3 ? PNR_DBG_K_MGEMM_BF16X3 : PNR_DBG_K_MGEMM_BF16, EPI_REG, &e, [&] {
+            if (half == 3)
+                hipLaunchKernelGGL((k_mgemm_bf16x3<true, !TRANS_W, RELU_X, false, false>), tiles, blk, 0, s, X, ldx, W, ldw, b, R, ldr, Mk,
+                                   ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0);
+            else
+                hipLaunchKernelGGL((k_mgemm_bf16<true, !TRANS_W, RELU_X, false, false>), tiles, blk, 0, s, X, ldx, W, ldw, b, R, ldr, Mk,
+                                   ldm, Y, ldy, (float*)nullptr, (int)M, N, K, 0);
+        });
+    // fp32 products, activations x weights as stored: both operands row-contiguous in the reduction index -> LDS-DMA k-loop
+    if (!TRANS_W && !half && N >= 32 && K >= 64 && K % 16 == 0 && al16(X, ldx) && al16(W, ldw))
+        return launch_site(dbg, PNR_DBG_K_SGEMM_DMA, EPI_LDS, &e, [&] {
+            hipLaunchKernelGGL((k_sgemm_dma<RELU_X>), tiles, blk, 0, s, X, ldx, W, ldw, b, R, ldr, Mk, ldm, Y, ldy, (int)M, N, K);
+        });
+    if (N >= 32 && K >= 16)         // MFMA tile kernel; the skinny heads (N = 4, K = 4) stay on the FMA kernel
+        return launch_site(dbg, PNR_DBG_K_MGEMM_F32, EPI_REG, &e, [&] {
+            hipLaunchKernelGGL((k_mgemm_f32<true, !TRANS_W, RELU_X, false, false>), tiles, blk, 0, s, X, ldx, W, ldw, b, R, ldr, Mk, ldm, Y,
+                               ldy, (float*)nullptr, (int)M, N, K, 0, vec_flags(X, ldx, W, ldw));
+        });
+    // the output head (lin_out, d_out = 4)
+    if (!TRANS_W && N == 4 && !R && !Mk && (K == 256 || K == 512) && al16(X, ldx) && al16(W, ldw) && al16(Y, ldy))
+        return launch_site(dbg, K == 512 ? PNR_DBG_K_LINEAR_HEAD_512 : PNR_DBG_K_LINEAR_HEAD_256, EPI_NOT_TILE, nullptr, [&] {
+            int64_t blocks = (M + 15) / 16;
+            if (blocks > 2048) blocks = 2048;
+            if (K == 512)
+                hipLaunchKernelGGL((k_linear_head<RELU_X, 2>), dim3((unsigned)blocks), blk, 0, s, X, ldx, W, ldw, b, Y, ldy, (int)M);
+            else
+                hipLaunchKernelGGL((k_linear_head<RELU_X, 1>), dim3((unsigned)blocks), blk, 0, s, X, ldx, W, ldw, b, Y, ldy, (int)M);
+        });
+    return launch_site(dbg, PNR_DBG_K_GEMM_F32, EPI_NOT_TILE, nullptr, [&] {
+        hipLaunchKernelGGL((k_gemm_f32<RELU_X, TRANS_W>), dim3((unsigned)((M + 63) / 64), (N + 63) / 64), blk, 0, s, X, ldx, W, ldw, b, R,
+                           ldr, Mk, ldm, Y, ldy, (int)M, N, K);
+    });
 }
 
 // dX of the output head: Y (P, N) = mask(Mk > 0) (.) (X (P, 4) . W (4, N)) — four products per element, i.e. a stream: one
@@ -2128,7 +2146,7 @@ static int32_t head_dx(const float* X, const float* W, int ldw, const float* Mk,
     const int per_row = N >> 2;
     int64_t blocks = (P * per_row + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    PNR_SITE(dbg, PNR_DBG_K_HEAD_DX);
+    if (dbg) dbg->id = PNR_DBG_K_HEAD_DX;
     hipLaunchKernelGGL(k_head_dx, dim3((unsigned)blocks), dim3(256), 0, s, (const float4*)X, W, ldw, Mk, ldm, Y, ldy, Y16, ldy, P, N);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
@@ -2160,9 +2178,10 @@ __global__ void k_col_sums16(const uint16_t* __restrict__ dY, int ldy, float* __
 // training forward uses.  W (N, K) row-major as nn.Linear stores it; accum adds to what Y holds.
 int32_t linear_f32_mfma(const float* X, int ldx, const float* W, int ldw, const float* b, bool relu_in, bool accum, float* Y,
                         int ldy, int64_t M, int N, int K, hipStream_t s) {
-    const float* R = accum ? Y : nullptr;
-    if (relu_in) return gemm<true, false>(X, ldx, W, ldw, b, R, ldy, nullptr, 0, Y, ldy, M, N, K, s, 0);
-    return gemm<false, false>(X, ldx, W, ldw, b, R, ldy, nullptr, 0, Y, ldy, M, N, K, s, 0);
+    const Mat x = f32_mat(X, ldx), y = f32_mat(Y, ldy), res = f32_mat(accum ? Y : nullptr, ldy);
+    const Weight w = plain_weight(W, ldw);
+    if (relu_in) return gemm<true, false>(x, w, b, res, NO_MAT, y, M, N, K, 0, s);
+    return gemm<false, false>(x, w, b, res, NO_MAT, y, M, N, K, 0, s);
 }
 
 // Ordered sum of the per-split partials: out[i] += part[0][i] + part[1][i] + ... (fixed order -> run-to-run identical bits)
@@ -2194,13 +2213,14 @@ __global__ void k_reduce_parts2(const float* __restrict__ pw, const float* __res
 
 // dW (N, K) += dY^T act(X),  db (N) += column sums of dY;  rows split over the grid, one partial slice per split,
 // ordered reduction at the end.  Either output may be NULL (a frozen parameter): the GEMM kernels need dW, so a bias-only
-// request takes k_col_sums.
+// request takes k_col_sums.  x.b16 (the 16-bit tape's form of the operand, instead of x.f32) goes to the bf16 MFMA kernels only;
+// dy.b16 (the gradient stream's bf16 copy, read instead of dy.f32) needs x.b16.  half: as gemm's mode (0, 1, 3).
 template <bool RELU_X>
-static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* dW, int ldw, float* db, int64_t M,
-                      int N, int K, hipStream_t s, int half, const DetWs& ws, const uint16_t* X16 = nullptr,
-                      const uint16_t* dY16 = nullptr /* the gradient stream's bf16 copy (with X16): read instead of dY */,
-                      DbgSite* dbg = nullptr) {
+static int32_t grad_w(const Mat& dy, const Mat& x, float* dW, int ldw, float* db, int64_t M, int N, int K, int half, const DetWs& ws,
+                      hipStream_t s, DbgSite* dbg = nullptr) {
     if ((!dW && !db) || M == 0) return PNR_OK;
+    const float* dY = dy.f32; const uint16_t* dY16 = dy.b16; const float* X = x.f32; const uint16_t* X16 = x.b16;
+    const int ldy = dy.ld, ldx = x.ld;
     const size_t zs_w = (size_t)N * K, zs_b = (size_t)N;
     // rows per split: the kernel's natural slice, enlarged until the splits fit the scratch
     auto splits_for = [&](int rows, int* rows_out) -> int {
@@ -2219,33 +2239,30 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
     };
     float* pw = ws.part;                 // (nz, N, K)
     int rows = 0, nz = 0;
-    auto finish = [&](int nz) -> int32_t {
+    const dim3 blk(256);
+    // the tail every candidate shares: its launch into the partial slices, then their ordered sums
+    auto run = [&](int id, auto&& launch) -> int32_t {
+        PNR_TRY(launch_site(dbg, id, EPI_NOT_TILE, nullptr, launch));
         float* pb = pw + (size_t)nz * zs_w;
         if (dbg) { dbg->splits = nz; dbg->rows = rows; dbg->reduce = dW && db ? 2 : 1; }
-        if (dW && db) {          // one launch for the weight and its bias (60 -> 40 launches per training step)
-            hipLaunchKernelGGL(k_reduce_parts2, dim3((unsigned)((zs_w + zs_b + 255) / 256)), dim3(256), 0, s, pw, pb, nz, zs_w, zs_b, dW, ldw, K, db);
-            PNR_LAUNCH_CHECK();
-            return PNR_OK;
-        }
-        if (dW) {
-            hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)((zs_w + 255) / 256)), dim3(256), 0, s, pw, nz, zs_w, dW, ldw, N, K);
-            PNR_LAUNCH_CHECK();
-        }
-        if (db) {
-            hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)((zs_b + 255) / 256)), dim3(256), 0, s, pb, nz, zs_b, db, N, 1, N);
-            PNR_LAUNCH_CHECK();
-        }
+        if (dW && db)            // one launch for the weight and its bias (60 -> 40 launches per training step)
+            hipLaunchKernelGGL(k_reduce_parts2, dim3((unsigned)((zs_w + zs_b + 255) / 256)), blk, 0, s, pw, pb, nz, zs_w, zs_b, dW, ldw, K, db);
+        else if (dW)
+            hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)((zs_w + 255) / 256)), blk, 0, s, pw, nz, zs_w, dW, ldw, N, K);
+        else
+            hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)((zs_b + 255) / 256)), blk, 0, s, pb, nz, zs_b, db, N, 1, N);
+        PNR_LAUNCH_CHECK();
         return PNR_OK;
     };
     if (!ws.part || ws.floats < zs_w + zs_b) return PNR_E_WORKSPACE;
     if (!dW) {
         nz = splits_for(2048, &rows);
         float* pb = pw + (size_t)nz * zs_w;
-        PNR_SITE(dbg, dY16 ? PNR_DBG_K_COL_SUMS16 : PNR_DBG_K_COL_SUMS);
-        if (dY16) hipLaunchKernelGGL(k_col_sums16, dim3((N + 255) / 256, (unsigned)nz), dim3(256), 0, s, dY16, ldy, pb, (int)M, N, rows, zs_b);
-        else hipLaunchKernelGGL(k_col_sums, dim3((N + 255) / 256, (unsigned)nz), dim3(256), 0, s, dY, ldy, pb, (int)M, N, rows, zs_b);
-        PNR_LAUNCH_CHECK();
-        return finish(nz);
+        const dim3 grid((N + 255) / 256, (unsigned)nz);
+        return run(dY16 ? PNR_DBG_K_COL_SUMS16 : PNR_DBG_K_COL_SUMS, [&] {
+            if (dY16) hipLaunchKernelGGL(k_col_sums16, grid, blk, 0, s, dY16, ldy, pb, (int)M, N, rows, zs_b);
+            else hipLaunchKernelGGL(k_col_sums, grid, blk, 0, s, dY, ldy, pb, (int)M, N, rows, zs_b);
+        });
     }
     const bool mfma_shape = N >= 32 && K >= 32;
     const bool use_half = half && mfma_shape && N % 4 == 0 && K % 4 == 0 && (dY16 ? ldy % 8 == 0 : al16(dY, ldy)) && (X16 ? true : al16(X, ldx));
@@ -2253,8 +2270,7 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
     if (dY16 && !X16) return PNR_E_UNSUPPORTED;
     const bool head = !mfma_shape && N == 4 && ldy == 4 && ((uintptr_t)dY & 15) == 0;
     // lin_in: few input columns against d_hidden output rows — its own kernel, fp32 operands in every mode
-    const bool skinny = !RELU_X && !X16 && !dY16 && K <= 96 && N >= 64 && dY && X;
-    if (skinny) {
+    if (!RELU_X && !X16 && !dY16 && K <= 96 && N >= 64 && dY && X) {
         // partial slices are small (N K floats): many of them, so that the chip is filled
         int64_t want = (M + 191) / 192;
         int64_t cap = (int64_t)(ws.floats / (zs_w + zs_b));
@@ -2263,13 +2279,12 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
         if (want < 1) want = 1;
         rows = (int)((M + want - 1) / want);
         nz = (int)((M + rows - 1) / rows);
-        float* pbs = pw + (size_t)nz * zs_w;
+        float* pbs = db ? pw + (size_t)nz * zs_w : nullptr;
         const dim3 grid((N + 255) / 256, (unsigned)nz);
-        PNR_SITE(dbg, K <= 48 ? PNR_DBG_K_GRAD_W_SKINNY48 : PNR_DBG_K_GRAD_W_SKINNY96);
-        if (K <= 48) hipLaunchKernelGGL((k_grad_w_skinny<48>), grid, dim3(256), 0, s, dY, ldy, X, ldx, pw, K, db ? pbs : nullptr, (int)M, N, K, rows, zs_w, zs_b);
-        else hipLaunchKernelGGL((k_grad_w_skinny<96>), grid, dim3(256), 0, s, dY, ldy, X, ldx, pw, K, db ? pbs : nullptr, (int)M, N, K, rows, zs_w, zs_b);
-        PNR_LAUNCH_CHECK();
-        return finish(nz);
+        return run(K <= 48 ? PNR_DBG_K_GRAD_W_SKINNY48 : PNR_DBG_K_GRAD_W_SKINNY96, [&] {
+            if (K <= 48) hipLaunchKernelGGL((k_grad_w_skinny<48>), grid, blk, 0, s, dY, ldy, X, ldx, pw, K, pbs, (int)M, N, K, rows, zs_w, zs_b);
+            else hipLaunchKernelGGL((k_grad_w_skinny<96>), grid, blk, 0, s, dY, ldy, X, ldx, pw, K, pbs, (int)M, N, K, rows, zs_w, zs_b);
+        });
     }
     // the LDS-DMA kernel runs two workgroups per CU: 32 slices x 16 tiles of a 512 x 512 weight = one full round of the chip's
     // 512 slots (48 slices of 1024 rows were 1.5 rounds), and a third less partial-sum traffic for k_reduce_parts
@@ -2283,58 +2298,51 @@ static int32_t grad_w(const float* dY, int ldy, const float* X, int ldx, float* 
     const bool dma32 = !use_half && !half && mfma_shape && M % 32 == 0 && N % 128 == 0 && K % 128 == 0 && al16(dY, ldy) && al16(X, ldx);
     const bool slices32 = (use_half && half == 1 && M % 32 == 0) || dma32;        // (fp32 products on k_sgemm_dma_kt: the same grid)
     nz = splits_for(slices32 ? rows_dma : mfma_shape ? 1024 : head ? 256 : 2048, &rows);
-    float* pb = pw + (size_t)nz * zs_w;
-    float* pbk = db ? pb : nullptr;
-    if (mfma_shape) {
-        // dW = A B with A(n, r = m) = dY[m][n] and B(r = m, k) = act(X[m][k]): both stored reduction-major
-        const dim3 grid = mgemm_grid(nz, ((N + 127) / 128) * ((K + 127) / 128));
-        if (use_half && half == 3) {
-            PNR_SITE(dbg, PNR_DBG_K_MGEMM_BF16X3_DW);
-            hipLaunchKernelGGL((k_mgemm_bf16x3<false, false, false, RELU_X, true>), grid, dim3(256), 0, s, dY, ldy, X, ldx,
-                               (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk,
-                               N, K, (int)M, rows, zs_w, zs_b);
-        } else if (dma_kt && rows % 64 == 0) {
-            PNR_SITE(dbg, PNR_DBG_K_HGEMM_DMA_KT);
-            hipLaunchKernelGGL((k_hgemm_dma_kt<RELU_X>), grid, dim3(256), 0, s, dY16, ldy, X16, ldx, pw, K, pbk, N, K, (int)M, rows,
-                               zs_w, zs_b);
-        } else if (use_half && X16 && dY16) {
-            PNR_SITE(dbg, PNR_DBG_K_MGEMM_BF16_DW_A16B16);
-            hipLaunchKernelGGL((k_mgemm_bf16<false, false, false, RELU_X, true, true, true, false>), grid, dim3(256), 0, s,
-                               (const void*)dY16, ldy, (const void*)X16, ldx, (const float*)nullptr, (const float*)nullptr, 0,
-                               (const void*)nullptr, 0, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
-        } else if (use_half && X16) {
-            PNR_SITE(dbg, PNR_DBG_K_MGEMM_BF16_DW_B16);
-            hipLaunchKernelGGL((k_mgemm_bf16<false, false, false, RELU_X, true, false, true, false>), grid, dim3(256), 0, s,
-                               (const void*)dY, ldy, (const void*)X16, ldx, (const float*)nullptr, (const float*)nullptr, 0,
-                               (const void*)nullptr, 0, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
-        } else if (use_half) {
-            PNR_SITE(dbg, PNR_DBG_K_MGEMM_BF16_DW);
-            hipLaunchKernelGGL((k_mgemm_bf16<false, false, false, RELU_X, true>), grid, dim3(256), 0, s, dY, ldy, X, ldx,
-                               (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk,
-                               N, K, (int)M, rows, zs_w, zs_b);
-        } else if (dma32 && rows % 16 == 0) {
-            PNR_SITE(dbg, PNR_DBG_K_SGEMM_DMA_KT);
-            hipLaunchKernelGGL((k_sgemm_dma_kt<RELU_X>), grid, dim3(256), 0, s, dY, ldy, X, ldx, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
-        } else {
-            PNR_SITE(dbg, PNR_DBG_K_MGEMM_F32_DW);
-            hipLaunchKernelGGL((k_mgemm_f32<false, false, false, RELU_X, true>), grid, dim3(256), 0, s, dY, ldy, X, ldx,
-                               (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk,
-                               N, K, (int)M, rows, vec_flags(dY, ldy, X, ldx), zs_w, zs_b);
-        }
-    } else if (head) {
-        dim3 grid((K + 127) / 128, (unsigned)nz);
-        PNR_SITE(dbg, PNR_DBG_K_GRAD_W_HEAD);
-        hipLaunchKernelGGL((k_grad_w_head<RELU_X>), grid, dim3(256), 0, s, (const float4*)dY, X, ldx, pw, K, pbk, (int)M, K, rows,
+    float* pbk = db ? pw + (size_t)nz * zs_w : nullptr;
+    if (head)
+        return run(PNR_DBG_K_GRAD_W_HEAD, [&] {
+            hipLaunchKernelGGL((k_grad_w_head<RELU_X>), dim3((K + 127) / 128, (unsigned)nz), blk, 0, s, (const float4*)dY, X, ldx, pw, K, pbk,
+                               (int)M, K, rows, zs_w, zs_b);
+        });
+    if (!mfma_shape)
+        return run(PNR_DBG_K_GRAD_W_F32, [&] {
+            hipLaunchKernelGGL((k_grad_w_f32<RELU_X>), dim3((N + 63) / 64, (K + 63) / 64, (unsigned)nz), blk, 0, s, dY, ldy, X, ldx, pw, K, pbk,
+                               (int)M, N, K, rows, zs_w, zs_b);
+        });
+    // dW = A B with A(n, r = m) = dY[m][n] and B(r = m, k) = act(X[m][k]): both stored reduction-major
+    const dim3 grid = mgemm_grid(nz, ((N + 127) / 128) * ((K + 127) / 128));
+    if (use_half && half == 3)
+        return run(PNR_DBG_K_MGEMM_BF16X3_DW, [&] {
+            hipLaunchKernelGGL((k_mgemm_bf16x3<false, false, false, RELU_X, true>), grid, blk, 0, s, dY, ldy, X, ldx, (const float*)nullptr,
+                               (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
+        });
+    if (dma_kt && rows % 64 == 0)
+        return run(PNR_DBG_K_HGEMM_DMA_KT, [&] {
+            hipLaunchKernelGGL((k_hgemm_dma_kt<RELU_X>), grid, blk, 0, s, dY16, ldy, X16, ldx, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
+        });
+    if (use_half && X16)        // the tape's operand as bf16, the gradient stream in whichever form it came
+        return run(dY16 ? PNR_DBG_K_MGEMM_BF16_DW_A16B16 : PNR_DBG_K_MGEMM_BF16_DW_B16, [&] {
+            with_flags([&](auto a16) {
+                hipLaunchKernelGGL((k_mgemm_bf16<false, false, false, RELU_X, true, a16(), true, false>), grid, blk, 0, s,
+                                   dY16 ? (const void*)dY16 : (const void*)dY, ldy, (const void*)X16, ldx, (const float*)nullptr,
+                                   (const float*)nullptr, 0, (const void*)nullptr, 0, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
+            }, dY16 != nullptr);
+        });
+    if (use_half)
+        return run(PNR_DBG_K_MGEMM_BF16_DW, [&] {
+            hipLaunchKernelGGL((k_mgemm_bf16<false, false, false, RELU_X, true>), grid, blk, 0, s, dY, ldy, X, ldx, (const float*)nullptr,
+                               (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
+        });
+    if (dma32 && rows % 16 == 0)
+        return run(PNR_DBG_K_SGEMM_DMA_KT, [&] {
+            hipLaunchKernelGGL((k_sgemm_dma_kt<RELU_X>), grid, blk, 0, s, dY, ldy, X, ldx, pw, K, pbk, N, K, (int)M, rows, zs_w, zs_b);
+        });
+    return run(PNR_DBG_K_MGEMM_F32_DW, [&] {
+        hipLaunchKernelGGL((k_mgemm_f32<false, false, false, RELU_X, true>), grid, blk, 0, s, dY, ldy, X, ldx, (const float*)nullptr,
+                           (const float*)nullptr, 0, (const float*)nullptr, 0, pw, K, pbk, N, K, (int)M, rows, vec_flags(dY, ldy, X, ldx),
                            zs_w, zs_b);
-    } else {
-        dim3 grid((N + 63) / 64, (K + 63) / 64, (unsigned)nz);
-        PNR_SITE(dbg, PNR_DBG_K_GRAD_W_F32);
-        hipLaunchKernelGGL((k_grad_w_f32<RELU_X>), grid, dim3(256), 0, s, dY, ldy, X, ldx, pw, K, pbk, (int)M, N, K, rows, zs_w, zs_b);
-    }
-    PNR_LAUNCH_CHECK();
-    return finish(nz);
+    });
 }
-
 
 // bf16 copy of a fp32 tensor (the residual stream behind a view reduction, or lin_in's output when no lin_z follows)
 static __global__ void k_to_bf16(const float* __restrict__ x, int64_t n, uint16_t* __restrict__ y) {
@@ -2342,134 +2350,68 @@ static __global__ void k_to_bf16(const float* __restrict__ x, int64_t n, uint16_
     if (i < n) y[i] = (uint16_t)(pk_bf16(x[i], 0.f) & 0xffffu);
 }
 
-// The taped forward with the 16-bit tape (train_precision = "bf16", see Tape): same GEMMs, same operands after rounding; the
-// fp32 residual stream ping-pongs between t.xw[0] / t.xw[1], every GEMM that produces a block input also writes its bf16 copy.
-static int32_t point_train_fwd_tape16(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, PointSrc src, int64_t P,
-                                      int64_t pts_per_obj, float* out, Tape& t, hipStream_t s) {
-    const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden;
-    const int E = (L + Din + 3) & ~3;
-    const int nb = mlp->n_blocks, cl = mlp->combine_layer;
-    const int n_lin_z = cl < nb ? cl : nb;
-    const int64_t MV = (int64_t)NS * P;
-    if (MV > 0x7fffffff) return PNR_E_SHAPE;
-    PNR_TRY(features_launch(*vw, src, 0, (int)P, pts_per_obj, L, Din, prm->use_code_viewdirs, prm->num_freqs, prm->freq_factor, t.zx, E, s,
-                            (t.lat_cl && P >= 4096) ? latent_cl_build(*vw, t.lat_cl, s) : LatCL{}));
-    PNR_LAUNCH_CHECK();
-    auto to16 = [&](const float* x, int64_t n, uint16_t* y) -> int32_t {
-        hipLaunchKernelGGL(k_to_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, y);
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
-    };
-    auto combine = [&](float* dst) -> int32_t {
-        int64_t per_view = P * H;
-        hipLaunchKernelGGL(k_combine_f32, dim3((unsigned)((per_view + 255) / 256)), dim3(256), 0, s, t.xpre, NS,
-                           per_view, mlp->combine_type, dst);
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
-    };
-    int cur = 0;
-    const bool comb0 = NS > 1 && cl == 0;
-    if (t.Wb[0]) {      // bf16 copies of the hidden weights (as stored + transposed) for the LDS-DMA GEMMs of forward and backward
-        W16Table tb{};
-        for (int b = 0; b < nb; ++b) {
-            tb.w[2 * b] = mlp->fc0_w[b]; tb.w[2 * b + 1] = mlp->fc1_w[b];
-            tb.wb[2 * b] = t.Wb[2 * b]; tb.wb[2 * b + 1] = t.Wb[2 * b + 1];
-            tb.wt[2 * b] = t.Wt[2 * b]; tb.wt[2 * b + 1] = t.Wt[2 * b + 1];
-            tb.rows[2 * b] = tb.rows[2 * b + 1] = tb.cols[2 * b] = tb.cols[2 * b + 1] = H;
-        }
-        tb.n = 2 * nb;
-        if (t.z16)
-            for (int b = 0; b < n_lin_z; ++b) {
-                tb.w[tb.n] = mlp->lin_z_w[b]; tb.wb[tb.n] = t.Wz[b]; tb.wt[tb.n] = t.Wzt[b]; tb.rows[tb.n] = H; tb.cols[tb.n] = L;
-                ++tb.n;
-            }
-        const int64_t biggest = (int64_t)H * (H > L ? H : L);
-        hipLaunchKernelGGL(k_w_to_bf16, dim3((unsigned)((biggest + 255) / 256), (unsigned)tb.n), dim3(256), 0, s, tb);
-        PNR_LAUNCH_CHECK();
-        if (t.z16 && n_lin_z > 0) {
-            const int64_t n2 = MV * (L / 2);
-            hipLaunchKernelGGL(k_cols_to_bf16, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, t.zx, MV, E, L, t.z16);
-            PNR_LAUNCH_CHECK();
-        }
-    }
-    // lin_in (Din is not a multiple of 32: the fp32 kernels, fp32 operand zx)
-    PNR_TRY((gemm<false, false>(t.zx + L, E, mlp->lin_in_w, Din, mlp->lin_in_b, nullptr, 0, nullptr, 0, comb0 ? t.xpre : t.xw[cur], H,
-                                MV, H, Din, s, 1)));
-    if (comb0) PNR_TRY(combine(t.xw[cur]));
-    if (!(L > 0 && 0 < n_lin_z)) PNR_TRY(to16(t.xw[cur], t.rows[0] * H, t.A16[0]));     // block 0's input is final already
-    for (int b = 0; b < nb; ++b) {
-        const int64_t M = t.rows[b];
-        float* x = t.xw[cur];
-        if (L > 0 && b < n_lin_z) {
-            // x += lin_z[b](z): fp32 operand zx; result in place + its bf16 copy = the block input
-            const G16 g{nullptr, nullptr, t.A16[b]};
-            if (t.z16) {             // both operands as bf16 copies: the LDS-DMA kernel (same rounding, same sums)
-                PNR_TRY((gemm16<false, false>(G16{t.z16, nullptr, t.A16[b], t.Wz[b]}, nullptr, L, mlp->lin_z_w[b], L, mlp->lin_z_b[b], x, H,
-                                              nullptr, 0, x, H, M, H, L, s)));
-            } else if (L % 32 == 0 && al16(t.zx, E)) {
-                PNR_TRY((gemm16<false, false>(g, t.zx, E, mlp->lin_z_w[b], L, mlp->lin_z_b[b], x, H, nullptr, 0, x, H, M, H, L, s)));
-            } else {
-                PNR_TRY((gemm<false, false>(t.zx, E, mlp->lin_z_w[b], L, mlp->lin_z_b[b], x, H, nullptr, 0, x, H, M, H, L, s, 1)));
-                PNR_TRY(to16(x, M * H, t.A16[b]));
-            }
-        }
-        // h = fc_0(relu(x)): operand and result live on the tape only
-        PNR_TRY((gemm16<true, false>(G16{t.A16[b], nullptr, t.h16p[b], t.Wb[2 * b]}, nullptr, H, mlp->fc0_w[b], H, mlp->fc0_b[b], nullptr, 0,
-                                     nullptr, 0, nullptr, H, M, H, H, s)));
-        const bool comb = NS > 1 && b + 1 == cl;
-        float* dst = comb ? t.xpre : t.xw[cur ^ 1];
-        // x' = x + fc_1(relu(h)): fp32 for the chain, bf16 copy = the next block's input (unless lin_z / the reduction rewrite it)
-        const bool next_final = !comb && !(L > 0 && b + 1 < n_lin_z);
-        PNR_TRY((gemm16<true, false>(G16{t.h16p[b], nullptr, next_final ? t.A16[b + 1] : nullptr, t.Wb[2 * b + 1]}, nullptr, H, mlp->fc1_w[b], H,
-                                     mlp->fc1_b[b], x, H, nullptr, 0, dst, H, M, H, H, s)));
-        cur ^= 1;
-        if (comb) {
-            PNR_TRY(combine(t.xw[cur]));
-            if (!(L > 0 && b + 1 < n_lin_z)) PNR_TRY(to16(t.xw[cur], t.rows[b + 1] * H, t.A16[b + 1]));
-        }
-    }
-    t.A[nb] = t.xw[cur];                 // the head reads the fp32 stream (non-MFMA kernels)
-    PNR_TRY((gemm<true, false>(t.A[nb], H, mlp->lin_out_w, H, mlp->lin_out_b, nullptr, 0, nullptr, 0, t.o4, 4, P, 4, H, s, 0)));
-    hipLaunchKernelGGL(k_out_act, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, t.o4, P, out);
+static int32_t to_bf16(const float* x, int64_t n, uint16_t* y, hipStream_t s) {
+    hipLaunchKernelGGL(k_to_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, y);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
 }
 
+// The step's weight copies in one launch: a table entry per hidden weight (2 b: fc_0, 2 b + 1: fc_1) and, for the first n_z
+// blocks, per lin_z; copies(tb, entry, i, is_lin_z) sets the entry's destination(s) for hidden weight i / lin_z of block i.
+template <class Table, class Copies>
+static int32_t weight_copies(void (*kernel)(Table), const pnr_mlp* mlp, int n_z, Copies copies, hipStream_t s) {
+    const int H = mlp->d_hidden, L = mlp->d_latent;
+    Table tb{};
+    for (int i = 0; i < 2 * mlp->n_blocks; ++i) {
+        tb.w[i] = (i & 1) ? mlp->fc1_w[i >> 1] : mlp->fc0_w[i >> 1];
+        tb.rows[i] = tb.cols[i] = H;
+        copies(tb, i, i, false);
+    }
+    tb.n = 2 * mlp->n_blocks;
+    for (int b = 0; b < n_z; ++b, ++tb.n) {
+        tb.w[tb.n] = mlp->lin_z_w[b]; tb.rows[tb.n] = H; tb.cols[tb.n] = L;
+        copies(tb, tb.n, b, true);
+    }
+    const int64_t biggest = (int64_t)H * (H > L ? H : L);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((biggest + 255) / 256), (unsigned)tb.n), dim3(256), 0, s, tb);
+    PNR_LAUNCH_CHECK();
+    return PNR_OK;
+}
+
+// The taped forward.  fp32 tape: every block input and fc_0 output is a tape slot.  16-bit tape (train_precision = "bf16", see
+// Tape): same GEMMs, same operands after rounding; the fp32 residual stream ping-pongs between two buffers, and every GEMM
+// that produces a block input or an fc_0 output also (or only) writes the bf16 copy the tape keeps.
 int32_t point_train_fwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, PointSrc src, int64_t P,
                         int64_t pts_per_obj, float* out, void* tape, uint64_t tape_bytes, hipStream_t s) {
-    const bool t16 = tape_is_16bit(prm, mlp);
     if (tape_bytes < train_tape_bytes_p(prm, mlp, vw, P)) return PNR_E_WORKSPACE;
-    const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden;
-    const int E = (L + Din + 3) & ~3;      // row stride of zx (16-byte rows for the vector loads)
-    const int nb = mlp->n_blocks, cl = mlp->combine_layer;
+    const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden, E = feature_stride(mlp);
+    const int nb = mlp->n_blocks, cl = mlp->combine_layer, nz = n_lin_z(mlp);
     if (NS > 1 && cl >= nb) return PNR_E_UNSUPPORTED;
-    Tape t = carve_tape(mlp, vw, P, tape, t16);
-    if (t16) return point_train_fwd_tape16(prm, mlp, vw, src, P, pts_per_obj, out, t, s);
-    const int n_lin_z = cl < nb ? cl : nb;
+    const Tape t = carve_tape(mlp, vw, P, tape, tape_is_16bit(prm, mlp));
     const int64_t MV = (int64_t)NS * P;
     if (MV > 0x7fffffff) return PNR_E_SHAPE;
-    // GEMM products: 0 = fp32 MFMA, 1 = bf16 MFMA, 3 = bf16x3 split (fp32-class) — all on the fp32 tape
+    // GEMM products: 0 = fp32 MFMA, 1 = bf16 MFMA, 3 = bf16x3 split (fp32-class); the products on the 16-bit tape's operands
+    // take its bf16 forms
     const int half = prm->precision == PNR_BF16 ? 1 : prm->precision == PNR_BF16X3 ? 3 : 0;
+    const int tape_mode = t.h16 ? (int)PNR_DBG_MODE_TAPE16 : half;
     PNR_TRY(features_launch(*vw, src, 0, (int)P, pts_per_obj, L, Din, prm->use_code_viewdirs, prm->num_freqs, prm->freq_factor, t.zx, E, s,
                             (t.lat_cl && P >= 4096) ? latent_cl_build(*vw, t.lat_cl, s) : LatCL{}));
     PNR_LAUNCH_CHECK();
-    const bool comb0 = NS > 1 && cl == 0;
-    float* x0 = comb0 ? t.xpre : t.A[0];
-    if (t.Wt32[0] && !half) {      // W^T of the hidden weights (and lin_z) for the backward's dX products on k_sgemm_dma
-        W32Table tb{};
-        for (int b = 0; b < nb; ++b) {
-            tb.w[2 * b] = mlp->fc0_w[b]; tb.w[2 * b + 1] = mlp->fc1_w[b];
-            tb.wt[2 * b] = t.Wt32[2 * b]; tb.wt[2 * b + 1] = t.Wt32[2 * b + 1];
-            tb.rows[2 * b] = tb.rows[2 * b + 1] = tb.cols[2 * b] = tb.cols[2 * b + 1] = H;
+    if (t.Wb[0]) {      // bf16 copies of the hidden weights (as stored + transposed) for the LDS-DMA GEMMs of forward and backward
+        PNR_TRY(weight_copies<W16Table>(k_w_to_bf16, mlp, t.z16 ? nz : 0, [&](W16Table& tb, int e, int i, bool lin_z) {
+            tb.wb[e] = lin_z ? t.Wz[i] : t.Wb[i];
+            tb.wt[e] = lin_z ? t.Wzt[i] : t.Wt[i];
+        }, s));
+        if (t.z16 && nz > 0) {
+            const int64_t n2 = MV * (L / 2);
+            hipLaunchKernelGGL(k_cols_to_bf16, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, t.zx, MV, E, L, t.z16);
+            PNR_LAUNCH_CHECK();
         }
-        tb.n = 2 * nb;
-        if (t.Wzt32[0])
-            for (int b = 0; b < n_lin_z; ++b) { tb.w[tb.n] = mlp->lin_z_w[b]; tb.wt[tb.n] = t.Wzt32[b]; tb.rows[tb.n] = H; tb.cols[tb.n] = L; ++tb.n; }
-        const int64_t biggest = (int64_t)H * (H > L ? H : L);
-        hipLaunchKernelGGL(k_w_transpose_f32, dim3((unsigned)((biggest + 255) / 256), (unsigned)tb.n), dim3(256), 0, s, tb);
-        PNR_LAUNCH_CHECK();
+    } else if (t.Wt32[0] && !half) {      // W^T of the hidden weights (and lin_z) for the backward's dX products on k_sgemm_dma
+        PNR_TRY(weight_copies<W32Table>(k_w_transpose_f32, mlp, t.Wzt32[0] ? nz : 0, [&](W32Table& tb, int e, int i, bool lin_z) {
+            tb.wt[e] = lin_z ? t.Wzt32[i] : t.Wt32[i];
+        }, s));
     }
-    PNR_TRY((gemm<false, false>(t.zx + L, E, mlp->lin_in_w, Din, mlp->lin_in_b, nullptr, 0, nullptr, 0, x0, H, MV, H, Din, s, half)));
     auto combine = [&](float* dst) -> int32_t {
         int64_t per_view = P * H;
         hipLaunchKernelGGL(k_combine_f32, dim3((unsigned)((per_view + 255) / 256)), dim3(256), 0, s, t.xpre, NS,
@@ -2477,18 +2419,41 @@ int32_t point_train_fwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_vie
         PNR_LAUNCH_CHECK();
         return PNR_OK;
     };
-    if (comb0) PNR_TRY(combine(t.A[0]));
+    // does lin_z rewrite the input of block b?  (otherwise what lin_in / fc_1 / the view reduction left is final already)
+    auto lin_z_at = [&](int b) { return L > 0 && b < nz; };
+    // lin_in (Din is not a multiple of 32: the fp32 kernels, fp32 operand zx)
+    const bool comb0 = NS > 1 && cl == 0;
+    const Mat code = f32_mat(t.zx + L, E), x0 = f32_mat(comb0 ? t.xpre : t.stream(0), H);
+    PNR_TRY((gemm<false, false>(code, plain_weight(mlp->lin_in_w, Din), mlp->lin_in_b, NO_MAT, NO_MAT, x0, MV, H, Din, half, s)));
+    if (comb0) PNR_TRY(combine(t.stream(0)));
+    if (t.h16 && !lin_z_at(0)) PNR_TRY(to_bf16(t.stream(0), t.rows[0] * H, t.A16[0], s));
     for (int b = 0; b < nb; ++b) {
         const int64_t M = t.rows[b];
-        if (L > 0 && b < n_lin_z)
-            PNR_TRY((gemm<false, false>(t.zx, E, mlp->lin_z_w[b], L, mlp->lin_z_b[b], t.A[b], H, nullptr, 0, t.A[b], H, M, H, L, s, half)));
-        PNR_TRY((gemm<true, false>(t.A[b], H, mlp->fc0_w[b], H, mlp->fc0_b[b], nullptr, 0, nullptr, 0, t.h[b], H, M, H, H, s, half)));
+        const Mat x = f32_mat(t.stream(b), H);
+        if (lin_z_at(b)) {
+            // x += lin_z[b](z), in place; 16-bit tape: + its bf16 copy = the block input, from the same launch when z suits a
+            // bf16-product kernel (as bf16 copies of both operands: the LDS-DMA kernel, same rounding, same sums)
+            const bool z_mfma = t.h16 && (t.z16 || (L % 32 == 0 && al16(t.zx, E)));
+            const Mat xin{x.f32, z_mfma ? t.A16[b] : nullptr, H};
+            PNR_TRY((gemm<false, false>(t.z(), t.lin_z_w(mlp->lin_z_w[b], b), mlp->lin_z_b[b], x, NO_MAT, xin, M, H, L,
+                                        z_mfma ? tape_mode : half, s)));
+            if (t.h16 && !z_mfma) PNR_TRY(to_bf16(x.f32, M * H, t.A16[b], s));
+        }
+        // h = fc_0(relu(x)); 16-bit tape: operand and result live on the tape only
+        PNR_TRY((gemm<true, false>(t.block_in(b), t.hidden_w(mlp->fc0_w[b], 2 * b), mlp->fc0_b[b], NO_MAT, NO_MAT, t.hidden(b), M, H, H,
+                                   tape_mode, s)));
+        // x' = x + fc_1(relu(h)): fp32 for the chain, into the view reduction's input where that follows; 16-bit tape: its bf16
+        // copy = the next block's input (unless lin_z / the reduction rewrite it)
         const bool comb = NS > 1 && b + 1 == cl;
-        float* dst = comb ? t.xpre : t.A[b + 1];
-        PNR_TRY((gemm<true, false>(t.h[b], H, mlp->fc1_w[b], H, mlp->fc1_b[b], t.A[b], H, nullptr, 0, dst, H, M, H, H, s, half)));
-        if (comb) PNR_TRY(combine(t.A[b + 1]));
+        const Mat x_next{comb ? t.xpre : t.stream(b + 1), !comb && !lin_z_at(b + 1) ? t.A16[b + 1] : nullptr, H};
+        PNR_TRY((gemm<true, false>(t.hidden(b), t.hidden_w(mlp->fc1_w[b], 2 * b + 1), mlp->fc1_b[b], x, NO_MAT, x_next, M, H, H, tape_mode, s)));
+        if (comb) {
+            PNR_TRY(combine(t.stream(b + 1)));
+            if (t.h16 && !lin_z_at(b + 1)) PNR_TRY(to_bf16(t.stream(b + 1), t.rows[b + 1] * H, t.A16[b + 1], s));
+        }
     }
-    PNR_TRY((gemm<true, false>(t.A[nb], H, mlp->lin_out_w, H, mlp->lin_out_b, nullptr, 0, nullptr, 0, t.o4, 4, P, 4, H, s, half)));
+    const Mat x_out = f32_mat(t.stream(nb), H), o4 = f32_mat(t.o4, 4);
+    PNR_TRY((gemm<true, false>(x_out, plain_weight(mlp->lin_out_w, H), mlp->lin_out_b, NO_MAT, NO_MAT, o4, P, 4, H, half, s)));
     hipLaunchKernelGGL(k_out_act, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, t.o4, P, out);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
@@ -2498,26 +2463,23 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
                   int64_t pts_per_obj, const float* out, const float* d_out, void* tape, uint64_t tape_bytes,
                   const pnr_mlp_grads* gr, float* const* d_latent, float* d_xyz, float* d_z, void* workspace,
                   uint64_t ws_bytes, hipStream_t s) {
-    const bool t16 = tape_is_16bit(prm, mlp);
     if (tape_bytes < train_tape_bytes_p(prm, mlp, vw, P)) return PNR_E_WORKSPACE;
     if (ws_bytes < train_bwd_workspace_bytes(mlp, vw, P)) return PNR_E_WORKSPACE;
-    const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden;
-    const int E = (L + Din + 3) & ~3;
-    const int nb = mlp->n_blocks, cl = mlp->combine_layer;
+    const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden, E = feature_stride(mlp);
+    const int nb = mlp->n_blocks, cl = mlp->combine_layer, nz = n_lin_z(mlp);
     if (NS > 1 && cl >= nb) return PNR_E_UNSUPPORTED;
-    Tape t = carve_tape(mlp, vw, P, tape, t16);
-    if (t16) t.A[nb] = t.xw[nb & 1];          // where the forward's fp32 stream ended (point_train_fwd_tape16)
-    const int n_lin_z = cl < nb ? cl : nb;
+    const Tape t = carve_tape(mlp, vw, P, tape, tape_is_16bit(prm, mlp));
     const int64_t MV = (int64_t)NS * P;
     const int half = prm->precision == PNR_BF16 ? 1 : prm->precision == PNR_BF16X3 ? 3 : 0;
-    uint8_t* wp = (uint8_t*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    float* dx = (float*)wp;                wp += a256((uint64_t)MV * H * 4);
-    float* dx2 = (float*)wp;               wp += a256((uint64_t)MV * H * 4);
-    float* dh = (float*)wp;                wp += a256((uint64_t)MV * H * 4);
-    float* dzx = (float*)wp;               wp += a256((uint64_t)MV * E * 4);
-    float* do4 = (float*)wp;               wp += a256((uint64_t)P * 16);
-    const DetWs dws{(float*)wp, det_ws_floats(mlp)};  wp += a256(det_ws_floats(mlp) * 4);
-    float* lat_part = (float*)wp;          wp += a256(latent_part_bytes(vw, P));
+    const int tape_mode = t.h16 ? (int)PNR_DBG_MODE_TAPE16 : half;
+    uint8_t* wp = (uint8_t*)round_up_256(workspace);
+    float* dx = (float*)wp;                wp += round_up_256((uint64_t)MV * H * 4);
+    float* dx2 = (float*)wp;               wp += round_up_256((uint64_t)MV * H * 4);
+    float* dh = (float*)wp;                wp += round_up_256((uint64_t)MV * H * 4);
+    float* dzx = (float*)wp;               wp += round_up_256((uint64_t)MV * E * 4);
+    float* do4 = (float*)wp;               wp += round_up_256((uint64_t)P * 16);
+    const DetWs dws{(float*)wp, det_ws_floats(mlp)};  wp += round_up_256(det_ws_floats(mlp) * 4);
+    float* lat_part = (float*)wp;          wp += round_up_256(latent_part_bytes(vw, P));
     uint8_t* lat_q = wp;                   // [scale words (256 B)][fixed-point maps], latent_q_bytes
     const bool want_p = d_xyz || d_z;
     bool want_lat = false;
@@ -2528,58 +2490,44 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
     hipLaunchKernelGGL(k_out_act_bwd, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const float4*)out,
                        (const float4*)d_out, P, (float4*)do4);
     PNR_LAUNCH_CHECK();
-    PNR_TRY((grad_w<true>(do4, 4, t.A[nb], H, gr->lin_out_w, H, gr->lin_out_b, P, 4, H, s, half, dws)));
+    const Mat g4 = f32_mat(do4, 4), x_out = f32_mat(t.stream(nb), H);
+    PNR_TRY((grad_w<true>(g4, x_out, gr->lin_out_w, H, gr->lin_out_b, P, 4, H, half, dws, s)));
     bool dz_started = false;
     // 16-bit tape: the fp32 dh buffer holds the two bf16 streams instead (dh, and the copy of dx)
     uint16_t* dh16 = (uint16_t*)dh;
     uint16_t* dx16 = dh16 + (size_t)MV * H;
-    bool dx16_valid = false;
-    if (head_dx_ok(do4, mlp->lin_out_w, H, t.A[nb], H, dx, H, H, 4)) {
+    // the gradient stream: fp32 for the residual sums, with its bf16 copy (b16) while one is valid
+    Mat g = f32_mat(dx, H);
+    if (head_dx_ok(do4, mlp->lin_out_w, H, x_out.f32, H, dx, H, H, 4)) {
         // the head's dX as a stream, with the gradient stream's first bf16 copy from the same pass (the head is behind the
         // view reduction: P rows, the row count of the last block)
-        const bool copy16 = t16 && nb > 0 && t.rows[nb - 1] == P;
-        PNR_TRY(head_dx(do4, mlp->lin_out_w, H, t.A[nb], H, dx, H, copy16 ? dx16 : nullptr, P, H, s));
-        dx16_valid = copy16;
+        const bool copy16 = t.h16 && nb > 0 && t.rows[nb - 1] == P;
+        PNR_TRY(head_dx(do4, mlp->lin_out_w, H, x_out.f32, H, dx, H, copy16 ? dx16 : nullptr, P, H, s));
+        if (copy16) g.b16 = dx16;
     } else {
-        PNR_TRY((gemm<false, true>(do4, 4, mlp->lin_out_w, H, nullptr, nullptr, 0, t.A[nb], H, dx, H, P, H, 4, s, half)));
+        PNR_TRY((gemm<false, true>(g4, plain_weight(mlp->lin_out_w, H), nullptr, NO_MAT, x_out, g, P, H, 4, half, s)));
     }
-    auto to16 = [&](const float* x, int64_t n, uint16_t* y) -> int32_t {
-        hipLaunchKernelGGL(k_to_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, y);
-        PNR_LAUNCH_CHECK();
-        return PNR_OK;
-    };
     for (int b = nb - 1; b >= 0; --b) {
         const int64_t M = t.rows[b];
-        if (t16) {
-            // the same four GEMMs, every operand read as the bf16 the fp32-tape form would round it to: the tape operands /
-            // masks, and (round 4) the gradient stream — dh exists as bf16 only (its two readers stage it as bf16 anyway), dx
-            // keeps its fp32 form for the residual sum and gets a bf16 copy from the epilogue that produces it.  Same roundings
-            // of the same values: gradients stay bit-identical to the fp32-tape form; 0.76x the bytes of a block's backward.
-            if (!dx16_valid) { PNR_TRY(to16(dx, M * H, dx16)); dx16_valid = true; }
-            PNR_TRY((grad_w<true>(dx, H, nullptr, H, gr->fc1_w[b], H, gr->fc1_b[b], M, H, H, s, half, dws, t.h16p[b], dx16)));
-            PNR_TRY((gemm16<false, true>(G16{dx16, t.h16p[b], dh16, t.Wt[2 * b + 1]}, nullptr, H, mlp->fc1_w[b], H, nullptr, nullptr, 0, nullptr, H,
-                                         nullptr, H, M, H, H, s)));
-            PNR_TRY((grad_w<true>(nullptr, H, nullptr, H, gr->fc0_w[b], H, gr->fc0_b[b], M, H, H, s, half, dws, t.A16[b], dh16)));
-            PNR_TRY((gemm16<false, true>(G16{dh16, t.A16[b], dx16, t.Wt[2 * b]}, nullptr, H, mlp->fc0_w[b], H, nullptr, dx, H, nullptr, H, dx, H,
-                                         M, H, H, s)));
-        } else {
-        PNR_TRY((grad_w<true>(dx, H, t.h[b], H, gr->fc1_w[b], H, gr->fc1_b[b], M, H, H, s, half, dws)));
-        PNR_TRY((gemm<false, true>(dx, H, mlp->fc1_w[b], H, nullptr, nullptr, 0, t.h[b], H, dh, H, M, H, H, s, half, t.Wt32[2 * b + 1])));
-        PNR_TRY((grad_w<true>(dh, H, t.A[b], H, gr->fc0_w[b], H, gr->fc0_b[b], M, H, H, s, half, dws)));
-        PNR_TRY((gemm<false, true>(dh, H, mlp->fc0_w[b], H, nullptr, dx, H, t.A[b], H, dx, H, M, H, H, s, half, t.Wt32[2 * b])));
-        }
-        if (L > 0 && b < n_lin_z) {
-            if (t16 && t.z16 && dx16_valid)
-                PNR_TRY((grad_w<false>(dx, H, nullptr, L, gr->lin_z_w[b], L, gr->lin_z_b[b], M, H, L, s, half, dws, t.z16, dx16)));
-            else
-                PNR_TRY((grad_w<false>(dx, H, t.zx, E, gr->lin_z_w[b], L, gr->lin_z_b[b], M, H, L, s, half, dws)));
+        // The four products of a block.  16-bit tape: every operand is read as the bf16 the fp32-tape form would round it to —
+        // the tape operands / masks, and the gradient stream: dh exists as bf16 only (its two readers stage it as bf16 anyway), dx
+        // keeps its fp32 form for the residual sum and gets a bf16 copy from the epilogue that produces it.  Same roundings
+        // of the same values: gradients stay bit-identical to the fp32-tape form; 0.76x the bytes of a block's backward.
+        if (t.h16 && !g.b16) { PNR_TRY(to_bf16(dx, M * H, dx16, s)); g.b16 = dx16; }
+        const Mat x_in = t.block_in(b), hid = t.hidden(b);
+        const Mat gh = t.h16 ? Mat{nullptr, dh16, H} : f32_mat(dh, H);
+        PNR_TRY((grad_w<true>(g, hid, gr->fc1_w[b], H, gr->fc1_b[b], M, H, H, half, dws, s)));
+        PNR_TRY((gemm<false, true>(g, t.hidden_w_dx(mlp->fc1_w[b], 2 * b + 1), nullptr, NO_MAT, hid, gh, M, H, H, tape_mode, s)));
+        PNR_TRY((grad_w<true>(gh, x_in, gr->fc0_w[b], H, gr->fc0_b[b], M, H, H, half, dws, s)));
+        PNR_TRY((gemm<false, true>(gh, t.hidden_w_dx(mlp->fc0_w[b], 2 * b), nullptr, f32_only(g), x_in, g, M, H, H, tape_mode, s)));
+        if (L > 0 && b < nz) {
+            // lin_z: with the bf16 copy of the latent columns both products read the bf16 forms, else fp32 operands only
+            const Mat z = t.z(), gz = z.b16 ? g : f32_only(g);
+            PNR_TRY((grad_w<false>(gz, z, gr->lin_z_w[b], L, gr->lin_z_b[b], M, H, L, half, dws, s)));
             if (want_dz) {
-                if (t16 && t.z16 && dx16_valid)
-                    PNR_TRY((gemm16<false, true>(G16{dx16, nullptr, nullptr, t.Wzt[b]}, nullptr, H, mlp->lin_z_w[b], L, nullptr,
-                                                 dz_started ? dzx : nullptr, E, nullptr, 0, dzx, E, M, L, H, s)));
-                else
-                    PNR_TRY((gemm<false, true>(dx, H, mlp->lin_z_w[b], L, nullptr, dz_started ? dzx : nullptr, E, nullptr, 0,
-                                               dzx, E, M, L, H, s, half, t16 ? nullptr : t.Wzt32[b])));
+                const Mat dz = f32_mat(dzx, E), dz_so_far = f32_mat(dz_started ? dzx : nullptr, E);
+                PNR_TRY((gemm<false, true>(gz, t.lin_z_w_dx(mlp->lin_z_w[b], b), nullptr, dz_so_far, NO_MAT, dz, M, L, H,
+                                           z.b16 ? tape_mode : half, s)));
                 dz_started = true;
             }
         }
@@ -2589,13 +2537,15 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
                                per_view, mlp->combine_type, dx2);
             PNR_LAUNCH_CHECK();
             float* tmp = dx; dx = dx2; dx2 = tmp;
-            dx16_valid = false;         // (P rows became NS P rows of another buffer)
+            g = f32_mat(dx, H);         // (P rows became NS P rows of another buffer: no bf16 copy of those)
         }
     }
-    PNR_TRY((grad_w<false>(dx, H, t.zx + L, E, gr->lin_in_w, Din, gr->lin_in_b, MV, H, Din, s, half, dws)));
+    const Mat gx = f32_only(g), code = f32_mat(t.zx + L, E);
+    PNR_TRY((grad_w<false>(gx, code, gr->lin_in_w, Din, gr->lin_in_b, MV, H, Din, half, dws, s)));
     if ((want_p || want_lat) && L > 0 && !dz_started) PNR_HIP_CHECK(hipMemsetAsync(dzx, 0, (size_t)MV * E * 4, s));
     if (want_p)
-        PNR_TRY((gemm<false, true>(dx, H, mlp->lin_in_w, Din, nullptr, nullptr, 0, nullptr, 0, dzx + L, E, MV, Din, H, s, half)));
+        PNR_TRY((gemm<false, true>(gx, plain_weight(mlp->lin_in_w, Din), nullptr, NO_MAT, NO_MAT, f32_mat(dzx + L, E), MV, Din, H,
+                                   half, s)));
     // small single-level map: latent gradient on per-block partial maps + an ordered reduction (bit-reproducible)
     if (want_lat && L > 0 && latent_grad_in_lds(vw)) {
         const int T = vw->lat_h[0] * vw->lat_w[0], C = vw->lat_c[0], views = vw->n_objs * vw->n_views;
@@ -2680,29 +2630,22 @@ template <bool RELU>
 static int32_t debug_linear(pnr_debug_linear_args* a, hipStream_t s, DbgSite* d) {
     const int64_t M = a->m;
     const int N = a->n, K = a->k;
-    const float* X = (const float*)a->x;
-    const float* W = (const float*)a->w;
-    const float* Mk = (const float*)a->mk;
-    float* Y = (float*)a->y;
-    const G16 g{(const uint16_t*)a->x16, (const uint16_t*)a->mk16, (uint16_t*)a->y16, (const uint16_t*)a->w16};
+    const Mat x{(const float*)a->x, (const uint16_t*)a->x16, a->ldx}, res{a->r, nullptr, a->ldr};
+    const Mat mask{(const float*)a->mk, (const uint16_t*)a->mk16, a->ldm}, y{(const float*)a->y, (const uint16_t*)a->y16, a->ldy};
+    // w16: the (n, k) copy in the form the mode reads (bf16 for PNR_DBG_MODE_TAPE16, fp32 W^T for a mode-0 dX)
+    const Weight w{(const float*)a->w, a->ldw, (const uint16_t*)a->w16, (const float*)a->w16};
+    const bool mode_ok = a->mode == 0 || a->mode == 1 || a->mode == 3 || a->mode == PNR_DBG_MODE_TAPE16;
     switch (a->op) {
     case PNR_DBG_OP_FWD:
-        if (a->mode == PNR_DBG_MODE_TAPE16)
-            return gemm16<RELU, false>(g, X, a->ldx, W, a->ldw, a->b, a->r, a->ldr, Mk, a->ldm, Y, a->ldy, M, N, K, s, d);
-        if (a->mode != 0 && a->mode != 1 && a->mode != 3) return PNR_E_UNSUPPORTED;
-        return gemm<RELU, false>(X, a->ldx, W, a->ldw, a->b, a->r, a->ldr, Mk, a->ldm, Y, a->ldy, M, N, K, s, a->mode, nullptr, d);
+        return mode_ok ? gemm<RELU, false>(x, w, a->b, res, mask, y, M, N, K, a->mode, s, d) : PNR_E_UNSUPPORTED;
     case PNR_DBG_OP_DX:
-        if (a->mode == PNR_DBG_MODE_TAPE16)
-            return gemm16<RELU, true>(g, X, a->ldx, W, a->ldw, a->b, a->r, a->ldr, Mk, a->ldm, Y, a->ldy, M, N, K, s, d);
-        if (a->mode != 0 && a->mode != 1 && a->mode != 3) return PNR_E_UNSUPPORTED;
-        return gemm<RELU, true>(X, a->ldx, W, a->ldw, a->b, a->r, a->ldr, Mk, a->ldm, Y, a->ldy, M, N, K, s, a->mode,
-                                (const float*)a->w16, d);
+        return mode_ok ? gemm<RELU, true>(x, w, a->b, res, mask, y, M, N, K, a->mode, s, d) : PNR_E_UNSUPPORTED;
     case PNR_DBG_OP_HEAD_DX:
-        if (!head_dx_ok(X, W, a->ldw, Mk, a->ldm, Y, a->ldy, N, K)) return PNR_E_UNSUPPORTED;
-        return head_dx(X, W, a->ldw, Mk, a->ldm, Y, a->ldy, (uint16_t*)a->y16, M, N, s, d);
+        if (!head_dx_ok(x.f32, w.f32, a->ldw, mask.f32, a->ldm, y.f32, a->ldy, N, K)) return PNR_E_UNSUPPORTED;
+        return head_dx(x.f32, w.f32, a->ldw, mask.f32, a->ldm, (float*)a->y, a->ldy, (uint16_t*)a->y16, M, N, s, d);
     case PNR_DBG_OP_DW:
-        return grad_w<RELU>(a->g, a->ldg, X, a->ldx, Y, a->ldy, a->db, M, N, K, s, a->mode, DetWs{a->ws, a->ws_floats},
-                            (const uint16_t*)a->x16, (const uint16_t*)a->g16, d);
+        return grad_w<RELU>(Mat{a->g, (const uint16_t*)a->g16, a->ldg}, x, (float*)a->y, a->ldy, a->db, M, N, K, a->mode,
+                            DetWs{a->ws, a->ws_floats}, s, d);
     }
     return PNR_E_UNSUPPORTED;
 }

@@ -245,3 +245,77 @@ def test_headline_dtype_is_held_to_survey_8c():
     # every BASELINE shape is benchmarked in the headline dtype
     for wl in bench.WORKLOADS:
         assert wl == bench.DEFAULT or (wl, h) in bench.SECONDARY, wl
+
+
+# pnr_train_tape_bytes_for (and, after each fp32 entry, pnr_train_tape_bytes) over _tape_configs(), in its order
+_TAPE_BYTES = (
+    164096, 164096, 167424, 167424, 12484864, 12484864, 256, 4096, 8651008, 164096, 167424, 12484864, 164096, 164096,
+    167424, 167424, 12484864, 12484864, 256, 4096, 8651008, 164096, 167424, 12484864, 164096, 164096, 167424, 167424,
+    12484864, 12484864, 256, 4096, 8651008, 164096, 167424, 12484864, 164096, 164096, 168704, 168704, 17072384, 17072384,
+    256, 6400, 17432832, 164096, 168704, 17072384, 164096, 164096, 171776, 171776, 29655296, 29655296, 256, 7936, 23724288,
+    164096, 171776, 29655296, 189696, 189696, 193536, 193536, 14148864, 14148864, 25856, 30208, 10315008, 189696, 193536,
+    14148864, 266496, 266496, 270336, 270336, 14225664, 14225664, 25856, 30208, 10315008, 266496, 270336, 14225664, 317696,
+    317696, 321536, 321536, 14276864, 14276864, 25856, 30208, 10315008, 317696, 321536, 14276864, 240896, 240896, 246528,
+    246528, 22064384, 22064384, 77056, 84224, 22424832, 240896, 246528, 22064384, 317696, 317696, 326400, 326400, 34724096,
+    34724096, 77056, 85760, 28716288, 317696, 326400, 34724096, 295168, 295168, 300544, 300544, 21004544, 21004544, 131328,
+    137216, 17170688, 295168, 300544, 21004544, 688384, 688384, 693760, 693760, 21397760, 21397760, 131328, 137216,
+    17170688, 688384, 693760, 21397760, 950528, 950528, 955904, 955904, 21659904, 21659904, 131328, 137216, 17170688,
+    950528, 955904, 21659904, 557312, 557312, 568064, 568064, 42631424, 42631424, 393472, 405760, 42991872, 557312, 568064,
+    42631424, 950528, 950528, 964352, 964352, 55607552, 55607552, 393472, 407296, 49283328, 950528, 964352, 55607552, 256,
+    256, 6400, 6400, 22413568, 22413568, 256, 6400, 22413568, 256, 6400, 22413568, 256, 256, 6400, 6400, 22413568, 22413568,
+    256, 6400, 22413568, 256, 6400, 22413568, 256, 256, 6400, 6400, 22413568, 22413568, 256, 6400, 22413568, 256, 6400,
+    22413568, 256, 256, 8448, 8448, 29753600, 29753600, 256, 8448, 29753600, 256, 8448, 29753600, 256, 256, 14592, 14592,
+    53346560, 53346560, 256, 14592, 53346560, 256, 14592, 53346560, 25856, 25856, 32512, 32512, 24077568, 24077568, 25856,
+    32512, 24077568, 25856, 32512, 24077568, 25856, 25856, 32512, 32512, 24077568, 24077568, 25856, 32512, 24077568, 25856,
+    32512, 24077568, 25856, 25856, 32512, 32512, 24077568, 24077568, 25856, 32512, 24077568, 25856, 32512, 24077568, 77056,
+    77056, 86272, 86272, 34745600, 34745600, 77056, 86272, 34745600, 77056, 86272, 34745600, 77056, 77056, 92416, 92416,
+    58338560, 58338560, 77056, 92416, 58338560, 77056, 92416, 58338560, 131328, 131328, 139520, 139520, 30933248, 30933248,
+    131328, 139520, 30933248, 131328, 139520, 30933248, 131328, 131328, 139520, 139520, 30933248, 30933248, 131328, 139520,
+    30933248, 131328, 139520, 30933248, 131328, 131328, 139520, 139520, 30933248, 30933248, 131328, 139520, 30933248,
+    131328, 139520, 30933248, 393472, 393472, 407808, 407808, 55312640, 55312640, 393472, 407808, 55312640, 393472, 407808,
+    55312640, 393472, 393472, 413952, 413952, 78905600, 78905600, 393472, 413952, 78905600, 393472, 413952, 78905600,
+    10486016, 10486016, 10509056, 10509056, 103547136, 103547136, 10486016, 10501888, 74187008, 10486016, 10509056,
+    103547136, 10486016, 10486016, 10509056, 10509056, 103547136, 103547136, 10486016, 10501888, 74187008, 10486016,
+    10509056, 103547136, 10486016, 10486016, 10509056, 10509056, 103547136, 103547136, 10486016, 10501888, 74187008,
+    10486016, 10509056, 103547136, 10486016, 10486016, 10515712, 10515712, 130154752, 130154752, 10486016, 10516736,
+    134349056, 10486016, 10515712, 130154752, 10486016, 10486016, 10540288, 10540288, 230818048, 230818048, 10486016,
+    10529024, 184680704, 10486016, 10540288, 230818048, 10511616, 10511616, 10535168, 10535168, 105211136, 105211136,
+    10511616, 10528000, 75851008, 10511616, 10535168, 105211136, 11126016, 11126016, 11149568, 11149568, 105825536,
+    105825536, 10511616, 10528000, 75851008, 11126016, 11149568, 105825536, 11535616, 11535616, 11559168, 11559168,
+    106235136, 106235136, 10511616, 10528000, 75851008, 11535616, 11559168, 106235136, 10562816, 10562816, 10593536,
+    10593536, 135146752, 135146752, 10562816, 10594560, 139341056, 10562816, 10593536, 135146752, 11177216, 11177216,
+    11232512, 11232512, 236424448, 236424448, 10562816, 10606848, 189672704, 11177216, 11232512, 236424448, 10617088,
+    10617088, 10642176, 10642176, 112066816, 112066816, 10617088, 10636032, 86900992, 10617088, 10642176, 112066816,
+    13762816, 13762816, 13787904, 13787904, 115212544, 115212544, 13762816, 13781760, 90046720, 13762816, 13787904,
+    115212544, 15859968, 15859968, 15885056, 15885056, 117309696, 117309696, 15859968, 15878912, 92143872, 15859968,
+    15885056, 117309696, 10879232, 10879232, 10915072, 10915072, 155713792, 155713792, 10879232, 10919168, 172491008,
+    10879232, 10915072, 155713792, 14024960, 14024960, 14085376, 14085376, 259522816, 259522816, 14024960, 14077184,
+    225968384, 14024960, 14085376, 259522816,
+)
+
+
+def _tape_configs():
+    import itertools
+    return itertools.product((64, 120, 512), (0, 100, 512), ((1, 0), (1, 3), (1, 5), (3, 0), (3, 3)),
+                             ("fp32", "bf16", "bf16_tape_fp32"), (0, 1, 4096))
+
+
+def test_train_tape_bytes_are_pinned():
+    """The training tape's layout (csrc/train_f32.hip carve_tape), seen through its size: d_hidden that suits no MFMA kernel /
+    the bf16 MFMA kernel / the LDS-DMA kernels, d_latent absent / unaligned / suiting the LDS-DMA lin_z, one view and three,
+    the view reduction in front of block 0, inside the chain and (one view) behind it, the fp32 tape, the 16-bit tape and the
+    fp32 tape under bf16 products, and 0, 1 and 4096 points.  The values are those of the layout the kernels were measured on."""
+    import ctypes as C
+    from pixel_nerf_multiscale_amd import _native as N
+    got = []
+    for H, L, (NS, cl), prec, P in _tape_configs():
+        mlp = N.pnr_mlp(d_in=42, d_latent=L, d_hidden=H, d_out=4, n_blocks=5, combine_layer=cl)
+        vw = N.pnr_views(n_objs=1, n_views=NS, n_levels=1 if L else 0)
+        vw.lat_c[0], vw.lat_h[0], vw.lat_w[0] = L, 8, 8
+        prm = N.pnr_params(precision=N.PNR_F32 if prec == "fp32" else N.PNR_BF16, train_tape_fp32=int(prec == "bf16_tape_fp32"))
+        got.append(((H, L, NS, cl, prec, P), N.lib.pnr_train_tape_bytes_for(C.byref(prm), C.byref(mlp), C.byref(vw), P)))
+        if prec == "fp32":
+            got.append(((H, L, NS, cl, "no params", P), N.lib.pnr_train_tape_bytes(C.byref(mlp), C.byref(vw), P)))
+    assert len(got) == len(_TAPE_BYTES) == 540
+    wrong = [(cfg, v, want) for (cfg, v), want in zip(got, _TAPE_BYTES) if v != want]
+    assert not wrong, wrong[:5]

@@ -27,8 +27,8 @@ def test_every_kernel_id_names_a_real_launch_site():
         "SGEMM_DMA_WT": "k_sgemm_dma<", "MGEMM_BF16X3": "k_mgemm_bf16x3<", "MGEMM_BF16": "k_mgemm_bf16<", "SGEMM_DMA": "k_sgemm_dma<",
         "MGEMM_F32": "k_mgemm_f32<", "LINEAR_HEAD_512": "k_linear_head<", "LINEAR_HEAD_256": "k_linear_head<",
         "GEMM_F32": "k_gemm_f32<", "HGEMM_DMA_M16": "k_hgemm_dma<", "HGEMM_DMA": "k_hgemm_dma<",
-        "MGEMM_BF16_A16_M16": "PNR_G16_LAUNCH", "MGEMM_BF16_A16": "PNR_G16_LAUNCH", "MGEMM_BF16_M16": "PNR_G16_LAUNCH",
-        "MGEMM_BF16_G16": "PNR_G16_LAUNCH", "HEAD_DX": "k_head_dx", "COL_SUMS16": "k_col_sums16", "COL_SUMS": "k_col_sums",
+        "MGEMM_BF16_A16_M16": "k_mgemm_bf16<true", "MGEMM_BF16_A16": "k_mgemm_bf16<true", "MGEMM_BF16_M16": "k_mgemm_bf16<true",
+        "MGEMM_BF16_G16": "k_mgemm_bf16<true", "HEAD_DX": "k_head_dx", "COL_SUMS16": "k_col_sums16", "COL_SUMS": "k_col_sums",
         "GRAD_W_SKINNY48": "k_grad_w_skinny<48>", "GRAD_W_SKINNY96": "k_grad_w_skinny<", "MGEMM_BF16X3_DW": "k_mgemm_bf16x3<",
         "HGEMM_DMA_KT": "k_hgemm_dma_kt<", "MGEMM_BF16_DW_A16B16": "k_mgemm_bf16<false",
         "MGEMM_BF16_DW_B16": "k_mgemm_bf16<false", "MGEMM_BF16_DW": "k_mgemm_bf16<",
@@ -40,8 +40,8 @@ def test_every_kernel_id_names_a_real_launch_site():
         sites = [m.end() for m in re.finditer(r"\bPNR_DBG_K_%s\b" % name, src)]
         assert len(sites) == 1, (name, len(sites))
         # (a record that chooses between two sites by the launch's own condition precedes both launches)
-        nxt = [m.group(0) for m in re.finditer(r"hipLaunchKernelGGL\(\(?[^,]*|PNR_G16_LAUNCH\(", src[sites[0]:])][:4]
-        assert any(expect[name] in n for n in nxt[:2 if expect[name] != "PNR_G16_LAUNCH" else 4]), (name, nxt)
+        nxt = [m.group(0) for m in re.finditer(r"hipLaunchKernelGGL\(\(?[^,]*", src[sites[0]:])][:2]
+        assert any(expect[name] in n for n in nxt), (name, nxt)
 
 
 def test_case_table_spans_the_edges():
