@@ -26,7 +26,8 @@ extern "C" {
 #define PNR_VERSION 102          /* 0.1.2: pnr_views.uv_scale_{x,y} (opt-in upstream texel mapping); 101: output strides, per-object ray index stride.
                                   * Added since, backward compatible (no bump): the training front end, pnr_train_batch / pnr_rgb_loss / pnr_rgb_loss_bwd;
                                   * the evaluation back end, pnr_eval_frame / pnr_eval_frame_workspace_bytes; mesh extraction,
-                                  * pnr_grid_points / pnr_mc_workspace_bytes / pnr_mc_count / pnr_mc_emit */
+                                  * pnr_grid_points / pnr_mc_workspace_bytes / pnr_mc_count / pnr_mc_emit; the training back end, pnr_optim_chunk_elems /
+                                  * pnr_optim_plan / pnr_optim_workspace_bytes / pnr_adam_step */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -422,6 +423,80 @@ int32_t pnr_mc_count(const float* field, int32_t stride, int32_t nx, int32_t ny,
 int32_t pnr_mc_emit(const float* field, int32_t stride, int32_t nx, int32_t ny, int32_t nz, double iso,
                     const double* origin, const double* scale, const void* workspace, uint64_t workspace_bytes,
                     int64_t n_vertices, int64_t n_triangles, double* vertices, int32_t* triangles, void* stream);
+
+/* ---- training back end: what follows loss.backward() in train/train.py:375-412 (GradScaler.unscale_, clip_grad_norm_,
+ * scaler.step, scaler.update) with Adam over every trainable tensor (trainlib/trainer.py:169), csrc/optim.hip ------------------
+ *
+ * Layout.  Gradients, exp_avg (m) and exp_avg_sq (v) each live in ONE flat fp32 buffer of n_flat floats; the parameters stay
+ * where the caller's framework put them.  A device table of segments names each tensor: its parameter pointer, its offset in
+ * the flat buffers (a multiple of 4, so an aligned tensor keeps 16-byte accesses) and its length.  A device table of chunks
+ * cuts the segments into pieces of at most pnr_optim_chunk_elems() = 4096 elements, none straddling a segment;
+ * pnr_optim_plan builds it on the host.  A segment of length 0 has no chunk: its p, m, v are not touched (a tensor without a
+ * gradient this step, which torch's Adam skips too).
+ *
+ * Arithmetic of one element, every operation a separately rounded fp32 operation (nothing fused), IEEE square root and division:
+ *     g  = (grad * inv_scale) * clip_coef
+ *     m' = b1 * m + omb1 * g                       b1 = (float)beta1, omb1 = (float)(1.0 - beta1)
+ *     v' = b2 * v + (omb2 * g) * g                 b2 = (float)beta2, omb2 = (float)(1.0 - beta2)
+ *     p' = p - step_size * (m' / (sqrt(v') * rsqrt_bc2 + (float)eps))
+ * with step_size = (float)(lr / (1 - beta1^t)) and rsqrt_bc2 = (float)(1 / sqrt(1 - beta2^t)) computed in fp64 on the device
+ * from the device-resident step count t AFTER its increment: torch.optim.Adam with weight_decay = 0, amsgrad = False, in
+ * another order of roundings (torch: lerp, addcmul, addcdiv).  lr, beta1, beta2, eps, max_norm are host doubles read at every
+ * call, so a learning-rate schedule is a different argument.
+ * Norm and clip (torch.nn.utils.clip_grad_norm_): total = sqrt(sum (grad * inv_scale)^2), the product rounded to fp32, its
+ * square and the sum in fp64; clip_coef = (float)min(1, max_norm / (total + 1e-6)) in fp64; max_norm <= 0 gives 1.
+ * Scaler (torch.amp.GradScaler.update), optional: `scaler` NULL means inv_scale = 1 and scale / growth_tracker are left alone.
+ * Otherwise inv_scale = (float)(1.0 / (double)scale) of the scale the gradients carry, the caller having initialised
+ * state->scale; then, non-finite gradients: scale *= backoff_factor, growth_tracker = 0; finite: growth_tracker + 1, and when
+ * that reaches growth_interval: scale *= growth_factor (kept where the product is not finite), growth_tracker = 0.
+ * Deviation from torch: a non-finite gradient (any grad * inv_scale that is Inf or NaN) skips the step WITH OR WITHOUT a
+ * scaler — p, m, v and step keep their bits, skipped += 1, clip_coef = 0 — where torch without a scaler writes NaN into every
+ * parameter.  grad is never written: after the call it still holds the scaled, unclipped values.
+ *
+ * Three launches on `stream`, no floating-point atomics, no host read (csrc/optim.hip): per chunk an fp64 partial and a
+ * non-finite flag into `workspace`; ONE workgroup that adds the partials (thread i of 256 the chunks i, i + 256, .. ascending,
+ * then a fixed tree) and fills the state record; the update, which returns at once when found_inf is set.  The summation
+ * order depends on the chunk table alone: the same inputs give the same bits.  The longest addition path of grad_norm is
+ * 16 + 8 + ceil(n_chunks / 256) + 8 fp64 additions.  The update takes 16-byte loads and stores in every chunk whose parameter
+ * pointer and flat offset are both 16-byte aligned and a scalar body otherwise.  The device tables are the caller's: an
+ * entry that does not fit (segment index or range outside the tables / n_flat) is skipped, nothing else is verified.
+ * Every check is made before any launch:
+ *   PNR_E_SHAPE      n_segments, n_chunks or n_flat negative, n_chunks >= 2^31; chunks without segments or flat floats;
+ *                    scaler->growth_interval < 1
+ *   PNR_E_NULL       state NULL; with n_chunks > 0: segments, chunks, grad, exp_avg, exp_avg_sq or workspace NULL
+ *   PNR_E_WORKSPACE  fewer workspace bytes than pnr_optim_workspace_bytes (12 per chunk, each part rounded up to 16; 0 for a
+ *                    count that is negative or too large)
+ *   PNR_E_ALIGN      grad, exp_avg, exp_avg_sq or workspace not 16-byte aligned; state, segments or chunks not 8-byte aligned
+ * n_chunks == 0 (no tensor has a gradient) returns PNR_OK without a launch: nothing moves, as in torch. */
+typedef struct pnr_optim_state {     /* device record, 56 bytes; the caller zeroes it once (and sets `scale` with a scaler) */
+    double grad_norm;                /* total of the last call, Inf / NaN included */
+    float clip_coef;                 /* applied by the last call; 0 on a skipped step */
+    float scale;                     /* GradScaler's scale, AFTER the last call's update */
+    float inv_scale;                 /* what the last call multiplied the gradients by */
+    int32_t found_inf;               /* 1: the last call skipped */
+    int32_t growth_tracker;
+    int32_t reserved0;
+    int64_t step;                    /* t: applied steps */
+    int64_t skipped;                 /* skipped steps */
+    float step_size;                 /* of the last applied step */
+    float rsqrt_bc2;
+} pnr_optim_state;
+typedef struct pnr_optim_segment { float* param; int64_t offset; int64_t n; } pnr_optim_segment;          /* device table */
+typedef struct pnr_optim_chunk { int32_t segment; int32_t reserved; int64_t first; } pnr_optim_chunk;     /* device table: elements
+                                                                                                           * [first, first + 4096) of the segment, cut at its end */
+typedef struct pnr_optim_scaler { float growth_factor; float backoff_factor; int32_t growth_interval; int32_t reserved; } pnr_optim_scaler;   /* host */
+
+int32_t pnr_optim_chunk_elems(void);
+/* Host only.  Writes the chunk table of segments of seg_n[0 .. n_segments) elements, in ascending (segment, first) order, into
+ * chunks_out (a HOST array of max_chunks entries, or NULL to count) and returns the number of chunks the table needs — entries
+ * past max_chunks are counted, not written.  PNR_E_SHAPE for a negative count or length, PNR_E_NULL for seg_n NULL. */
+int64_t pnr_optim_plan(const int64_t* seg_n, int32_t n_segments, pnr_optim_chunk* chunks_out, int64_t max_chunks);
+uint64_t pnr_optim_workspace_bytes(int64_t n_chunks);
+int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_segments, const pnr_optim_chunk* chunks, int64_t n_chunks,
+                      const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n_flat,
+                      double lr, double beta1, double beta2, double eps, double max_norm,
+                      const pnr_optim_scaler* scaler /* host, or NULL */, pnr_optim_state* state,
+                      void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* Timing hook for bench.py: microseconds between the first and last point-MLP launch of the most recent
  * pnr_render on this thread is NOT kept (no global state); instead the caller brackets calls with

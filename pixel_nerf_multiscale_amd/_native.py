@@ -88,6 +88,26 @@ class pnr_debug_linear_args(C.Structure):
     ]
 
 
+class pnr_optim_state(C.Structure):
+    """The optimizer's device record (56 bytes); optim.DeviceAdam views its fields as 0-dim tensors at these offsets."""
+    _fields_ = [("grad_norm", C.c_double), ("clip_coef", C.c_float), ("scale", C.c_float), ("inv_scale", C.c_float),
+                ("found_inf", C.c_int32), ("growth_tracker", C.c_int32), ("reserved0", C.c_int32), ("step", C.c_int64),
+                ("skipped", C.c_int64), ("step_size", C.c_float), ("rsqrt_bc2", C.c_float)]
+
+
+class pnr_optim_segment(C.Structure):
+    _fields_ = [("param", _fp), ("offset", C.c_int64), ("n", C.c_int64)]
+
+
+class pnr_optim_chunk(C.Structure):
+    _fields_ = [("segment", C.c_int32), ("reserved", C.c_int32), ("first", C.c_int64)]
+
+
+class pnr_optim_scaler(C.Structure):
+    _fields_ = [("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # every symbol include/pnr.h declares: name -> (restype, argtypes)
 _i32, _i64, _u64, _f = C.c_int32, C.c_int64, C.c_uint64, C.c_float
 PROTOTYPES = {
@@ -134,6 +154,11 @@ PROTOTYPES = {
     "pnr_mc_count": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, _fp, _u64, _fp, _fp]),
     "pnr_mc_emit": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _fp, _u64,
                            _i64, _i64, _fp, _fp, _fp]),
+    "pnr_optim_chunk_elems": (_i32, []),
+    "pnr_optim_plan": (_i64, [C.POINTER(C.c_int64), _i32, _fp, _i64]),        # chunks_out: a HOST address
+    "pnr_optim_workspace_bytes": (_u64, [_i64]),
+    "pnr_adam_step": (_i32, [_fp, _i32, _fp, _i64, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double,
+                             C.c_double, C.POINTER(pnr_optim_scaler), _fp, _fp, _u64, _fp]),
     "pnr_event_create": (_i32, [C.POINTER(C.c_void_p)]),
     "pnr_event_record": (_i32, [_fp, _fp]),
     "pnr_event_elapsed_ms": (_i32, [_fp, _fp, C.POINTER(C.c_float)]),

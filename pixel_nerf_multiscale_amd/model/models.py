@@ -111,8 +111,9 @@ class PixelNeRFNet(torch.nn.Module):
         trans = -torch.bmm(rot, poses[:, :3, 3:])
         self.poses = torch.cat((rot, trans), dim=-1).contiguous()
         # filled on the device: a host tensor copied over would make every encode() of a training step wait for the stream
+        # (fill_ takes the scalar as a kernel argument; `image_shape[1] = height` would copy a host scalar and wait as well)
         self.image_shape = torch.full((2,), float(width), device=dev)
-        self.image_shape[1] = float(height)
+        self.image_shape[1:].fill_(float(height))
         focal = torch.as_tensor(focal, dtype=torch.float32, device=dev)
         if focal.dim() == 0:
             focal = focal[None, None].repeat(1, 2)

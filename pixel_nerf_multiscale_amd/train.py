@@ -98,3 +98,28 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
         loss_dict["rf"] = stats[1]
     loss_dict["t"] = stats[2]
     return total, loss_dict
+
+
+def train_step(net, render_par, data, optim, *, grad_hook=None, **calc_losses_kw):
+    """Trainer.train_step of the reference (train/train.py:375-412) with both ends on the device: zero_grad, calc_losses,
+    optim.scale(loss).backward(), grad_hook, optim.step().
+
+    optim        optim.DeviceAdam: unscale, clip_grad_norm_, the found-inf skip, Adam and the scaler's update are its step()
+    grad_hook    called with no arguments between backward and the step — the place for
+                 parallel.allreduce_gradients(params); a gradient it replaces is re-adopted by optim.step()
+    the rest     calc_losses' keywords (ray_batch_size, nviews, z_near, z_far, loss, use_bbox, is_train)
+
+    -> calc_losses' loss_dict with "grad_norm" added (the fp64 norm of the unscaled gradients before clipping, what
+    clip_grad_norm_ returns): 0-dim device views, like the others.  Nothing in here waits for the device; whether the step
+    was applied is optim.found_inf, also on the device."""
+    optim.zero_grad()
+    out = calc_losses(net, render_par, data, **calc_losses_kw)
+    if not out:
+        return {}
+    loss, loss_dict = out
+    optim.scale(loss).backward()
+    if grad_hook is not None:
+        grad_hook()
+    optim.step()
+    loss_dict["grad_norm"] = optim.grad_norm
+    return loss_dict
