@@ -148,7 +148,13 @@ static __global__ void __launch_bounds__(256) k_grad_w_f32(
 // tiles stored r-major so a fragment read is 64 consecutive floats), register-staged global prefetch of
 // the next r-tile behind the MFMAs.  One float per lane per operand: a = A[row = l%32][r = l/32],
 // b = B[r = l/32][col = l%32]; acc[j] = C[8*(j/4) + 4*(l/32) + j%4][l%32].
+// (the vector types of all the tile GEMMs of this section)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // Loads are unconditional (indices clamped into the operand, the value zeroed afterwards): a predicated
 // load would put a branch and a full vmcnt(0) wait in front of every element.
@@ -258,15 +264,14 @@ static __global__ void __launch_bounds__(256) k_linear_head(const float* __restr
     }
 }
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
     f32x2v f = {a, b};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2v));
 }
 
-// ------------------------------------------------------------------ shared by the three MFMA tile GEMMs below
+// ------------------------------------------------------------------ shared by the seven 128 x 128 MFMA tile GEMMs below
+// (k_mgemm_f32, k_mgemm_bf16, k_mgemm_bf16x3: register-staged; k_hgemm_dma, k_sgemm_dma, k_sgemm_dma_kt, k_hgemm_dma_kt: LDS-DMA.)
+// The tile order, the accumulators and their 2 x 2 products, the LDS-DMA issue and wait and the epilogues are stated here, once.
 // 1-D grid with an XCD-aware tile order.  Workgroup ids go round the 8 XCDs, each with its own L2: the tiles that share an
 // operand — the N tiles of one 128-row block of the activations, or all (m, n) tiles of one reduction split — get
 // consecutive slots on ONE XCD, so the operand is fetched from HBM once instead of once per tile (measured before:
@@ -289,6 +294,87 @@ __host__ __device__ __forceinline__ bool mgemm_tile_of(int block, int M, int N, 
 template <bool SPLIT>
 __device__ __forceinline__ bool mgemm_tile(int M, int N, int Rn, int r_per_split, int& bx, int& by, int& bz) {
     return mgemm_tile_of<SPLIT>((int)blockIdx.x, M, N, Rn, r_per_split, bx, by, bz);
+}
+
+__device__ __forceinline__ void tile_zero(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+
+// One reduction step of a wave's 2 x 2 fragments (a0, a1: rows wm, wm + 32; b0, b1: columns wn, wn + 32), one helper per operand
+// form.  The operands are SWAPPED (mfma(b, a)): the 32 x 32 tiles come out transposed, as mgemm_epilogue below takes them.
+__device__ __forceinline__ void tile_mfma_f32(f32x16 (&acc)[2][2], float a0, float a1, float b0, float b1) {
+    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, a0, acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, a0, acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, a1, acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, a1, acc[1][1], 0, 0, 0);
+}
+__device__ __forceinline__ void tile_mfma_bf16(f32x16 (&acc)[2][2], bf16x8 a0, bf16x8 a1, bf16x8 b0, bf16x8 b1) {
+    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc[1][1], 0, 0, 0);
+}
+// bf16x3, one accumulator: both fragments as their hi and lo images; hi*lo + lo*hi + hi*hi, the small terms first
+__device__ __forceinline__ void mfma_bf16x3(f32x16& acc, bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, al, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl, ah, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, ah, acc, 0, 0, 0);
+}
+// relu on packed bf16 values (sign bit set -> 0): what staging relu(fp32) and rounding gives
+__device__ __forceinline__ bf16x8 relu_bf16x8(bf16x8 v) {
+    const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    return __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, v), z));
+}
+
+// A wave's share of one k-step by LDS-DMA: PIECES (4 or 8) lane-linear 1-KiB pieces — lane l's 16 bytes from src + voff[j] to LDS
+// byte dst + 0x400 j + 16 l.  M0 (the destination base) is the compiler's: saved, written and restored in the ONE statement that
+// reads it.  hipcc does not count these loads: dma_step_wait does.
+template <int PIECES>
+__device__ __forceinline__ void dma_issue(const uint32_t (&voff)[PIECES], const char* src, uint32_t dst) {
+    static_assert(PIECES == 4 || PIECES == 8, "a wave issues 4 or 8 pieces per k-step");
+    uint32_t keep;
+    if constexpr (PIECES == 8)
+        asm volatile("s_mov_b32 %0, m0\n\t"
+                     "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %9\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %9\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %9\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %9\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %6, %9\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %7, %9\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %8, %9\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(keep)
+                     : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]), "v"(voff[7]),
+                       "s"(src), "s"(dst)
+                     : "memory", "scc");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\t"
+                     "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
+                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(src), "s"(dst) : "memory", "scc");
+}
+// The head of k-step ks of a DMA k-loop with DEPTH k-steps in flight: wait for this wave's pieces of k-step ks — DEPTH 1: the
+// only ones outstanding; DEPTH 3 (4-piece k-steps): all but those of the `younger` (= nk - 1 - ks) k-steps issued behind it —
+// and for the wave's own LDS reads, then the barrier: every wave's pieces of k-step ks are in, and the slot the caller issues
+// into next has no reader left.
+template <int DEPTH>
+__device__ __forceinline__ void dma_step_wait(int younger = 0) {
+    static_assert(DEPTH == 1 || DEPTH == 3, "one or three k-steps in flight");
+    if (DEPTH == 3 && younger >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else if (DEPTH == 3 && younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
 }
 
 // Epilogue of a 128 x 128 workgroup tile whose MFMAs ran with the operands SWAPPED (mfma(b, a)): the 32 x 32 tiles come out
@@ -522,12 +608,7 @@ static __global__ void __launch_bounds__(256) k_mgemm_f32(
     const int re = SPLIT ? min(Rn, rb + r_per_split) : Rn;
     const int wm = (wv >> 1) * 64, wn = (wv & 1) * 64;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    tile_zero(acc);
     float va[8], vb[8];
     float rs = 0.f;
     const bool fast_a = (vec_ok & 1) && m0 + 128 <= M, fast_b = (vec_ok & 2) && n0 + 128 <= N;   // block-uniform
@@ -571,13 +652,7 @@ static __global__ void __launch_bounds__(256) k_mgemm_f32(
             float(&a)[4] = fa[g & 1];
             float(&b)[4] = fb[g & 1];
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                // (operands swapped: transposed tiles for mgemm_epilogue)
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[2 * q], a[2 * q], acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[2 * q + 1], a[2 * q], acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[2 * q], a[2 * q + 1], acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[2 * q + 1], a[2 * q + 1], acc[1][1], 0, 0, 0);
-            }
+            for (int q = 0; q < 2; ++q) tile_mfma_f32(acc, a[2 * q], a[2 * q + 1], b[2 * q], b[2 * q + 1]);
             if (g < 3) {        // keep the next group's reads ahead of this group's MFMAs in the schedule
                 __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
             }
@@ -738,12 +813,7 @@ static __global__ void __launch_bounds__(256) k_mgemm_bf16(
     const int wm = (wv >> 1) * 64, wn = (wv & 1) * 64;
     const int lr = lane >> 5, lc = lane & 31;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    tile_zero(acc);
     float4 va[4], vb[4];
     float rs = 0.f;
     mh_fetch<A_RC, A16>(A, lda, m0, M, rb, re, va);
@@ -767,17 +837,9 @@ static __global__ void __launch_bounds__(256) k_mgemm_bf16(
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            bf16x8 a0 = *(const bf16x8*)&As[buf][wm + lc][16 * s + 8 * lr];
-            bf16x8 a1 = *(const bf16x8*)&As[buf][wm + 32 + lc][16 * s + 8 * lr];
-            bf16x8 b0 = *(const bf16x8*)&Bs[buf][wn + lc][16 * s + 8 * lr];
-            bf16x8 b1 = *(const bf16x8*)&Bs[buf][wn + 32 + lc][16 * s + 8 * lr];
-            // operands swapped: the tile comes out TRANSPOSED — lane lc holds row m, its registers 4 consecutive n per group
-            // of four (n = 8 (e >> 2) + 4 lr + (e & 3)) — so the epilogue moves 16-byte rows of C / R / the mask instead of
-            // single elements (64 -> 16 memory instructions per thread and tensor; same products, same sums)
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc[1][1], 0, 0, 0);
+            const int ko = 16 * s + 8 * lr;
+            tile_mfma_bf16(acc, *(const bf16x8*)&As[buf][wm + lc][ko], *(const bf16x8*)&As[buf][wm + 32 + lc][ko],
+                           *(const bf16x8*)&Bs[buf][wn + lc][ko], *(const bf16x8*)&Bs[buf][wn + 32 + lc][ko]);
         }
         if (rowsum && by == 0 && t < 128) {       // bias gradient = row sums of the (bf16-rounded) A tile
 #pragma unroll
@@ -813,7 +875,6 @@ static __global__ void __launch_bounds__(256) k_mgemm_bf16(
 // odd, their r >> 1 distinct mod 8 — then fall on 16 different bank quads.  An LDS-DMA piece is lane-linear (lane l -> base + 16 l =
 // row l >> 3, physical chunk l & 7), so the swizzle is on the SOURCE address.  A wave issues 8 pieces per k-step (waves 0, 1: the
 // A tile, waves 2, 3: the B tile).  Requires K % 64 == 0 (else the register-staged kernel).
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 template <bool RELU_A, bool M16>
 static __global__ void __launch_bounds__(256, 2) k_hgemm_dma(
     const uint16_t* __restrict__ A, int lda, const uint16_t* __restrict__ B, int ldb, const float* __restrict__ bias,
@@ -841,32 +902,11 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma(
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)ring;
     const uint32_t dst0 = __builtin_amdgcn_readfirstlane(ring_lds + (loads_b ? 16384 : 0) + 8192 * (wv & 1));
     const char* src_tile = (const char*)src + (size_t)x0 * ld * 2;
-    auto issue = [&](int ks) __attribute__((always_inline)) {
-        const char* sb = src_tile + (size_t)ks * 128;                // 64 k = 128 B further along every row
-        const uint32_t dst = dst0 + (uint32_t)(ks & 1) * 32768u;
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\t"
-                     "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %6, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %7, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %8, %9\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]), "v"(voff[7]),
-                       "s"(sb), "s"(dst)
-                     : "memory", "scc");
+    auto issue = [&](int ks) __attribute__((always_inline)) {        // 64 k = 128 B further along every row
+        dma_issue<8>(voff, src_tile + (size_t)ks * 128, dst0 + (uint32_t)(ks & 1) * 32768u);
     };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    tile_zero(acc);
     const int nk = K >> 6;
     issue(0);
     // fragment addresses within a slot (fixed over the loop): row r, logical chunk 2 s + lr of the row's eight
@@ -880,10 +920,7 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma(
             fb[i][sp] = 16384u + (uint32_t)rb * 128u + 16u * ((2 * sp + lr) ^ ((rb >> 1) & 7));
         }
     for (int ks = 0; ks < nk; ++ks) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's pieces of k-step ks (the only ones outstanding)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();          // every wave's pieces of k-step ks are in; slot (ks + 1) & 1 has no reader left
-        asm volatile("" ::: "memory");
+        dma_step_wait<1>();
         if (ks + 1 < nk) issue(ks + 1);
         const char* slot = ring + (ks & 1) * 32768;
 #pragma unroll
@@ -892,15 +929,8 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma(
             bf16x8 a1 = *(const bf16x8*)(slot + fa[1][sp]);
             const bf16x8 b0 = *(const bf16x8*)(slot + fb[0][sp]);
             const bf16x8 b1 = *(const bf16x8*)(slot + fb[1][sp]);
-            if (RELU_A) {       // relu on the bf16 values (sign bit set -> 0): what staging relu(fp32) and rounding gives
-                const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-                a0 = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, a0), z));
-                a1 = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, a1), z));
-            }
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc[1][1], 0, 0, 0);
+            if (RELU_A) { a0 = relu_bf16x8(a0); a1 = relu_bf16x8(a1); }
+            tile_mfma_bf16(acc, a0, a1, b0, b1);
         }
     }
     if (tile_epilogue_ok(bias, R, ldr, Mk, ldm, M16, C, ldc, C16, ldc16, N))
@@ -944,25 +974,11 @@ static __global__ void __launch_bounds__(256, 2) k_sgemm_dma(
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)ring;
     const uint32_t dst0 = __builtin_amdgcn_readfirstlane(ring_lds + (loads_b ? 8192 : 0) + 4096 * (wv & 1));
     const char* src_tile = (const char*)src + (size_t)x0 * ld * 4;
-    auto issue = [&](int ks) __attribute__((always_inline)) {
-        const char* sb = src_tile + (size_t)ks * 64;                 // 16 floats further along every row
-        const uint32_t dst = dst0 + (uint32_t)(ks & 3) * 16384u;
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\t"
-                     "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(sb), "s"(dst) : "memory", "scc");
+    auto issue = [&](int ks) __attribute__((always_inline)) {        // 16 floats further along every row
+        dma_issue<4>(voff, src_tile + (size_t)ks * 64, dst0 + (uint32_t)(ks & 3) * 16384u);
     };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    tile_zero(acc);
     const int nk = K >> 4;
     for (int ks = 0; ks < 3 && ks < nk; ++ks) issue(ks);
     // fragment addresses within a slot: row r, chunk 2 cp + lr of chunk pair cp
@@ -976,13 +992,7 @@ static __global__ void __launch_bounds__(256, 2) k_sgemm_dma(
             fb[i][cp] = 8192u + (uint32_t)rb * 64u + 16u * ((2 * cp + lr) ^ ((rb >> 3) & 3));
         }
     for (int ks = 0; ks < nk; ++ks) {
-        const int younger = nk - 1 - ks;
-        if (younger >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_step_wait<3>(nk - 1 - ks);
         if (ks + 3 < nk) issue(ks + 3);
         const char* slot = ring + (ks & 3) * 16384;
 #pragma unroll
@@ -998,12 +1008,7 @@ static __global__ void __launch_bounds__(256, 2) k_sgemm_dma(
             const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
             const float bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv0[e], av0[e], acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv1[e], av0[e], acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv0[e], av1[e], acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv1[e], av1[e], acc[1][1], 0, 0, 0);
-            }
+            for (int e = 0; e < 4; ++e) tile_mfma_f32(acc, av0[e], av1[e], bv0[e], bv1[e]);
         }
     }
     if (tile_epilogue_ok(bias, R, ldr, (const void*)Mk, ldm, false, C, ldc, nullptr, 0, N))
@@ -1040,36 +1045,16 @@ static __global__ void __launch_bounds__(256, 2) k_sgemm_dma_kt(
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)ring;
     const uint32_t dst0 = __builtin_amdgcn_readfirstlane(ring_lds + (loads_b ? 8192 : 0) + 4096 * (wv & 1));
     const char* src_rb = (const char*)src + (size_t)rb * ld * 4;
-    auto issue = [&](int ks) __attribute__((always_inline)) {
-        const char* sb = src_rb + (size_t)ks * 16 * ld * 4;
-        const uint32_t dst = dst0 + (uint32_t)(ks & 3) * 16384u;
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\t"
-                     "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(sb), "s"(dst) : "memory", "scc");
+    auto issue = [&](int ks) __attribute__((always_inline)) {        // 16 reduction rows further
+        dma_issue<4>(voff, src_rb + (size_t)ks * 16 * ld * 4, dst0 + (uint32_t)(ks & 3) * 16384u);
     };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    tile_zero(acc);
     const int nk = (re - rb) >> 4;
     for (int ks = 0; ks < 3 && ks < nk; ++ks) issue(ks);
     float rs = 0.f;
     for (int ks = 0; ks < nk; ++ks) {
-        const int younger = nk - 1 - ks;
-        if (younger >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_step_wait<3>(nk - 1 - ks);
         if (ks + 3 < nk) issue(ks + 3);
         const float* As = (const float*)(ring + (ks & 3) * 16384);          // [16 rows][128]
         const float* Bs = As + 2048;
@@ -1079,10 +1064,7 @@ static __global__ void __launch_bounds__(256, 2) k_sgemm_dma_kt(
             const float a0 = As[r * 128 + wm + lc], a1 = As[r * 128 + wm + 32 + lc];
             float b0 = Bs[r * 128 + wn + lc], b1 = Bs[r * 128 + wn + 32 + lc];
             if (RELU_B) { b0 = fmaxf(b0, 0.f); b1 = fmaxf(b1, 0.f); }
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, a0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, a0, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, a1, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, a1, acc[1][1], 0, 0, 0);
+            tile_mfma_f32(acc, a0, a1, b0, b1);
         }
         if (rowsum && by == 0 && t < 128) {
 #pragma unroll
@@ -1104,7 +1086,6 @@ static __global__ void __launch_bounds__(256, 2) k_sgemm_dma_kt(
 // LDS image: [64 rows][16 chunks of 16 B], chunk ch of row r at 256 r + 16 (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))) — the
 // swizzle that keeps both the transposed reads and row reads conflict-free on 256-byte rows (cdna_hip_programming.md T10);
 // applied on the DMA's source address.  Needs the slice bounds and M to be multiples of 64 (no zero-filled tail rows).
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 template <bool RELU_B>
 static __global__ void __launch_bounds__(256, 2) k_hgemm_dma_kt(
     const uint16_t* __restrict__ A, int lda, const uint16_t* __restrict__ B, int ldb, float* __restrict__ C, int ldc,
@@ -1132,32 +1113,11 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma_kt(
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)ring;
     const uint32_t dst0 = __builtin_amdgcn_readfirstlane(ring_lds + (loads_b ? 16384 : 0) + 8192 * (wv & 1));
     const char* src_rb = (const char*)src + (size_t)rb * ld * 2;
-    auto issue = [&](int ks) __attribute__((always_inline)) {
-        const char* sb = src_rb + (size_t)ks * 64 * ld * 2;             // 64 reduction rows further
-        const uint32_t dst = dst0 + (uint32_t)(ks & 1) * 32768u;
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\t"
-                     "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %6, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %7, %9\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %8, %9\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]), "v"(voff[7]),
-                       "s"(sb), "s"(dst)
-                     : "memory", "scc");
+    auto issue = [&](int ks) __attribute__((always_inline)) {        // 64 reduction rows further
+        dma_issue<8>(voff, src_rb + (size_t)ks * 64 * ld * 2, dst0 + (uint32_t)(ks & 1) * 32768u);
     };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    tile_zero(acc);
     const int nk = (re - rb) >> 6;
     if (nk > 0) issue(0);
     // transposed-read addresses within a slot: fragment (i, s, h) = rows 16 s + 8 lr + 4 h .. + 3 of the 16-column block that
@@ -1187,10 +1147,7 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma_kt(
         return __builtin_bit_cast(bf16x8, v);
     };
     for (int ks = 0; ks < nk; ++ks) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's pieces of k-step ks (the only ones outstanding)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_step_wait<1>();
         if (ks + 1 < nk) issue(ks + 1);
         const uint32_t slot_lds = ring_lds + (uint32_t)(ks & 1) * 32768u;
 #pragma unroll
@@ -1199,15 +1156,8 @@ static __global__ void __launch_bounds__(256, 2) k_hgemm_dma_kt(
             const bf16x8 a1 = frag(slot_lds, fa[1][sp]);
             bf16x8 b0 = frag(slot_lds, fb[0][sp]);
             bf16x8 b1 = frag(slot_lds, fb[1][sp]);
-            if (RELU_B) {
-                const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-                b0 = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, b0), z));
-                b1 = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, b1), z));
-            }
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc[1][1], 0, 0, 0);
+            if (RELU_B) { b0 = relu_bf16x8(b0); b1 = relu_bf16x8(b1); }
+            tile_mfma_bf16(acc, a0, a1, b0, b1);
         }
         if (rowsum && by == 0 && t < 128) {       // bias gradient = sums over the points of A's column t, pairwise like k_mgemm_bf16
             const char* slot = ring + (ks & 1) * 32768;
@@ -1278,12 +1228,7 @@ static __global__ void __launch_bounds__(256) k_mgemm_bf16x3(
     const int wm = (wv >> 1) * 64, wn = (wv & 1) * 64;
     const int lr = lane >> 5, lc = lane & 31;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    tile_zero(acc);
     float4 va[4], vb[4];
     float rs = 0.f;
     mh_fetch<A_RC>(A, lda, m0, M, rb, re, va);
@@ -1303,16 +1248,10 @@ static __global__ void __launch_bounds__(256) k_mgemm_bf16x3(
             bf16x8 a1h = *(const bf16x8*)&As[0][wm + 32 + lc][ko], a1l = *(const bf16x8*)&As[1][wm + 32 + lc][ko];
             bf16x8 b0h = *(const bf16x8*)&Bs[0][wn + lc][ko], b0l = *(const bf16x8*)&Bs[1][wn + lc][ko];
             bf16x8 b1h = *(const bf16x8*)&Bs[0][wn + 32 + lc][ko], b1l = *(const bf16x8*)&Bs[1][wn + 32 + lc][ko];
-            // (operands swapped: transposed tiles for mgemm_epilogue)
-#define PNR_X3(ACC, AH, AL, BH, BL)                                              \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BH, AL, ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BL, AH, ACC, 0, 0, 0);        \
-    ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BH, AH, ACC, 0, 0, 0)
-            PNR_X3(acc[0][0], a0h, a0l, b0h, b0l);
-            PNR_X3(acc[0][1], a0h, a0l, b1h, b1l);
-            PNR_X3(acc[1][0], a1h, a1l, b0h, b0l);
-            PNR_X3(acc[1][1], a1h, a1l, b1h, b1l);
-#undef PNR_X3
+            mfma_bf16x3(acc[0][0], a0h, a0l, b0h, b0l);
+            mfma_bf16x3(acc[0][1], a0h, a0l, b1h, b1l);
+            mfma_bf16x3(acc[1][0], a1h, a1l, b0h, b0l);
+            mfma_bf16x3(acc[1][1], a1h, a1l, b1h, b1l);
         }
         if (rowsum && by == 0 && t < 128) {
 #pragma unroll
