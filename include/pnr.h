@@ -498,6 +498,50 @@ int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_segments, con
                       const pnr_optim_scaler* scaler /* host, or NULL */, pnr_optim_state* state,
                       void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* ---- upstream pixelNeRF's latent map: the tail of its SpatialEncoder.forward, csrc/upsample.hip -------------------------------
+ *
+ * Every encoder level is resized to level 0's size (bilinear, align_corners=True) and the levels are concatenated along the
+ * channels into ONE map of sumC = sum lat_c channels — what F.interpolate + torch.cat give, with the arithmetic written down.
+ * levels / d_levels, lat_c, lat_h, lat_w are HOST arrays of n_levels entries; the level maps and the outputs live on the device.
+ *
+ * Position of fine index D on an axis with n_in coarse and n_out fine samples (exact integers, no rounded scale factor):
+ *     n_in == 1 or n_out == 1:  i0 = 0, lam = 0
+ *     otherwise:                num = D (n_in - 1);  i0 = num / (n_out - 1) (integer division);
+ *                               lam = (float)(num % (n_out - 1)) / (float)(n_out - 1) (IEEE division)
+ *     i1 = min(i0 + 1, n_in - 1);  mu = 1.0f - lam
+ * Value, every operation a separately rounded fp32 operation (nothing fused), a, b the taps of row y0 at columns x0, x1 and
+ * c, d those of row y1:
+ *     top = mux a + lamx b;  bot = mux c + lamx d;  out = muy top + lamy bot
+ * A level of level 0's own size comes out as a copy; a level may be larger than level 0 (the same formula).  out16 is the
+ * round-to-nearest-even conversion of the fp32 value `out` holds or would hold; out, out16 or both may be asked for (one
+ * launch each).  `out` is stored along W, out16 along the channels, both in whole row segments.
+ *
+ * Adjoint.  d_levels[l][n, c, y, x] = the sum of w g over every tap of every fine node that lands on (y, x), g the node's
+ * d_out value, w = fl(wy wx) with wy in {muy, lamy} and wx in {mux, lamx} as above; where i0 == i1 both taps land on the same
+ * texel and both count.  Gather form: a thread owns one texel and walks the fine nodes of its support (rows ascending,
+ * columns ascending inside a row, taps y0x0, y0x1, y1x0, y1x1 inside a node), adds the products (double)w (double)g in fp64 and
+ * rounds ONCE to fp32.  No floating-point atomics: the same inputs give the same bits.  Level 0 and every level of its size
+ * are a slice copy.  d_levels[l] is WRITTEN (=), not accumulated; a NULL entry is skipped.  One launch per level.
+ *
+ * Every check is made before any launch:
+ *   PNR_E_NULL         levels / d_levels, lat_c, lat_h, lat_w or d_out NULL; a levels[i] NULL; out and out16 both NULL
+ *   PNR_E_SHAPE        n_levels outside 1..PNR_MAX_LEVELS; a size < 1, H or W above 32768; n_maps < 0; a level, out or d_out
+ *                      of 2^31 elements or more; out16 with sumC % 8 != 0
+ *   PNR_E_UNSUPPORTED  out16 with a dtype other than PNR_BF16 / PNR_F16
+ *   PNR_E_ALIGN        out16 not 16-byte aligned
+ * n_maps == 0 returns PNR_OK without a launch. */
+int32_t pnr_upsample_concat(const float* const* levels,       /* device, (N, C_i, H_i, W_i) fp32 NCHW contiguous */
+                            const int32_t* lat_c, const int32_t* lat_h, const int32_t* lat_w,
+                            int32_t n_levels, int32_t n_maps  /* N */,
+                            float* out,                       /* (N, sumC, H_0, W_0) fp32 NCHW, or NULL */
+                            void* out16, int32_t out16_dtype, /* (N, H_0, W_0, sumC) channels-last PNR_BF16 / PNR_F16, or NULL */
+                            void* stream);
+int32_t pnr_upsample_concat_bwd(const float* d_out,           /* (N, sumC, H_0, W_0) */
+                                const int32_t* lat_c, const int32_t* lat_h, const int32_t* lat_w,
+                                int32_t n_levels, int32_t n_maps,
+                                float* const* d_levels,       /* WRITTEN (=), not accumulated; a NULL entry is skipped */
+                                void* stream);
+
 /* Timing hook for bench.py: microseconds between the first and last point-MLP launch of the most recent
  * pnr_render on this thread is NOT kept (no global state); instead the caller brackets calls with
  * hipEvents on `stream`.  These two helpers expose hipEvent timing on an arbitrary hipStream_t to

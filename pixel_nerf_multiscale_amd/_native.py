@@ -159,6 +159,10 @@ PROTOTYPES = {
     "pnr_optim_workspace_bytes": (_u64, [_i64]),
     "pnr_adam_step": (_i32, [_fp, _i32, _fp, _i64, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double,
                              C.c_double, C.POINTER(pnr_optim_scaler), _fp, _fp, _u64, _fp]),
+    "pnr_upsample_concat": (_i32, [C.POINTER(C.c_void_p), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _fp,
+                                   _fp, _i32, _fp]),                       # levels and the size arrays: HOST addresses
+    "pnr_upsample_concat_bwd": (_i32, [_fp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32,
+                                       C.POINTER(C.c_void_p), _fp]),
     "pnr_event_create": (_i32, [C.POINTER(C.c_void_p)]),
     "pnr_event_record": (_i32, [_fp, _fp]),
     "pnr_event_elapsed_ms": (_i32, [_fp, _fp, C.POINTER(C.c_float)]),

@@ -3,6 +3,8 @@ SpatialEncoder: holder of the pixel-aligned latent map(s) the render kernels sam
 torch.nn ResNet trunk (torchvision key names, so upstream checkpoints load) that produces them once per
 object via PyTorch-ROCm/MIOpen.  Reference: src/model/encoder.py.  The per-point lookup `index()` of the
 reference (encoder.py:138-205) happens inside the HIP point kernel; see csrc/pnr_common.h bilinear_taps.
+latent_mode = "upstream" builds upstream pixelNeRF's single concatenated map instead of the fork's latents
+(util.upsample_concat; csrc/upsample.hip).
 """
 import torch
 from torch import nn
@@ -53,8 +55,12 @@ _DEPTHS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
 class SpatialEncoder(nn.Module):
     def __init__(self, backbone="resnet34", pretrained=True, num_layers=4, index_interp="bilinear",
                  index_padding="border", upsample_interp="bilinear", feature_scale=1.0, use_first_pool=True,
-                 norm_type="batch", use_multi_scale=False):
+                 norm_type="batch", use_multi_scale=False, latent_mode="fork"):
         super().__init__()
+        if latent_mode not in ("fork", "upstream"):
+            raise ValueError(f"latent_mode must be 'fork' or 'upstream', got {latent_mode!r}")
+        if latent_mode == "upstream" and use_multi_scale:
+            raise ValueError('latent_mode = "upstream" builds ONE map from every level; it excludes use_multi_scale')
         if backbone not in _DEPTHS:
             raise NotImplementedError(f"Backbone {backbone} not supported")
         if index_interp != "bilinear" or index_padding != "border":
@@ -70,6 +76,14 @@ class SpatialEncoder(nn.Module):
         self.layers = nn.ModuleList([nn.Sequential(*stem)] +
                                     [getattr(self.model, f"layer{i}") for i in range(1, num_layers)])
         self.latent_size = sizes if use_multi_scale else sizes[-1]
+        # "fork" (default, the parity target): the reference fork's latents — the last level alone, or with use_multi_scale
+        # every level sampled at its own size.  "upstream": upstream pixelNeRF's SpatialEncoder.forward — level 0 taken BEFORE
+        # the max-pool, every level resized to level 0's size (bilinear, align_corners=True) and concatenated into ONE map of
+        # sum(sizes) channels (512 for num_layers = 4), built by util.upsample_concat (include/pnr.h, pnr_upsample_concat).
+        # Same modules, same state-dict keys.  Parity against upstream itself is unpinned (see README).
+        self.latent_mode = latent_mode
+        if latent_mode == "upstream":
+            self.latent_size = sum(sizes)
         self.latent = None      # plain attributes, like the reference (encoder.py:106-107)
         self.latents = []
         # N2: None = fp32 NCHW trunk (reference numerics).  torch.float16 / torch.bfloat16 = run the trunk under autocast
@@ -81,9 +95,39 @@ class SpatialEncoder(nn.Module):
         # coordinate, image_size ignored — encoder.py:152-164), the default and the parity target; "image" = upstream
         # pixelNeRF's (texel = uv * latent_size / image_size), for checkpoints trained with upstream semantics.  Honoured by
         # index() and by every render / training kernel (pnr_views.uv_scale_x / _y).  Parity unpinned for "image".
-        self.uv_scale = "latent"
+        # latent_mode = "upstream" means an upstream checkpoint, which was trained with upstream's lookup
+        self.uv_scale = "image" if latent_mode == "upstream" else "latent"
+
+    def level_features(self, x):
+        """Upstream's encoder levels in plain torch (runs on any device): level 0 = relu(bn1(conv1(x))) BEFORE the max-pool,
+        then the pool (if use_first_pool and a further level follows) and layer1.. -> list of num_layers (N, C_i, H_i, W_i)."""
+        m = self.model
+        x = m.relu(m.bn1(m.conv1(x * self.feature_scale)))
+        feats = [x]
+        for i in range(1, self.num_layers):
+            if i == 1 and self.use_first_pool:
+                x = m.maxpool(x)
+            x = getattr(m, f"layer{i}")(x)
+            feats.append(x)
+        return feats
+
+    def _forward_upstream(self, x):
+        from ..util import upsample_concat
+        if self.half_dtype is not None and x.is_cuda:
+            # as in fork mode the trunk runs under autocast; the kernel then leaves the map twice: fp32 NCHW for the fp32 and
+            # training paths, and channels-last 16-bit — the image the render kernels gather from, handed over without a repack
+            with torch.autocast("cuda", dtype=self.half_dtype):
+                feats = self.level_features(x.contiguous(memory_format=torch.channels_last))
+            out, out16 = upsample_concat([f.float() for f in feats], self.half_dtype)
+            self.set_latents([out])
+            self._level_maps16 = [out16.detach()]
+        else:
+            self.set_latents([upsample_concat([f.float() for f in self.level_features(x)])])
+        return self.latent
 
     def forward(self, x):
+        if self.latent_mode == "upstream":
+            return self._forward_upstream(x)
         x = x * self.feature_scale
         feats = []
         if self.half_dtype is not None and x.is_cuda:
@@ -169,7 +213,7 @@ class SpatialEncoder(nn.Module):
                    upsample_interp=conf.get("upsample_interp", "bilinear"),
                    feature_scale=conf.get("feature_scale", 1.0), use_first_pool=conf.get("use_first_pool", True),
                    norm_type=conf.get("norm_type", "batch"), use_multi_scale=conf.get("use_multi_scale", False),
-                   **kwargs)
+                   latent_mode=conf.get("latent_mode", "fork"), **kwargs)
 
 
 ImageEncoder = SpatialEncoder

@@ -310,3 +310,73 @@ def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True,
                                  dp(compare_u8), dp(depth_norm), dp(metrics), dp(ws), nbytes, N.current_stream(dev)),
             "pnr_eval_frame")
     return rgb_u8, compare_u8, depth_norm, metrics
+
+
+def _upsample_sizes(shapes):
+    import ctypes as C
+    arr = lambda k: (C.c_int32 * len(shapes))(*[int(s[k]) for s in shapes])
+    return arr(1), arr(2), arr(3)
+
+
+class _UpsampleConcat(torch.autograd.Function):
+    """pnr_upsample_concat and its adjoint pnr_upsample_concat_bwd.  Saves nothing but the level shapes: the map is linear in
+    the levels and its weights depend on the sizes alone."""
+
+    @staticmethod
+    def forward(ctx, half_dtype, *levels):
+        import ctypes as C
+        from . import _native as N
+        dev = N.same_device(*levels)
+        shapes = [tuple(l.shape) for l in levels]
+        n, (h0, w0) = shapes[0][0], shapes[0][2:]
+        sum_c = sum(s[1] for s in shapes)
+        out = torch.empty(n, sum_c, h0, w0, device=dev, dtype=torch.float32)
+        out16 = None
+        if half_dtype is not None:
+            out16 = torch.empty((n, sum_c, h0, w0), device=dev, dtype=half_dtype, memory_format=torch.channels_last)
+        if n > 0:
+            lat_c, lat_h, lat_w = _upsample_sizes(shapes)
+            ptrs = (C.c_void_p * len(levels))(*[N.ptr(l) for l in levels])
+            dt = N.PNR_F32 if half_dtype is None else (N.PNR_F16 if half_dtype == torch.float16 else N.PNR_BF16)
+            N.check(N.lib.pnr_upsample_concat(ptrs, lat_c, lat_h, lat_w, len(levels), n, N.ptr(out),
+                                              None if out16 is None else out16.data_ptr(), dt, N.current_stream(dev)),
+                    "pnr_upsample_concat")
+        ctx.shapes, ctx.device = shapes, dev
+        if out16 is None:
+            return out
+        ctx.mark_non_differentiable(out16)
+        return out, out16
+
+    @staticmethod
+    def backward(ctx, d_out, *_):
+        import ctypes as C
+        from . import _native as N
+        shapes, dev = ctx.shapes, ctx.device
+        grads = [torch.empty(s, device=dev, dtype=torch.float32) if need else None
+                 for s, need in zip(shapes, ctx.needs_input_grad[1:])]
+        if shapes[0][0] > 0 and any(g is not None for g in grads):
+            lat_c, lat_h, lat_w = _upsample_sizes(shapes)
+            ptrs = (C.c_void_p * len(shapes))(*[None if g is None else g.data_ptr() for g in grads])
+            d_out = N.f32c(d_out)
+            N.check(N.lib.pnr_upsample_concat_bwd(N.ptr(d_out), lat_c, lat_h, lat_w, len(shapes), shapes[0][0], ptrs,
+                                                  N.current_stream(dev)), "pnr_upsample_concat_bwd")
+        return (None, *grads)
+
+
+def upsample_concat(levels, half_dtype=None):
+    """The tail of upstream pixelNeRF's SpatialEncoder.forward on the GPU by libpnr_hip (pnr_upsample_concat): levels, a list
+    of (N, C_i, H_i, W_i) float32 device tensors, each resized to level 0's size (bilinear, align_corners=True) and
+    concatenated along the channels -> out (N, sum C_i, H_0, W_0) float32.  half_dtype = torch.float16 / torch.bfloat16:
+    -> (out, out16), out16 the same values rounded to nearest even, channels-last — the image the 16-bit render kernels
+    gather from (sum C_i % 8 == 0).  Differentiable in the levels; the backward is the deterministic gather kernel
+    (pnr_upsample_concat_bwd) and runs only for the levels that require grad.  include/pnr.h fixes the arithmetic."""
+    from . import _native as N
+    levels = list(levels)
+    if not levels or len(levels) > N.PNR_MAX_LEVELS:
+        raise ValueError(f"upsample_concat takes 1..{N.PNR_MAX_LEVELS} levels, got {len(levels)}")
+    if half_dtype not in (None, torch.float16, torch.bfloat16):
+        raise ValueError(f"half_dtype must be None, torch.float16 or torch.bfloat16, got {half_dtype}")
+    for l in levels:
+        if l.dim() != 4 or l.dtype != torch.float32 or l.shape[0] != levels[0].shape[0]:
+            raise ValueError(f"every level must be float32 (N, C, H, W) with one N, got {l.dtype} {tuple(l.shape)}")
+    return _UpsampleConcat.apply(half_dtype, *[l.contiguous() for l in levels])
