@@ -27,7 +27,8 @@ extern "C" {
                                   * Added since, backward compatible (no bump): the training front end, pnr_train_batch / pnr_rgb_loss / pnr_rgb_loss_bwd;
                                   * the evaluation back end, pnr_eval_frame / pnr_eval_frame_workspace_bytes; mesh extraction,
                                   * pnr_grid_points / pnr_mc_workspace_bytes / pnr_mc_count / pnr_mc_emit; the training back end, pnr_optim_chunk_elems /
-                                  * pnr_optim_plan / pnr_optim_workspace_bytes / pnr_adam_step */
+                                  * pnr_optim_plan / pnr_optim_workspace_bytes / pnr_adam_step; the visualisation panel and the colour map, pnr_cmap_workspace_bytes /
+                                  * pnr_cmap / pnr_vis_panel_workspace_bytes / pnr_vis_panel */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -384,6 +385,74 @@ int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride,       /* rendered (
                        float* depth_norm,                          /* (H, W), or NULL */
                        double* metrics,                            /* 2 doubles, or NULL */
                        void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* ---- visualisation: the colour map of src/util/util.py:13-30 and the panel of train/train.py:423-537 (vis_step), csrc/vis.hip -- */
+/* quantize(map), the reference's image_float_to_uint8 for a float32 map:
+ *   vmin, vmax  the map's fp32 minimum and maximum; a NaN anywhere makes both NaN (np.min)
+ *   widening    if vmax - vmin (one fp32 subtraction) < 1e-10, compared in fp64: vmax = fp32(double(vmax) + 1e-10)
+ *   q           (x - vmin) / (vmax - vmin): one fp32 subtraction, one correctly rounded fp32 division
+ *   byte        trunc(q * 255.0f), ONE fp32 product contracted with nothing; a product that is not finite gives 0 (numpy's cast
+ *               is undefined there; 0 is what it yields where this was developed)
+ * So a constant non-zero map (0 / 0) and a map with a NaN are byte 0 everywhere, the all-zero map too (0 / 1e-10), and the
+ * largest element of any other map is byte 255.
+ * cmap(map, lut) = lut[quantize(map)], lut a (256, 3) uint8 table on the device, owned by the caller.  The package's default
+ * table (util.hot_lut) is PARITY UNPINNED: it restates the "hot" ramp (r = min(1, x / 0.375), g = clamp((x - 0.375) / 0.375),
+ * b = clamp((x - 0.75) / 0.25), x = i / 255 in fp64, byte floor(255 v + 0.5), RGB order); OpenCV's own COLORMAP_HOT table may
+ * differ and comes out as BGR, which the reference shows unswapped.  Whoever has cv2 passes its table.
+ *
+ * pnr_cmap: out_u8 (H, W, 3) = cmap(map); minmax (2 floats, or NULL) = vmin, vmax before the widening.  `stride` in floats per
+ * pixel (0 = 1) lets `map` look into a per-pixel record.  Three launches: per-tile (min, max) into the workspace, one workgroup
+ * that folds them in tile order, the writer.  No atomics, nothing allocated, nothing read back, the same inputs give the same
+ * bits.  Checks, all before any launch:
+ *   PNR_E_NULL       map, out_u8, lut or workspace NULL
+ *   PNR_E_SHAPE      W < 1, H < 1, W * H >= 2^31 or more than 2^23 tiles; stride < 1
+ *   PNR_E_WORKSPACE  fewer bytes than pnr_cmap_workspace_bytes (64 + 8 per 16 x 16 tile; 0 for a bad shape)
+ *   PNR_E_ALIGN      workspace not 4-byte aligned */
+#define PNR_VIS_MAX_SRC 8
+uint64_t pnr_cmap_workspace_bytes(int32_t W, int32_t H);
+int32_t  pnr_cmap(const float* map, int32_t stride /* floats per pixel, 0 = 1 */, int32_t W, int32_t H,
+                  const uint8_t* lut /* device, 256 x 3 */, uint8_t* out_u8 /* (H, W, 3) */,
+                  float* minmax /* 2 floats, or NULL */, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* pnr_vis_panel: the panel of vis_step for ONE target view.  n_pass rows of height H (coarse, then fine if there is one), each
+ * [src_0 .. src_{NS-1}, gt, cmap(depth), rgb, cmap(alpha)] in tiles W wide: (n_pass H, (NS + 4) W, 3).
+ *   image tiles  0.5 * image + 0.5 with the bits of torch's images * 0.5 + 0.5 (as pnr_eval_frame's g)
+ *   alpha[p]     sum_k weights[p, k] (train.py:480,485), accumulated in fp64 in ascending k, rounded once to fp32.  NOT PINNED
+ *                to torch's fp32 .sum(-1), whose order is unspecified: all terms are non-negative, so the two are within
+ *                K * 2^-24 * alpha[p] of each other
+ *   panel_f32    the image tiles as above, the rendered rgb as it is (unclamped), the colour-map bytes as fp32(byte) / 255.0f
+ *                (for all 256 bytes the reference's float64 byte / 255 rounded to fp32)
+ *   panel_u8     trunc(clamp(x, 0, 1) * 255.0f) of the same values; for the colour-map tiles the LUT byte itself
+ *   alpha        (n_pass, H, W), the opacity maps
+ *   stats        n_pass x 6 fp32: rgb min, max, alpha min, max, depth min, max (the reference prints the first four)
+ *   mse          mean over 3 H W elements of (double(x) - double(g))^2, x the LAST pass's unclamped rgb, g the ground-truth tile;
+ *                fp64 sums in a fixed order.  PSNR = -10 log10(mse) (util.psnr)
+ * Strides in floats per pixel (0 = dense: 3, 1, K) let the pass pointers look into the packed per-ray record of
+ * NeRFRenderer.forward_packed.  src_views and passes are HOST arrays, read before the call returns.  Three launches on the
+ * caller's stream: pixel tiles (alpha, per-tile extrema and squared-error sums into the workspace), one workgroup that folds
+ * them in tile order into stats, mse and a record in the workspace, the writer over output tiles (only when a panel is asked
+ * for).  No floating-point atomics, nothing allocated, nothing read back, the same inputs give the same bits.  Checks, all
+ * before any launch:
+ *   PNR_E_NULL       images, src_views, passes or lut NULL; a pass without rgb, depth or weights; an output (mse among them)
+ *                    without a workspace
+ *   PNR_E_SHAPE      W < 1, H < 1, W * H >= 2^31 or more than 2^23 tiles; n_pass not 1 or 2; NS < 1 or NS > PNR_VIS_MAX_SRC;
+ *                    NV < 1; a view index outside [0, NV); K < 1; a stride below the record's own width
+ *   PNR_E_WORKSPACE  fewer bytes than pnr_vis_panel_workspace_bytes (64 + (8 + 24 n_pass) per tile + 4 n_pass W H; 0 for a
+ *                    bad shape)
+ *   PNR_E_ALIGN      workspace not 8-byte aligned
+ * With every output NULL the call returns 0 and launches nothing. */
+typedef struct pnr_vis_pass {      /* one row of the panel: what the renderer left for this pass */
+    const float* rgb; const float* depth; const float* weights;      /* (H*W) x 3, (H*W), (H*W) x K */
+    int32_t rgb_stride, depth_stride, weights_stride;                /* floats per pixel; 0 = dense (3, 1, K) */
+    int32_t K;
+} pnr_vis_pass;
+uint64_t pnr_vis_panel_workspace_bytes(int32_t W, int32_t H, int32_t n_pass);
+int32_t  pnr_vis_panel(const float* images /* device, (NV, 3, H, W) in [-1, 1] */, int32_t NV,
+                       const int32_t* src_views /* HOST, NS entries */, int32_t NS, int32_t gt_view,
+                       const pnr_vis_pass* passes /* HOST */, int32_t n_pass /* 1 or 2 */, int32_t W, int32_t H,
+                       const uint8_t* lut, float* panel_f32, uint8_t* panel_u8 /* either may be NULL */,
+                       float* alpha /* (n_pass, H, W) or NULL */, float* stats /* n_pass x 6 or NULL */,
+                       double* mse /* 1 double or NULL */, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* Mesh extraction (util/recon.py: marching_cubes, with util.gen_grid util.py:98-115 and PyMCubes behind it), csrc/mesh.hip.
  *

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("PNR_LIB") or os.path.join(HERE, "lib", "libpnr_hip.so
 
 PNR_MAX_LEVELS = 5
 PNR_MAX_BLOCKS = 8
+PNR_VIS_MAX_SRC = 8
 PNR_F32, PNR_BF16, PNR_F16 = 0, 1, 2
 PNR_BF16X3 = 3     # training entry points only
 PRECISIONS = {"fp32": PNR_F32, "f32": PNR_F32, "bf16": PNR_BF16, "fp16": PNR_F16, "f16": PNR_F16, "bf16x3": PNR_BF16X3}
@@ -74,6 +75,11 @@ class pnr_outputs(C.Structure):
                 ("fine_depth", _fp), ("fine_weights", _fp), ("z_coarse", _fp), ("z_fine", _fp),
                 ("ev_point_begin", _fp), ("ev_point_end", _fp), ("rgb_stride", C.c_int32), ("depth_stride", C.c_int32),
                 ("coarse_weights_stride", C.c_int32), ("fine_weights_stride", C.c_int32)]
+
+
+class pnr_vis_pass(C.Structure):
+    _fields_ = [("rgb", _fp), ("depth", _fp), ("weights", _fp), ("rgb_stride", C.c_int32), ("depth_stride", C.c_int32),
+                ("weights_stride", C.c_int32), ("K", C.c_int32)]
 
 
 class pnr_debug_linear_args(C.Structure):
@@ -149,6 +155,11 @@ PROTOTYPES = {
     "pnr_rgb_loss_bwd": (_i32, [_fp, _fp, _fp, _i64, _i32, _f, _f, _fp, _fp, _fp, _fp]),
     "pnr_eval_frame_workspace_bytes": (_u64, [_i32, _i32]),
     "pnr_eval_frame": (_i32, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _f, _f, _fp, _fp, _fp, _fp, _fp, _u64, _fp]),
+    "pnr_cmap_workspace_bytes": (_u64, [_i32, _i32]),
+    "pnr_cmap": (_i32, [_fp, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _u64, _fp]),
+    "pnr_vis_panel_workspace_bytes": (_u64, [_i32, _i32, _i32]),
+    "pnr_vis_panel": (_i32, [_fp, _i32, C.POINTER(_i32), _i32, _i32, C.POINTER(pnr_vis_pass), _i32, _i32, _i32, _fp, _fp, _fp,
+                             _fp, _fp, _fp, _fp, _u64, _fp]),         # src_views and passes: HOST addresses
     "pnr_grid_points": (_i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _i64, _i64, _i32, _fp, _fp, _fp]),
     "pnr_mc_workspace_bytes": (_u64, [_i32, _i32, _i32]),
     "pnr_mc_count": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, _fp, _u64, _fp, _fp]),

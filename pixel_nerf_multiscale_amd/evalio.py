@@ -142,7 +142,7 @@ def write_png(path, rgb_u8):
 def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None, eval_view_list=None,
              include_src=False, scale=1.0, multicat=False, gpu_id=None, ray_batch_size=50000, no_compare_gt=False,
              write_compare=False, write_images=True, max_objects=50, z_near=None, z_far=None,
-             verbose=True, seed=None, metrics="host", write_depth=False):
+             verbose=True, seed=None, metrics="host", write_depth=False, depth_png=False, lut=None):
     """The per-object evaluation loop of the reference (eval/eval.py:186-362) on this package's renderer.
 
     dataset: a sequence of per-object dicts as the reference's datasets yield them (unbatched): "path", "images"
@@ -166,11 +166,14 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
     Deliberate differences: the rays of all target views are not concatenated and re-split (:250-267) — a view is the unit;
     the random jitter is keyed by (seed, ray): one base seed per call (`seed`, else drawn from torch's generator on rank 0
     and broadcast) and a seed derived per (object, view), so neither the chunk size, nor the number of ranks, nor a resume changes a pixel; SSIM is this module's restatement
-    (skimage is not importable here: parity unpinned); depth EXR / colour-mapped depth outputs (:303-316) are not written
-    (they need cv2, which this package does not depend on).
+    (skimage is not importable here: parity unpinned); the depth EXR (:304-306, :312) is not written (it needs cv2, which
+    this package does not depend on).
 
     write_depth=True writes "<obj>/<view:06>_depth.npy" instead: float32 (H, W), (depth - z_near) / (z_far - z_near)
-    (:288-289), with either back end.
+    (:288-289), with either back end.  With depth_png=True as well it also writes the reference's colour-mapped
+    "<obj>/<view:06>_depth_norm.png" (:307-313) = cmap(normalised depth): util.cmap on the host with metrics="host",
+    util.cmap_device (pnr_cmap) where the frame lies with metrics="device".  lut: the (256, 3) uint8 colour table, None =
+    util.hot_lut() (parity unpinned against cv2.COLORMAP_HOT, see there).  Without depth_png the written files are unchanged.
 
     metrics="host" (the default) is the reference's recipe: every frame is copied to the host as fp32 and numpy / scipy do
     the rest.  metrics="device": util.eval_frame (pnr_eval_frame) runs on each frame where the render left it — the object's
@@ -325,13 +328,16 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
                     u8_h = pinned("u8", (n_gen, H, W, 3), torch.uint8) if want_u8 else None
                     cmp_h = pinned("cmp", (n_gen, H, 2 * W, 3), torch.uint8) if want_cmp else None
                     dn_h = pinned("dn", (n_gen, H, W), torch.float32) if want_dn else None
+                    want_dpng = want_dn and depth_png
+                    dpng_h = pinned("dpng", (n_gen, H, W, 3), torch.uint8) if want_dpng else None
                     for i, vi in enumerate(views):
                         rgb, depth = render_view(vi)
                         u8, cmp, dn, _ = util.eval_frame(rgb, depth if want_dn else None, gt_dev[i] if compare else None,
                                                          z_near=z_near, z_far=z_far, want_u8=want_u8, want_compare=want_cmp,
                                                          want_depth=want_dn, want_metrics=compare,
                                                          metrics_out=pairs[i] if compare else None)
-                        for dst, src_t in ((u8_h, u8), (cmp_h, cmp), (dn_h, dn)):
+                        dpng = util.cmap_device(dn, lut)[0] if want_dpng else None
+                        for dst, src_t in ((u8_h, u8), (cmp_h, cmp), (dn_h, dn), (dpng_h, dpng)):
                             if dst is not None:
                                 dst[i].copy_(src_t, non_blocking=True)
                     pairs_h = None
@@ -350,6 +356,8 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
                             write_png(os.path.join(obj_out, "{:06}.png".format(vi)), u8_h[i].numpy())
                         if want_dn:
                             np.save(os.path.join(obj_out, "{:06}_depth.npy".format(vi)), dn_h[i].numpy())
+                        if want_dpng:
+                            write_png(os.path.join(obj_out, "{:06}_depth_norm.png".format(vi)), dpng_h[i].numpy())
                         if compare:
                             mse, s = (float(x) for x in pairs_h[i])
                             curr_ssim += s
@@ -384,6 +392,9 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
                         all_depth = ((torch.stack(depths) - z_near) / (z_far - z_near)).numpy()       # eval.py:288-289
                         for i in range(n_gen):
                             np.save(os.path.join(obj_out, "{:06}_depth.npy".format(int(novel[i]))), all_depth[i])
+                            if depth_png:
+                                write_png(os.path.join(obj_out, "{:06}_depth_norm.png".format(int(novel[i]))),
+                                          util.cmap(all_depth[i], lut))
                     curr_psnr = curr_ssim = 0.0
                     if not no_compare_gt and n_gen:
                         gt = (images * 0.5 + 0.5)[tgt_mask].permute(0, 2, 3, 1).contiguous().numpy()

@@ -123,3 +123,124 @@ def train_step(net, render_par, data, optim, *, grad_hook=None, **calc_losses_kw
     optim.step()
     loss_dict["grad_norm"] = optim.grad_norm
     return loss_dict
+
+
+def eval_step(net, renderer, render_par, data, **calc_losses_kw):
+    """Trainer.eval_step of the reference (train/train.py:414-421): calc_losses(..., is_train=False) under torch.no_grad()
+    with the renderer in eval mode -> the loss_dict ("rc", "rf" with a fine pass, "t"), the part Trainer.validate consumes,
+    its values still on the device; {} for a batch without images.  The reference ends with an unconditional
+    renderer.train(); this RESTORES the mode the renderer was in instead.  Nothing in here waits for the device."""
+    calc_losses_kw.pop("is_train", None)
+    was_training = renderer.training
+    renderer.eval()
+    try:
+        with torch.no_grad():
+            out = calc_losses(net, render_par, data, is_train=False, **calc_losses_kw)
+    finally:
+        renderer.train(was_training)
+    return out[1] if out else {}
+
+
+def validate(net, renderer, render_par, loader, **calc_losses_kw):
+    """Trainer.validate of the reference (train/trainlib/trainer.py:404-460): the mean of loss_dict["t"] over the loader's
+    batches with the net in eval mode, skipping None batches (a failed collate) and batches without "images"; float("inf")
+    when no batch counts.  The reference reads three values per batch back; here "t" is accumulated where eval_step left it
+    (on the device) and the mean is read ONCE at the end.  The net's mode is restored, where the reference calls net.train().
+    Its progress bar, its TensorBoard scalar and its skipping of batches that raise RuntimeError are the caller's."""
+    was_training = net.training
+    net.eval()
+    total, count = None, 0
+    try:
+        for data in loader:
+            if data is None or not data or "images" not in data:
+                continue
+            loss_dict = eval_step(net, renderer, render_par, data, **calc_losses_kw)
+            if "t" not in loss_dict:
+                continue
+            t = torch.as_tensor(loss_dict["t"]).detach().double()
+            total = t if total is None else total + t
+            count += 1
+    finally:
+        net.train(was_training)
+    if count == 0:
+        return float("inf")
+    return float(total) / count
+
+
+def draw_vis_views(NV, nviews):
+    """The view draws of vis_step in the reference's order (train/train.py:446-450): curr_nviews from torch's global CPU
+    generator, the sorted source views and the target view from numpy's; the target is drawn among the NV - curr_nviews views
+    that are left and pushed past the sources.  -> (views_src sorted int64 array, view_dest).  ValueError for more sources
+    than a panel holds or for no view left over."""
+    from ._native import PNR_VIS_MAX_SRC
+    curr_nviews = int(nviews[torch.randint(0, len(nviews), (1,)).item()])
+    if curr_nviews > PNR_VIS_MAX_SRC:
+        raise ValueError(f"vis_step draws at most {PNR_VIS_MAX_SRC} source views, got nviews entry {curr_nviews}")
+    if curr_nviews >= NV:
+        raise ValueError(f"vis_step needs a target view besides the {curr_nviews} source views, the object has {NV}")
+    views_src = np.sort(np.random.choice(NV, curr_nviews, replace=False))
+    view_dest = int(np.random.randint(0, NV - curr_nviews))
+    for vs in range(curr_nviews):
+        view_dest += int(view_dest >= views_src[vs])
+    return views_src, view_dest
+
+
+def vis_step(net, renderer, render_par, data, *, nviews, z_near, z_far, idx=None, lut=None, out="float", verbose=False):
+    """Trainer.vis_step of the reference (train/train.py:423-537): one object of the batch, curr_nviews of its views as
+    sources, one other view rendered, and the picture a run is judged by — per pass [source views | ground truth | depth map
+    | rendered colours | opacity map], coarse row over fine row — plus the view's PSNR.
+
+    The reference generates rays for all NV views to use one, copies seven arrays to the host and colour-maps, stacks and
+    measures there.  Here only the target view's rays are made (util.gen_rays_device), the render runs under torch.no_grad()
+    with the renderer in eval mode, and ONE util.vis_panel call (pnr_vis_panel) builds panel and PSNR on the device.
+
+    data       the loader's dict (host tensors): images (SB, NV, 3, H, W) in [-1, 1], poses, focal, optional c
+    nviews     the source-view counts to draw from; idx: the object, else drawn
+    lut        (256, 3) uint8 colour table; None = util.hot_lut() (parity unpinned, see there)
+    out        "float": the float32 panel (n_pass H, (NS + 4) W, 3); "uint8": the same as bytes
+    -> (vis, {"psnr": 0-dim float64 device tensor}); {} for a batch without images.
+
+    Draws in the reference's order: batch_idx from np.random.randint unless idx is given, then draw_vis_views.  Parity for
+    that order is unpinned, as calc_losses says for its own draws.  The renderer's mode is RESTORED afterwards (the reference
+    calls renderer.train()).  verbose=True prints the reference's min / max lines and the PSNR, at the cost of one host read;
+    with verbose=False the call waits for the device only if data["poses"] is a device tensor (the camera is read on the host)."""
+    if "images" not in data:
+        return {}
+    if out not in ("float", "uint8"):
+        raise ValueError(f"out must be 'float' or 'uint8', got {out!r}")
+    batch_idx = int(np.random.randint(0, data["images"].shape[0])) if idx is None else int(idx)
+    dev = net.poses.device
+    NV, _, H, W = data["images"][batch_idx].shape
+    views_src, view_dest = draw_vis_views(NV, nviews)
+    images = util.upload(data["images"][batch_idx].float().contiguous(), dev)        # (NV, 3, H, W)
+    poses = data["poses"][batch_idx].float()
+    focal = torch.as_tensor(data["focal"], dtype=torch.float32)[batch_idx:batch_idx + 1]
+    c = data.get("c")
+    if c is not None:
+        c = torch.as_tensor(c, dtype=torch.float32)[batch_idx:batch_idx + 1]
+    src_idx = torch.from_numpy(views_src)
+    rays = util.gen_rays_device(poses[view_dest], W, H, focal[0], z_near, z_far, c=None if c is None else c[0], device=dev)
+    src_images = images.index_select(0, util.upload(src_idx, dev))                    # (NS, 3, H, W)
+    was_training = renderer.training
+    renderer.eval()
+    try:
+        with torch.no_grad():
+            net.encode(src_images.unsqueeze(0), util.upload(poses[src_idx].contiguous(), dev).unsqueeze(0),
+                       util.upload(focal, dev), c=None if c is None else util.upload(c, dev))
+            render_dict = render_par(rays[None], want_weights=True)
+            passes = [render_dict["coarse"]]
+            fine = render_dict.get("fine")
+            if fine is not None and len(fine) > 0:
+                passes.append(fine)
+            res = util.vis_panel(images, views_src, view_dest,
+                                 [(p["rgb"][0], p["depth"][0], p["weights"][0]) for p in passes],
+                                 lut=lut, want_f32=out == "float", want_u8=out == "uint8")
+    finally:
+        renderer.train(was_training)
+    if verbose:
+        stats = res.stats.cpu().tolist()
+        for tag, s in zip("cf", stats):
+            print("{} rgb min {} max {}".format(tag, s[0], s[1]))
+            print("{} alpha min {}, max {}".format(tag, s[2], s[3]))
+        print("psnr", float(res.psnr))
+    return (res.panel if out == "float" else res.panel_u8), {"psnr": res.psnr}

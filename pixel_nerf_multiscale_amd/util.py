@@ -380,3 +380,153 @@ def upsample_concat(levels, half_dtype=None):
         if l.dim() != 4 or l.dtype != torch.float32 or l.shape[0] != levels[0].shape[0]:
             raise ValueError(f"every level must be float32 (N, C, H, W) with one N, got {l.dtype} {tuple(l.shape)}")
     return _UpsampleConcat.apply(half_dtype, *[l.contiguous() for l in levels])
+
+
+# ------------------------------------------------------------------------------------------- colour map and the vis_step panel
+def hot_lut():
+    """The package's default colour table, (256, 3) uint8 in RGB order: the "hot" ramp black - red - yellow - white,
+    r = min(1, x / 0.375), g = clamp((x - 0.375) / 0.375, 0, 1), b = clamp((x - 0.75) / 0.25, 0, 1) for x = i / 255 in fp64,
+    each byte floor(255 v + 0.5).  PARITY UNPINNED: the reference indexes cv2.COLORMAP_HOT (src/util/util.py:26-30), cv2 is
+    not importable where this package is developed, OpenCV's own table may differ from this ramp, and OpenCV returns BGR, which
+    the reference shows unswapped.  With cv2 at hand pass
+    lut=cv2.applyColorMap(np.arange(256, dtype=np.uint8), cv2.COLORMAP_HOT)[:, 0] to cmap / cmap_device / vis_panel."""
+    x = np.arange(256, dtype=np.float64) / 255.0
+    r = np.minimum(1.0, x / 0.375)
+    g = np.clip((x - 0.375) / 0.375, 0.0, 1.0)
+    b = np.clip((x - 0.75) / 0.25, 0.0, 1.0)
+    return np.floor(255.0 * np.stack((r, g, b), axis=-1) + 0.5).astype(np.uint8)
+
+
+def image_float_to_uint8(img):
+    """The reference's image_float_to_uint8 (src/util/util.py:13-23) for a float32 map, as include/pnr.h states it: whole-frame
+    fp32 min / max (a NaN anywhere makes both NaN), vmax widened by 1e-10 when the range is below 1e-10, (x - vmin) /
+    (vmax - vmin) in fp32, ONE fp32 product with 255, truncation; a product that is not finite gives byte 0."""
+    img = np.asarray(img, dtype=np.float32)
+    vmin, vmax = np.float32(np.min(img)), np.float32(np.max(img))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        if float(vmax - vmin) < 1e-10:
+            vmax = np.float32(float(vmax) + 1e-10)
+        p = ((img - vmin) / np.float32(vmax - vmin)) * np.float32(255.0)
+    out = np.zeros(img.shape, np.uint8)
+    ok = np.isfinite(p)
+    out[ok] = p[ok].astype(np.int32).astype(np.uint8)
+    return out
+
+
+def cmap(img, lut=None):
+    """The reference's util.cmap (src/util/util.py:26-30) on the host in pure numpy, with the colour table as data:
+    lut[image_float_to_uint8(img)] -> (H, W, 3) uint8.  lut (256, 3) uint8; None = hot_lut() (parity unpinned, see there)."""
+    lut = hot_lut() if lut is None else np.asarray(lut)
+    if lut.shape != (256, 3) or lut.dtype != np.uint8:
+        raise ValueError(f"lut must be uint8 (256, 3), got {lut.dtype} {lut.shape}")
+    return lut[image_float_to_uint8(img)]
+
+
+_LUT_CACHE = {}
+
+
+def _device_lut(lut, dev):
+    """(256, 3) uint8 table on `dev`: a device tensor passes through; the default table is uploaded once per device."""
+    if lut is None:
+        key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+        t = _LUT_CACHE.get(key)
+        if t is None:
+            t = _LUT_CACHE[key] = upload(torch.from_numpy(hot_lut()), dev)
+        return t
+    if not torch.is_tensor(lut):
+        lut = torch.from_numpy(np.ascontiguousarray(lut))
+    if tuple(lut.shape) != (256, 3) or lut.dtype != torch.uint8:
+        raise ValueError(f"lut must be uint8 (256, 3), got {lut.dtype} {tuple(lut.shape)}")
+    return upload(lut, dev).contiguous()
+
+
+def cmap_device(map, lut=None):
+    """util.cmap on the GPU by libpnr_hip (pnr_cmap): map (H, W) float32, dense or a view into a per-pixel record ->
+    (u8 (H, W, 3) uint8 = lut[image_float_to_uint8(map)], minmax (2,) float32 = the map's min and max), both on the device.
+    lut: (256, 3) uint8, numpy or tensor; None = hot_lut(), uploaded once per device (parity unpinned, see hot_lut).  Nothing
+    here waits for the device."""
+    from . import _native as N
+    if not torch.is_tensor(map) or map.dim() != 2:
+        raise ValueError(f"map must be a float32 (H, W) tensor, got {tuple(getattr(map, 'shape', ()))}")
+    H, W = int(map.shape[0]), int(map.shape[1])
+    stride = _pixel_stride(map, H, W, 0, "map")
+    dev = N.same_device(map)
+    lut = _device_lut(lut, dev)
+    N.same_device(map, lut)
+    u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    minmax = torch.empty(2, dtype=torch.float32, device=dev)
+    nbytes = int(N.lib.pnr_cmap_workspace_bytes(W, H))
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dev)
+    N.check(N.lib.pnr_cmap(map.data_ptr(), stride, W, H, lut.data_ptr(), u8.data_ptr(), minmax.data_ptr(), ws.data_ptr(),
+                           nbytes, N.current_stream(dev)), "pnr_cmap")
+    return u8, minmax
+
+
+class VisPanel:
+    """What vis_panel leaves on the device: panel (n_pass H, (NS + 4) W, 3) float32, panel_u8 the same as uint8, alpha
+    (n_pass, H, W), stats (n_pass, 6) = rgb min max, alpha min max, depth min max, mse and psnr = -10 log10(mse) as 0-dim
+    float64 tensors.  None for what was not asked for."""
+    __slots__ = ("panel", "panel_u8", "alpha", "stats", "mse", "psnr")
+
+    def __init__(self, panel, panel_u8, alpha, stats, mse, psnr):
+        self.panel, self.panel_u8, self.alpha, self.stats, self.mse, self.psnr = panel, panel_u8, alpha, stats, mse, psnr
+
+
+def _ray_stride(t, n, last, name):
+    """Floats per ray of a per-ray output that is dense or a column range of a packed per-ray record: (n, last) with strides
+    (s, 1), or (n,) with stride s."""
+    want = (n, last) if last else (n,)
+    if tuple(t.shape) != want or t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32 {want}, got {t.dtype} {tuple(t.shape)}")
+    if t.is_contiguous():
+        return max(last, 1)
+    st = t.stride()
+    if st[0] < max(last, 1) or (last and last > 1 and st[1] != 1):
+        raise ValueError(f"{name} must be dense or a view into a per-ray record, got strides {st}")
+    return st[0]
+
+
+def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, want_u8=False, want_alpha=False):
+    """The picture of the reference's vis_step (train/train.py:497-526) for one target view, on the GPU by libpnr_hip
+    (pnr_vis_panel): per pass one row [source views | ground truth | cmap(depth) | rgb | cmap(alpha)], coarse over fine.
+    images (NV, 3, H, W) float32 in [-1, 1] on the device; src_views 1..8 view indices and gt_view, on the host; passes a list
+    of one or two (rgb (H W, 3), depth (H W), weights (H W, K)), float32, dense or views into a packed per-ray record.
+    -> VisPanel; everything stays on the device and nothing waits.  lut as in cmap_device.  include/pnr.h fixes the arithmetic
+    (alpha is an fp64 sum in ascending k, not torch's .sum(-1); the default table is parity unpinned)."""
+    import ctypes as C
+    from . import _native as N
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"images must be float32 (NV, 3, H, W), got {images.dtype} {tuple(images.shape)}")
+    NV, _, H, W = (int(s) for s in images.shape)
+    src = [int(v) for v in (src_views.tolist() if hasattr(src_views, "tolist") else src_views)]
+    NS, n_pass = len(src), len(passes)
+    if not 1 <= NS <= N.PNR_VIS_MAX_SRC:
+        raise ValueError(f"vis_panel takes 1..{N.PNR_VIS_MAX_SRC} source views, got {NS}")
+    if n_pass not in (1, 2):
+        raise ValueError(f"vis_panel takes one or two passes, got {n_pass}")
+    images = images.contiguous()
+    dev = N.same_device(images, *[t for ps in passes for t in ps])
+    lut = _device_lut(lut, dev)
+    N.same_device(images, lut)
+    arr = (N.pnr_vis_pass * n_pass)()
+    for i, (rgb, depth, weights) in enumerate(passes):
+        if weights.dim() != 2:
+            raise ValueError(f"weights must be (H*W, K), got {tuple(weights.shape)}")
+        K = int(weights.shape[1])
+        arr[i].rgb, arr[i].depth, arr[i].weights = rgb.data_ptr(), depth.data_ptr(), weights.data_ptr()
+        arr[i].rgb_stride = _ray_stride(rgb, H * W, 3, "rgb")
+        arr[i].depth_stride = _ray_stride(depth, H * W, 0, "depth")
+        arr[i].weights_stride = _ray_stride(weights, H * W, K, "weights")
+        arr[i].K = K
+    panel = torch.empty(n_pass * H, (NS + 4) * W, 3, dtype=torch.float32, device=dev) if want_f32 else None
+    panel_u8 = torch.empty(n_pass * H, (NS + 4) * W, 3, dtype=torch.uint8, device=dev) if want_u8 else None
+    alpha = torch.empty(n_pass, H, W, dtype=torch.float32, device=dev) if want_alpha else None
+    stats = torch.empty(n_pass, 6, dtype=torch.float32, device=dev)
+    mse = torch.empty((), dtype=torch.float64, device=dev)
+    nbytes = int(N.lib.pnr_vis_panel_workspace_bytes(W, H, n_pass))
+    ws = torch.empty(max(nbytes, 16) // 8 + 1, dtype=torch.float64, device=dev)
+    dp = lambda t: None if t is None else t.data_ptr()
+    N.check(N.lib.pnr_vis_panel(images.data_ptr(), NV, (C.c_int32 * NS)(*src), NS, int(gt_view), arr, n_pass, W, H,
+                                lut.data_ptr(), dp(panel), dp(panel_u8), dp(alpha), stats.data_ptr(), mse.data_ptr(),
+                                ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_vis_panel")
+    return VisPanel(panel, panel_u8, alpha, stats, mse, -10.0 * torch.log10(mse))
