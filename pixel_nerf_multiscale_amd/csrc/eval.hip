@@ -3,14 +3,12 @@
 // normalised depth (:288-289), and the two numbers finish.txt is made of — the mean squared error behind PSNR and the mean
 // SSIM (:324-332, as evalio.ssim restates skimage: uniform 7x7 window, sample covariance, whole windows only, per channel).
 // Latency-bound: a 128 x 128 frame is 64 workgroups; the point is that nothing waits on the host.
-#include "pnr_common.h"
+#include "frame_common.h"
 
 namespace pnr {
 
-constexpr int EV_TILE = 16;                        // pixels per tile edge; one thread per pixel
 constexpr int EV_HALO = 3;                         // (7 - 1) / 2
-constexpr int EV_LDS = EV_TILE + 2 * EV_HALO;      // 22
-constexpr int EV_THREADS = EV_TILE * EV_TILE;      // 256 = 4 waves
+constexpr int EV_LDS = FRAME_TILE + 2 * EV_HALO;   // 22
 constexpr int EV_WIN = 2 * EV_HALO + 1;            // 7
 
 struct EvalArgs {
@@ -21,21 +19,11 @@ struct EvalArgs {
     double* part;                                  // (tiles, 2): squared-error sum, SSIM sum of the tile; NULL = no metrics
 };
 
-// clamp to [0, 1] that keeps a NaN (fminf / fmaxf would turn it into a bound: the host path's metrics are NaN then)
-__device__ __forceinline__ float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
-// (x * 255).astype(uint8) of a clamped value: ONE fp32 product, then truncation ((k / 255) * 255 may land just below k); NaN -> 0
-__device__ __forceinline__ uint8_t quant_u8(float x) { return x == x ? (uint8_t)(int)__fmul_rn(x, 255.0f) : (uint8_t)0; }
-
-// Sum of (a, b) over the workgroup, the same bits in every thread.  Order fixed by the launch shape alone: thread t adds
-// t + 128, then t + 64, .., t + 1.
-__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[EV_THREADS], int tid) {
+// Sum of (a, b) over the workgroup (block_fold), the same bits in every thread.
+__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[FRAME_THREADS], int tid) {
     red[0][tid] = a;
     red[1][tid] = b;
-    __syncthreads();
-    for (int s = EV_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
-        __syncthreads();
-    }
+    block_fold<FRAME_THREADS>(tid, [red](int i, int j) { red[0][i] += red[0][j]; red[1][i] += red[1][j]; });
     a = red[0][0];
     b = red[1][0];
 }
@@ -45,16 +33,16 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[E
 // the pixel is the centre of a whole window — its SSIM term from the 49 taps around it.  The window arithmetic is fp64: mean
 // first, then CENTRED second moments (sum (x - mx)(y - my)), so a white background with variances around 1e-7 keeps them; the
 // MI355X runs fp64 FMAs at half the fp32 rate, and 2 x 49 taps x 3 channels per pixel are nothing next to the render.
-__global__ void __launch_bounds__(EV_THREADS) k_eval_frame(EvalArgs a) {
+__global__ void __launch_bounds__(FRAME_THREADS) k_eval_frame(EvalArgs a) {
     __shared__ float sx[3][EV_LDS][EV_LDS];
     __shared__ float sg[3][EV_LDS][EV_LDS];
-    __shared__ double red[2][EV_THREADS];
-    const int tid = threadIdx.x, tx = tid & (EV_TILE - 1), ty = tid / EV_TILE;
-    const int x0 = ((int)blockIdx.x % a.tiles_x) * EV_TILE, y0 = ((int)blockIdx.x / a.tiles_x) * EV_TILE;
+    __shared__ double red[2][FRAME_THREADS];
+    const int tid = threadIdx.x, tx = tid & (FRAME_TILE - 1), ty = tid / FRAME_TILE;
+    const auto [x0, y0] = tile_origin((int)blockIdx.x, a.tiles_x);
     const int W = a.W, H = a.H;
     const int64_t HW = (int64_t)W * H;
 
-    for (int i = tid; i < EV_LDS * EV_LDS; i += EV_THREADS) {
+    for (int i = tid; i < EV_LDS * EV_LDS; i += FRAME_THREADS) {
         const int ly = i / EV_LDS, lx = i % EV_LDS;
         const int gy = y0 - EV_HALO + ly, gx = x0 - EV_HALO + lx;
         float v[3] = {0.0f, 0.0f, 0.0f}, g[3] = {0.0f, 0.0f, 0.0f};       // outside the image: never part of a whole window
@@ -127,12 +115,12 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_frame(EvalArgs a) {
 
 // ONE workgroup: thread t adds the tiles t, t + 256, .. in ascending order, then block_sum2 — no atomics, the same inputs give
 // the same bits.  metrics[0] = mean squared error over 3 H W elements, metrics[1] = mean SSIM over 3 (H - 6)(W - 6) windows.
-__global__ void __launch_bounds__(EV_THREADS) k_eval_finish(const double* __restrict__ part, int tiles, int W, int H,
-                                                            double* __restrict__ metrics) {
-    __shared__ double red[2][EV_THREADS];
+__global__ void __launch_bounds__(FRAME_THREADS) k_eval_finish(const double* __restrict__ part, int tiles, int W, int H,
+                                                               double* __restrict__ metrics) {
+    __shared__ double red[2][FRAME_THREADS];
     const int tid = threadIdx.x;
     double se = 0.0, ss = 0.0;
-    for (int t = tid; t < tiles; t += EV_THREADS) { se += part[2 * (int64_t)t]; ss += part[2 * (int64_t)t + 1]; }
+    for (int t = tid; t < tiles; t += FRAME_THREADS) { se += part[2 * (int64_t)t]; ss += part[2 * (int64_t)t + 1]; }
     block_sum2(se, ss, red, tid);
     if (tid == 0) {
         metrics[0] = se / (3.0 * (double)W * (double)H);
@@ -140,18 +128,13 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_finish(const double* __rest
     }
 }
 
-static inline int64_t eval_tiles(int32_t W, int32_t H) {
-    return (int64_t)((W + EV_TILE - 1) / EV_TILE) * ((H + EV_TILE - 1) / EV_TILE);
-}
-constexpr int64_t EV_MAX_TILES = (int64_t)1 << 23;        // 2^23 workgroups of 256 threads: a launch stays below 2^32 threads
-
 }  // namespace pnr
 
 using namespace pnr;
 
 extern "C" uint64_t pnr_eval_frame_workspace_bytes(int32_t W, int32_t H) {
-    if (W < 1 || H < 1 || (int64_t)W * H >= ((int64_t)1 << 31)) return 0;
-    return (uint64_t)eval_tiles(W, H) * 2 * sizeof(double);
+    if (!frame_pixels_ok(W, H)) return 0;                  // not the tile limit: pnr_eval_frame refuses such a frame itself
+    return (uint64_t)frame_tiles(W, H) * 2 * sizeof(double);
 }
 
 extern "C" int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride, const float* depth, int32_t depth_stride, const float* gt,
@@ -161,26 +144,26 @@ extern "C" int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride, const fl
     if ((compare_u8 || metrics) && !gt) return PNR_E_NULL;
     if (depth_norm && !depth) return PNR_E_NULL;
     if (metrics && !workspace) return PNR_E_NULL;
-    if (W < 1 || H < 1 || (int64_t)W * H >= ((int64_t)1 << 31)) return PNR_E_SHAPE;
+    if (!frame_pixels_ok(W, H)) return PNR_E_SHAPE;
     if (rgb_stride == 0) rgb_stride = 3;
     if (depth_stride == 0) depth_stride = 1;
     if (rgb_stride < 3 || depth_stride < 1) return PNR_E_SHAPE;
     if (metrics && (W < EV_WIN || H < EV_WIN)) return PNR_E_SHAPE;
     if (depth_norm && z_far == z_near) return PNR_E_SHAPE;
-    const int64_t tiles = eval_tiles(W, H);
-    if (tiles > EV_MAX_TILES) return PNR_E_SHAPE;
+    const int64_t tiles = frame_tiles(W, H);
+    if (tiles > FRAME_MAX_TILES) return PNR_E_SHAPE;
     if (metrics && workspace_bytes < pnr_eval_frame_workspace_bytes(W, H)) return PNR_E_WORKSPACE;
     if (!rgb_u8 && !compare_u8 && !depth_norm && !metrics) return PNR_OK;
     EvalArgs a;
     a.rgb = rgb; a.depth = depth; a.gt = gt;
-    a.rgb_stride = rgb_stride; a.depth_stride = depth_stride; a.W = W; a.H = H; a.tiles_x = (W + EV_TILE - 1) / EV_TILE;
+    a.rgb_stride = rgb_stride; a.depth_stride = depth_stride; a.W = W; a.H = H; a.tiles_x = frame_tiles_x(W);
     a.z_near = z_near; a.z_range = z_far - z_near;
     a.rgb_u8 = rgb_u8; a.compare_u8 = compare_u8; a.depth_norm = depth_norm;
     a.part = metrics ? (double*)workspace : nullptr;
-    hipLaunchKernelGGL(k_eval_frame, dim3((unsigned)tiles), dim3(EV_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_eval_frame, dim3((unsigned)tiles), dim3(FRAME_THREADS), 0, (hipStream_t)stream, a);
     PNR_LAUNCH_CHECK();
     if (metrics) {
-        hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(EV_THREADS), 0, (hipStream_t)stream, (const double*)workspace, (int)tiles, W,
+        hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)workspace, (int)tiles, W,
                            H, metrics);
         PNR_LAUNCH_CHECK();
     }

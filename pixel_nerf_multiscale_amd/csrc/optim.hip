@@ -9,7 +9,7 @@
 // table alone, so the same inputs give the same bits.
 #include <math.h>
 
-#include "pnr_common.h"
+#include "frame_common.h"
 
 // include/pnr.h fixes the arithmetic as separately rounded fp32 operations (what torch's kernels round, in another order):
 // hipcc's default -ffp-contract=fast would fuse the products into the sums.  As in mesh.hip, nothing in this file is fused.
@@ -43,15 +43,11 @@ __device__ __forceinline__ ChunkView chunk_view(const pnr_optim_segment* __restr
 
 __device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.402823466e+38f; }      // false for Inf and NaN
 
-// Sum of `a` over the workgroup in thread 0 and OR of `bad`; thread t adds t + 128, then t + 64, .., t + 1.
+// Sum of `a` over the workgroup and OR of `bad` (block_fold).
 __device__ __forceinline__ void block_sum_or(double& a, int& bad, double* red, int* redb, int tid) {
     red[tid] = a;
     redb[tid] = bad;
-    __syncthreads();
-    for (int s = OPT_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) { red[tid] += red[tid + s]; redb[tid] |= redb[tid + s]; }
-        __syncthreads();
-    }
+    block_fold<OPT_THREADS>(tid, [red, redb](int i, int j) { red[i] += red[j]; redb[i] |= redb[j]; });
     a = red[0];
     bad = redb[0];
     __syncthreads();                                      // the next chunk of a grid-strided workgroup reuses red

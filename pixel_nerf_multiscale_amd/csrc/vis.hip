@@ -4,22 +4,15 @@
 // A whole-frame minimum has to exist before any byte can, so each entry point is three launches on the caller's stream:
 // per-tile partials, ONE workgroup that folds them in tile order, the writer.  include/pnr.h fixes the arithmetic.
 // Latency-bound: a 128 x 128 view is 64 workgroups; the point is that nothing is copied to the host and nothing waits.
-#include "pnr_common.h"
+#include "frame_common.h"
 
 namespace pnr {
 
-constexpr int VS_TILE = 16;                        // pixels per tile edge; one thread per pixel
-constexpr int VS_THREADS = VS_TILE * VS_TILE;      // 256 = 4 waves
-constexpr int64_t VS_MAX_TILES = (int64_t)1 << 23; // 2^23 workgroups of 256 threads: a launch stays below 2^32 threads
 constexpr uint64_t VS_RECORD_BYTES = 64;           // the fold's record at the head of the workspace (up to 8 floats)
 
 // min / max as np.min / np.max: a NaN on either side is the answer
 __device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
 __device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-
-__device__ __forceinline__ float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
-// trunc(x * 255.0f) of a clamped value: ONE fp32 product; NaN -> 0 (csrc/eval.hip)
-__device__ __forceinline__ uint8_t quant_u8(float x) { return x == x ? (uint8_t)(int)__fmul_rn(x, 255.0f) : (uint8_t)0; }
 
 // image_float_to_uint8 for one element: (x - vmin) / (vmax - vmin), one product with 255, truncation; not finite -> 0
 __device__ __forceinline__ uint8_t quant_map(float x, float vmin, float den) {
@@ -32,41 +25,27 @@ __device__ __forceinline__ float widen_vmax(float vmin, float vmax) {
 }
 
 // (min, max) over the workgroup into red[0][0], red[1][0]; the caller syncs before it reuses `red`
-__device__ __forceinline__ void block_minmax(float lo, float hi, float (*red)[VS_THREADS], int tid) {
+__device__ __forceinline__ void block_minmax(float lo, float hi, float (*red)[FRAME_THREADS], int tid) {
     red[0][tid] = lo;
     red[1][tid] = hi;
-    __syncthreads();
-    for (int s = VS_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) { red[0][tid] = nan_min(red[0][tid], red[0][tid + s]); red[1][tid] = nan_max(red[1][tid], red[1][tid + s]); }
-        __syncthreads();
-    }
+    block_fold<FRAME_THREADS>(tid, [red](int i, int j) {
+        red[0][i] = nan_min(red[0][i], red[0][j]); red[1][i] = nan_max(red[1][i], red[1][j]);
+    });
 }
-// sum over the workgroup, order fixed by the launch shape alone: thread t adds t + 128, then t + 64, .., t + 1
+// sum over the workgroup (block_fold); the caller syncs before it reuses `red`
 __device__ __forceinline__ double block_sum(double a, double* red, int tid) {
     red[tid] = a;
-    __syncthreads();
-    for (int s = VS_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
+    block_fold<FRAME_THREADS>(tid, [red](int i, int j) { red[i] += red[j]; });
     return red[0];
-}
-
-static inline int64_t vis_tiles(int32_t W, int32_t H) {
-    return (int64_t)((W + VS_TILE - 1) / VS_TILE) * ((H + VS_TILE - 1) / VS_TILE);
-}
-static inline bool vis_shape_ok(int32_t W, int32_t H) {
-    return W >= 1 && H >= 1 && (int64_t)W * H < ((int64_t)1 << 31) && vis_tiles(W, H) <= VS_MAX_TILES;
 }
 
 // ------------------------------------------------------------------------------------------------------------ pnr_cmap
 // per tile: (min, max) of the map -> part[2 tile], part[2 tile + 1]
-__global__ void __launch_bounds__(VS_THREADS) k_cmap_reduce(const float* __restrict__ map, int stride, int W, int H, int tiles_x,
-                                                            float* __restrict__ part) {
-    __shared__ float red[2][VS_THREADS];
+__global__ void __launch_bounds__(FRAME_THREADS) k_cmap_reduce(const float* __restrict__ map, int stride, int W, int H, int tiles_x,
+                                                               float* __restrict__ part) {
+    __shared__ float red[2][FRAME_THREADS];
     const int tid = threadIdx.x;
-    const int gx = ((int)blockIdx.x % tiles_x) * VS_TILE + (tid & (VS_TILE - 1));
-    const int gy = ((int)blockIdx.x / tiles_x) * VS_TILE + tid / VS_TILE;
+    const auto [gx, gy] = tile_pixel((int)blockIdx.x, tiles_x, tid);
     float lo = INFINITY, hi = -INFINITY;
     if (gx < W && gy < H) lo = hi = map[((int64_t)gy * W + gx) * stride];
     block_minmax(lo, hi, red, tid);
@@ -74,12 +53,12 @@ __global__ void __launch_bounds__(VS_THREADS) k_cmap_reduce(const float* __restr
 }
 
 // ONE workgroup: thread t folds the tiles t, t + 256, .. in ascending order.  record = (vmin, widened vmax)
-__global__ void __launch_bounds__(VS_THREADS) k_cmap_fold(const float* __restrict__ part, int tiles, float* __restrict__ record,
-                                                          float* __restrict__ minmax) {
-    __shared__ float red[2][VS_THREADS];
+__global__ void __launch_bounds__(FRAME_THREADS) k_cmap_fold(const float* __restrict__ part, int tiles, float* __restrict__ record,
+                                                             float* __restrict__ minmax) {
+    __shared__ float red[2][FRAME_THREADS];
     const int tid = threadIdx.x;
     float lo = INFINITY, hi = -INFINITY;
-    for (int t = tid; t < tiles; t += VS_THREADS) { lo = nan_min(lo, part[2 * (int64_t)t]); hi = nan_max(hi, part[2 * (int64_t)t + 1]); }
+    for (int t = tid; t < tiles; t += FRAME_THREADS) { lo = nan_min(lo, part[2 * (int64_t)t]); hi = nan_max(hi, part[2 * (int64_t)t + 1]); }
     block_minmax(lo, hi, red, tid);
     if (tid == 0) {
         lo = red[0][0];
@@ -90,12 +69,11 @@ __global__ void __launch_bounds__(VS_THREADS) k_cmap_fold(const float* __restric
     }
 }
 
-__global__ void __launch_bounds__(VS_THREADS) k_cmap_write(const float* __restrict__ map, int stride, int W, int H, int tiles_x,
-                                                           const uint8_t* __restrict__ lut, const float* __restrict__ record,
-                                                           uint8_t* __restrict__ out) {
+__global__ void __launch_bounds__(FRAME_THREADS) k_cmap_write(const float* __restrict__ map, int stride, int W, int H, int tiles_x,
+                                                              const uint8_t* __restrict__ lut, const float* __restrict__ record,
+                                                              uint8_t* __restrict__ out) {
     const int tid = threadIdx.x;
-    const int gx = ((int)blockIdx.x % tiles_x) * VS_TILE + (tid & (VS_TILE - 1));
-    const int gy = ((int)blockIdx.x / tiles_x) * VS_TILE + tid / VS_TILE;
+    const auto [gx, gy] = tile_pixel((int)blockIdx.x, tiles_x, tid);
     if (gx >= W || gy >= H) return;
     const float vmin = record[0], den = __fsub_rn(record[1], vmin);
     const int64_t pix = (int64_t)gy * W + gx;
@@ -124,12 +102,11 @@ struct VisArgs {
 
 // Launch one, a workgroup per 16 x 16 pixel tile: the opacity of every pass (fp64 sum in ascending k, one rounding), the tile's
 // partial extrema and, from the last pass's colours against the ground-truth tile, its squared-error sum.
-__global__ void __launch_bounds__(VS_THREADS) k_vis_reduce(VisArgs a) {
-    __shared__ float red[2][VS_THREADS];
-    __shared__ double dred[VS_THREADS];
+__global__ void __launch_bounds__(FRAME_THREADS) k_vis_reduce(VisArgs a) {
+    __shared__ float red[2][FRAME_THREADS];
+    __shared__ double dred[FRAME_THREADS];
     const int tid = threadIdx.x;
-    const int gx = ((int)blockIdx.x % a.tiles_x) * VS_TILE + (tid & (VS_TILE - 1));
-    const int gy = ((int)blockIdx.x / a.tiles_x) * VS_TILE + tid / VS_TILE;
+    const auto [gx, gy] = tile_pixel((int)blockIdx.x, a.tiles_x, tid);
     const bool inside = gx < a.W && gy < a.H;
     const int64_t HW = (int64_t)a.W * a.H, pix = (int64_t)gy * a.W + gx;
 
@@ -175,9 +152,9 @@ __global__ void __launch_bounds__(VS_THREADS) k_vis_reduce(VisArgs a) {
 
 // Launch two, ONE workgroup: thread t folds the tiles t, t + 256, .. in ascending order, then the tree — no atomics, the same
 // inputs give the same bits.
-__global__ void __launch_bounds__(VS_THREADS) k_vis_fold(VisArgs a) {
-    __shared__ float red[2][VS_THREADS];
-    __shared__ double dred[VS_THREADS];
+__global__ void __launch_bounds__(FRAME_THREADS) k_vis_fold(VisArgs a) {
+    __shared__ float red[2][FRAME_THREADS];
+    __shared__ double dred[FRAME_THREADS];
     const int tid = threadIdx.x;
     for (int p = 0; p < a.n_pass; ++p) {
         const float* part = a.mm_part + (int64_t)p * a.tiles * 6;
@@ -185,7 +162,7 @@ __global__ void __launch_bounds__(VS_THREADS) k_vis_fold(VisArgs a) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             float lo = INFINITY, hi = -INFINITY;
-            for (int t = tid; t < a.tiles; t += VS_THREADS) {
+            for (int t = tid; t < a.tiles; t += FRAME_THREADS) {
                 lo = nan_min(lo, part[(int64_t)t * 6 + 2 * q]);
                 hi = nan_max(hi, part[(int64_t)t * 6 + 2 * q + 1]);
             }
@@ -207,16 +184,15 @@ __global__ void __launch_bounds__(VS_THREADS) k_vis_fold(VisArgs a) {
     }
     if (!a.mse) return;
     double se = 0.0;
-    for (int t = tid; t < a.tiles; t += VS_THREADS) se += a.se_part[t];
+    for (int t = tid; t < a.tiles; t += FRAME_THREADS) se += a.se_part[t];
     se = block_sum(se, dred, tid);
     if (tid == 0) *a.mse = se / (3.0 * (double)a.W * (double)a.H);
 }
 
 // Launch three, a workgroup per (pixel tile, panel column, pass): every thread writes the three channels of one panel pixel.
-__global__ void __launch_bounds__(VS_THREADS) k_vis_write(VisArgs a) {
+__global__ void __launch_bounds__(FRAME_THREADS) k_vis_write(VisArgs a) {
     const int tid = threadIdx.x;
-    const int gx = ((int)blockIdx.x % a.tiles_x) * VS_TILE + (tid & (VS_TILE - 1));
-    const int gy = ((int)blockIdx.x / a.tiles_x) * VS_TILE + tid / VS_TILE;
+    const auto [gx, gy] = tile_pixel((int)blockIdx.x, a.tiles_x, tid);
     if (gx >= a.W || gy >= a.H) return;
     const int col = blockIdx.y, p = blockIdx.z, NS = a.NS;
     const int64_t HW = (int64_t)a.W * a.H, pix = (int64_t)gy * a.W + gx;
@@ -250,27 +226,27 @@ __global__ void __launch_bounds__(VS_THREADS) k_vis_write(VisArgs a) {
 using namespace pnr;
 
 extern "C" uint64_t pnr_cmap_workspace_bytes(int32_t W, int32_t H) {
-    if (!vis_shape_ok(W, H)) return 0;
-    return VS_RECORD_BYTES + (uint64_t)vis_tiles(W, H) * 2 * sizeof(float);
+    if (!frame_shape_ok(W, H)) return 0;
+    return VS_RECORD_BYTES + (uint64_t)frame_tiles(W, H) * 2 * sizeof(float);
 }
 
 extern "C" int32_t pnr_cmap(const float* map, int32_t stride, int32_t W, int32_t H, const uint8_t* lut, uint8_t* out_u8,
                             float* minmax, void* workspace, uint64_t workspace_bytes, void* stream) {
     if (!map || !out_u8 || !lut || !workspace) return PNR_E_NULL;
     if (((uintptr_t)workspace & 3) != 0) return PNR_E_ALIGN;
-    if (!vis_shape_ok(W, H)) return PNR_E_SHAPE;
+    if (!frame_shape_ok(W, H)) return PNR_E_SHAPE;
     if (stride == 0) stride = 1;
     if (stride < 1) return PNR_E_SHAPE;
     if (workspace_bytes < pnr_cmap_workspace_bytes(W, H)) return PNR_E_WORKSPACE;
-    const int tiles = (int)vis_tiles(W, H), tiles_x = (W + VS_TILE - 1) / VS_TILE;
+    const int tiles = (int)frame_tiles(W, H), tiles_x = frame_tiles_x(W);
     float* record = (float*)workspace;
     float* part = (float*)((char*)workspace + VS_RECORD_BYTES);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_cmap_reduce, dim3((unsigned)tiles), dim3(VS_THREADS), 0, s, map, stride, W, H, tiles_x, part);
+    hipLaunchKernelGGL(k_cmap_reduce, dim3((unsigned)tiles), dim3(FRAME_THREADS), 0, s, map, stride, W, H, tiles_x, part);
     PNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_cmap_fold, dim3(1), dim3(VS_THREADS), 0, s, (const float*)part, tiles, record, minmax);
+    hipLaunchKernelGGL(k_cmap_fold, dim3(1), dim3(FRAME_THREADS), 0, s, (const float*)part, tiles, record, minmax);
     PNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_cmap_write, dim3((unsigned)tiles), dim3(VS_THREADS), 0, s, map, stride, W, H, tiles_x, lut,
+    hipLaunchKernelGGL(k_cmap_write, dim3((unsigned)tiles), dim3(FRAME_THREADS), 0, s, map, stride, W, H, tiles_x, lut,
                        (const float*)record, out_u8);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
@@ -278,8 +254,8 @@ extern "C" int32_t pnr_cmap(const float* map, int32_t stride, int32_t W, int32_t
 
 // workspace: record (64 bytes) | squared-error partials (tiles doubles) | extrema partials (n_pass, tiles, 6) | alpha (n_pass, H W)
 extern "C" uint64_t pnr_vis_panel_workspace_bytes(int32_t W, int32_t H, int32_t n_pass) {
-    if (!vis_shape_ok(W, H) || n_pass < 1 || n_pass > 2) return 0;
-    const uint64_t tiles = (uint64_t)vis_tiles(W, H);
+    if (!frame_shape_ok(W, H) || n_pass < 1 || n_pass > 2) return 0;
+    const uint64_t tiles = (uint64_t)frame_tiles(W, H);
     return VS_RECORD_BYTES + tiles * sizeof(double) + (uint64_t)n_pass * tiles * 6 * sizeof(float) +
            (uint64_t)n_pass * (uint64_t)W * (uint64_t)H * sizeof(float);
 }
@@ -295,7 +271,7 @@ extern "C" int32_t pnr_vis_panel(const float* images, int32_t NV, const int32_t*
     const bool any = panel_f32 || panel_u8 || alpha || stats || mse;
     if (any && !workspace) return PNR_E_NULL;
     if (((uintptr_t)workspace & 7) != 0) return PNR_E_ALIGN;
-    if (!vis_shape_ok(W, H)) return PNR_E_SHAPE;
+    if (!frame_shape_ok(W, H)) return PNR_E_SHAPE;
     if (NS < 1 || NS > PNR_VIS_MAX_SRC || NV < 1 || gt_view < 0 || gt_view >= NV) return PNR_E_SHAPE;
     for (int i = 0; i < NS; ++i)
         if (src_views[i] < 0 || src_views[i] >= NV) return PNR_E_SHAPE;
@@ -313,11 +289,11 @@ extern "C" int32_t pnr_vis_panel(const float* images, int32_t NV, const int32_t*
     if (n_pass == 1) a.pass[1] = a.pass[0];
     if (!any) return PNR_OK;
     if (workspace_bytes < pnr_vis_panel_workspace_bytes(W, H, n_pass)) return PNR_E_WORKSPACE;
-    const int64_t tiles = vis_tiles(W, H);
+    const int64_t tiles = frame_tiles(W, H);
     a.images = images;
     for (int i = 0; i < PNR_VIS_MAX_SRC; ++i) a.src[i] = i < NS ? src_views[i] : 0;
     a.NS = NS; a.gt_view = gt_view; a.n_pass = n_pass; a.W = W; a.H = H;
-    a.tiles_x = (W + VS_TILE - 1) / VS_TILE; a.tiles = (int)tiles;
+    a.tiles_x = frame_tiles_x(W); a.tiles = (int)tiles;
     a.lut = lut; a.panel_f32 = panel_f32; a.panel_u8 = panel_u8; a.alpha_out = alpha; a.stats = stats; a.mse = mse;
     char* ws = (char*)workspace;
     a.record = (float*)ws;
@@ -325,12 +301,12 @@ extern "C" int32_t pnr_vis_panel(const float* images, int32_t NV, const int32_t*
     a.mm_part = (float*)(ws + VS_RECORD_BYTES + (uint64_t)tiles * sizeof(double));
     a.alpha_ws = a.mm_part + (int64_t)n_pass * tiles * 6;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_vis_reduce, dim3((unsigned)tiles), dim3(VS_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_vis_reduce, dim3((unsigned)tiles), dim3(FRAME_THREADS), 0, s, a);
     PNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_vis_fold, dim3(1), dim3(VS_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_vis_fold, dim3(1), dim3(FRAME_THREADS), 0, s, a);
     PNR_LAUNCH_CHECK();
     if (panel_f32 || panel_u8) {
-        hipLaunchKernelGGL(k_vis_write, dim3((unsigned)tiles, (unsigned)(NS + 4), (unsigned)n_pass), dim3(VS_THREADS), 0, s, a);
+        hipLaunchKernelGGL(k_vis_write, dim3((unsigned)tiles, (unsigned)(NS + 4), (unsigned)n_pass), dim3(FRAME_THREADS), 0, s, a);
         PNR_LAUNCH_CHECK();
     }
     return PNR_OK;

@@ -14,10 +14,17 @@ per-frame work (clamp, quantisation, PSNR / SSIM sums, normalised depth) to the 
 * evaluate()                  reference eval/eval.py:186-362           the per-object loop that composes the above with
                               encode -> render -> clamp -> metrics -> finish.txt (resume), on this package's renderer
 """
+import math
 import os
+import warnings
+from types import SimpleNamespace
 
 import numpy as np
 import torch
+import torch.distributed as dist
+
+from . import util
+from .parallel import frame_seed
 
 
 class FinishLog:
@@ -139,6 +146,232 @@ def write_png(path, rgb_u8):
                 + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+# ------------------------------------------------------------------------------------------------- the parts of evaluate()
+def _open_log(output_dir, sharded, rank):
+    """The FinishLog of an evaluation; without an output directory one that has no file and holds the running sums alone
+    (path None).  Under a process group every rank runs the loop
+    (each call's rays are cut over the ranks and every rank gets the whole frame back), but the output directory has ONE
+    writer: rank 0 owns finish.txt and the PNGs; the other ranks start from rank 0's view of the file — broadcast once, so
+    all ranks skip the same objects whatever the file system shows them — and keep their running means in memory."""
+    if not (output_dir and str(output_dir).strip()):
+        return FinishLog(None, state=((), 0.0, 0.0, 0))
+    path = os.path.join(output_dir, "finish.txt")
+    log = FinishLog(path) if rank == 0 else None
+    if sharded:
+        box = [log.state() if rank == 0 else None]
+        dist.broadcast_object_list(box, src=0)
+        if rank != 0:
+            log = FinishLog(path, state=box[0])
+    return log
+
+
+def _base_seed(seed, sharded):
+    """One base seed per call: `seed`, else drawn from torch's generator on every rank; rank 0's draw is the one kept."""
+    if seed is not None:
+        return int(seed)
+    box = [util.seed_from_torch()]
+    if sharded:
+        dist.broadcast_object_list(box, src=0)
+    return int(box[0])
+
+
+def target_views(NV, src, eval_view_list, include_src):
+    """-> (src_mask (NV,) bool, tgt_mask (NV,) bool, novel = the target view indices, ascending): the targets are
+    eval_view_list (None = every view) minus the source views `src` unless include_src (eval.py:170-178, :246-248)."""
+    src_mask = torch.zeros(NV, dtype=torch.bool)
+    src_mask[src] = True
+    tgt_mask = torch.ones(NV, dtype=torch.bool)
+    if eval_view_list is not None:
+        tgt_mask = torch.zeros(NV, dtype=torch.bool)
+        tgt_mask[torch.as_tensor(eval_view_list, dtype=torch.long)] = True
+    if not include_src:
+        tgt_mask = tgt_mask & ~src_mask
+    return src_mask, tgt_mask, tgt_mask.nonzero(as_tuple=False).reshape(-1)
+
+
+def _render_size(images, scale):
+    H, W = images.shape[-2:]
+    if scale == 1.0:
+        return H, W
+    Ht, Wt = int(H * scale), int(W * scale)
+    if abs(Ht / scale - H) > 1e-10 or abs(Wt / scale - W) > 1e-10:
+        warnings.warn(f"Inexact scaling, please check {scale} times ({H}, {W}) is integral")
+    return Ht, Wt
+
+
+def _encode_object(net, data, src_mask, dev, sharded):
+    """net.encode on the object's source views (eval.py:271-276) -> its (poses, focal, c) as float tensors on the host."""
+    focal = data["focal"]
+    focal = torch.tensor(focal, dtype=torch.float32) if isinstance(focal, float) else torch.as_tensor(focal).float()
+    c = data.get("c")
+    c = None if c is None else torch.as_tensor(c).float()
+    poses = torch.as_tensor(data["poses"]).float()
+    net.encode(data["images"][src_mask].to(dev).unsqueeze(0), poses[src_mask].to(dev).unsqueeze(0), focal[None].to(dev),
+               c=None if c is None else c.to(dev).unsqueeze(0))
+    if sharded:
+        # every rank ran the trunk on the same images, but a convolution library may pick different algorithms in
+        # different processes (last-bit differences): rank 0's maps are THE maps, so that the gathered frame is one
+        # consistent render (64 KB ... 6 MB per object, once — SURVEY 8e)
+        maps = [m.detach().clone() for m in net.encoder.level_maps()]
+        for m in maps:
+            if dist.get_backend() == "nccl":
+                dist.broadcast(m, src=0)
+            else:
+                h = m.cpu()
+                dist.broadcast(h, src=0)
+                m.copy_(h)
+        net.encoder.set_latents(maps)
+    return poses, focal, c
+
+
+def _sharded_renderer(net, renderer):
+    # built directly: bind_parallel() only shards when the caller lists several gpu ids (eval.py:151 passes args.gpu_id),
+    # and a rank of a one-process-per-GPU job has exactly one
+    from .render.nerf import _ShardedRenderWrapper
+    return _ShardedRenderWrapper(net, renderer, simple_output=True).eval()
+
+
+def _render_view(net, renderer, render_par, view_seed, pose, W, H, focal, c, z_near, z_far, ray_batch_size):
+    """-> (rgb (H, W, 3), depth (H, W)) of one view on the device: ONE renderer.render_image call (looked up here, per call:
+    a caller may have wrapped it on the instance), or chunks of ray_batch_size through the sharded wrapper render_par."""
+    if render_par is None:
+        keep_seed, renderer.forced_seed = renderer.forced_seed, view_seed
+        try:
+            return renderer.render_image(net, pose, W, H, focal, z_near, z_far, c=c)
+        finally:
+            renderer.forced_seed = keep_seed
+    rays = util.gen_rays_device(pose, W, H, focal, z_near, z_far, c=c, device=net.poses.device)
+    parts, at = [], 0
+    for r in torch.split(rays, ray_batch_size, dim=0):
+        parts.append(render_par(r[None], ray_index_base=at, seed=view_seed))
+        at += r.shape[0]
+    return (torch.cat([p[0][0] for p in parts], 0).reshape(H, W, 3),
+            torch.cat([p[1][0] for p in parts], 0).reshape(H, W))
+
+
+class _BackEnd:
+    """What becomes of an object's rendered frames: begin(obj_out, images, tgt_mask, views, H, W) per object — obj_out the
+    object's directory, None on a rank that writes nothing —, frame(i, vi, rgb, depth) for the i-th target view vi as the
+    render left it on the device, finish() -> the object's (psnr, ssim), after it has waited and written the object's files.
+    o: what evaluate() was asked for (z_near, z_far, compare_gt, write_images, write_compare, write_depth, depth_png, lut)."""
+
+    def check_size(self, H, W, images):
+        pass
+
+    def _write(self, vi, u8=None, depth_norm=None, depth_png=None, compare=None):
+        """The files of view vi from host arrays, None = not written; the object's directory is made with its first file."""
+        files = ((".png", u8), ("_depth.npy", depth_norm), ("_depth_norm.png", depth_png), ("_compare.png", compare))
+        for suffix, a in files:
+            if a is not None:
+                os.makedirs(self.obj_out, exist_ok=True)
+                (np.save if suffix.endswith(".npy") else write_png)(os.path.join(self.obj_out, "{:06}{}".format(vi, suffix)), a)
+
+
+class _HostBackEnd(_BackEnd):
+    """metrics="host", the reference's recipe: every frame goes to the host as fp32 — to_host(rgb, depth) -> (rgb_host,
+    depth_host, event), the renderer's frame_to_host_async — and numpy / scipy do the rest."""
+
+    def __init__(self, o, to_host):
+        self.o, self.to_host = o, to_host
+
+    def begin(self, obj_out, images, tgt_mask, views, H, W):
+        self.obj_out, self.images, self.tgt_mask, self.views, self.shape = obj_out, images, tgt_mask, views, (H, W)
+        self.copies = []                                            # (rgb_host, depth_host, event) per view
+
+    def frame(self, i, vi, rgb, depth):
+        self.copies.append(self.to_host(rgb, depth))                # D2H overlaps the next view's render:
+        if i > 0:
+            self.copies[i - 1][2].synchronize()                     # the host waits for the view before, not for this one
+
+    def finish(self):
+        o, views, n_gen, writes = self.o, self.views, len(self.copies), self.obj_out is not None
+        all_rgb = np.zeros((0, *self.shape, 3), np.float32)
+        if n_gen:
+            self.copies[-1][2].synchronize()
+            all_rgb = torch.clamp(torch.stack([c[0] for c in self.copies]), 0.0, 1.0).numpy()
+        if writes and o.write_images:
+            os.makedirs(self.obj_out, exist_ok=True)                # as the reference: also for an object without target views
+            for i in range(n_gen):
+                self._write(views[i], u8=quantize_uint8(all_rgb[i]))
+        if writes and o.write_depth and n_gen:
+            all_depth = ((torch.stack([c[1] for c in self.copies]) - o.z_near) / (o.z_far - o.z_near)).numpy()      # eval.py:288-289
+            for i in range(n_gen):
+                self._write(views[i], depth_norm=all_depth[i], depth_png=util.cmap(all_depth[i], o.lut) if o.depth_png else None)
+        if not (o.compare_gt and n_gen):
+            return 0.0, 0.0
+        curr_psnr = curr_ssim = 0.0
+        gt = (self.images * 0.5 + 0.5)[self.tgt_mask].permute(0, 2, 3, 1).contiguous().numpy()
+        for i in range(n_gen):
+            curr_ssim += ssim(all_rgb[i], gt[i], data_range=1)
+            curr_psnr += psnr(all_rgb[i], gt[i], data_range=1)
+            if writes and o.write_compare:
+                self._write(views[i], compare=quantize_uint8(np.hstack((all_rgb[i], gt[i]))))
+        return curr_psnr / n_gen, curr_ssim / n_gen
+
+
+class _DeviceBackEnd(_BackEnd):
+    """metrics="device": util.eval_frame on each frame where the render left it; the object's ground truth is uploaded once,
+    the (mse, ssim) pairs collect in one device buffer, what will be written travels to pinned host buffers asynchronously
+    and finish() holds the one wait of the object.  The pinned buffers are kept for the next object of the same shape."""
+
+    def __init__(self, o, dev):
+        self.o, self.dev, self.pin = o, dev, {}
+
+    def check_size(self, H, W, images):
+        if self.o.compare_gt and (H, W) != tuple(images.shape[-2:]):
+            raise ValueError(f"metrics='device' compares a {H} x {W} render with {tuple(images.shape[-2:])} ground truth: "
+                             "use scale=1 or no_compare_gt")
+
+    def _pinned(self, name, wanted, shape, dtype):
+        if not wanted:
+            return None
+        t = self.pin.get(name)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self.pin[name] = torch.empty(shape, dtype=dtype, pin_memory=True)
+        return t
+
+    def begin(self, obj_out, images, tgt_mask, views, H, W):
+        o, n_gen, writes = self.o, len(views), obj_out is not None
+        self.obj_out, self.views = obj_out, views
+        self.compare = compare = o.compare_gt and n_gen > 0
+        self.gt_dev = util.upload(images[tgt_mask].float().contiguous(), self.dev) if compare else None
+        self.pairs = torch.empty(n_gen, 2, dtype=torch.float64, device=self.dev) if compare else None
+        want_dn = writes and o.write_depth
+        self.u8_h = self._pinned("u8", writes and o.write_images, (n_gen, H, W, 3), torch.uint8)
+        self.cmp_h = self._pinned("cmp", writes and o.write_compare and compare, (n_gen, H, 2 * W, 3), torch.uint8)
+        self.dn_h = self._pinned("dn", want_dn, (n_gen, H, W), torch.float32)
+        self.dpng_h = self._pinned("dpng", want_dn and o.depth_png, (n_gen, H, W, 3), torch.uint8)
+
+    def frame(self, i, vi, rgb, depth):
+        o, compare, want_dn = self.o, self.compare, self.dn_h is not None
+        u8, cmp, dn, _ = util.eval_frame(rgb, depth if want_dn else None, self.gt_dev[i] if compare else None,
+                                         z_near=o.z_near, z_far=o.z_far, want_u8=self.u8_h is not None,
+                                         want_compare=self.cmp_h is not None, want_depth=want_dn, want_metrics=compare,
+                                         metrics_out=self.pairs[i] if compare else None)
+        dpng = util.cmap_device(dn, o.lut)[0] if self.dpng_h is not None else None
+        for dst, src_t in ((self.u8_h, u8), (self.cmp_h, cmp), (self.dn_h, dn), (self.dpng_h, dpng)):
+            if dst is not None:
+                dst[i].copy_(src_t, non_blocking=True)
+
+    def finish(self):
+        views, compare, n_gen = self.views, self.compare, len(self.views)
+        if compare:
+            pairs_h = self._pinned("pairs", True, (n_gen, 2), torch.float64)
+            pairs_h.copy_(self.pairs, non_blocking=True)
+        if n_gen:
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(self.dev))
+            done.synchronize()                                  # the one wait of this object
+        curr_psnr = curr_ssim = 0.0
+        for i, vi in enumerate(views):
+            self._write(vi, *(None if h is None else h[i].numpy() for h in (self.u8_h, self.dn_h, self.dpng_h, self.cmp_h)))
+            if compare:
+                mse, s = (float(x) for x in pairs_h[i])
+                curr_ssim += s
+                curr_psnr += float("inf") if mse == 0.0 else 10.0 * math.log10(1.0 / mse) if mse > 0.0 else float("nan")
+        return (curr_psnr / n_gen, curr_ssim / n_gen) if compare else (0.0, 0.0)
+
+
 def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None, eval_view_list=None,
              include_src=False, scale=1.0, multicat=False, gpu_id=None, ray_batch_size=50000, no_compare_gt=False,
              write_compare=False, write_images=True, max_objects=50, z_near=None, z_far=None,
@@ -183,61 +416,29 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
     finish.txt line.  PSNR is 10 log10(1 / mse) on the host in fp64.  Under a process group every rank computes the metrics
     (the return value is the same everywhere) and rank 0 alone copies bytes out and writes.  A ground truth whose size differs
     from the render's (scale != 1 with comparison) is a ValueError: there is no resampling on the device."""
-    import math
-    import torch.distributed as dist
-    from . import util
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
     dev = net.poses.device
     z_near = float(getattr(dataset, "z_near", None) if z_near is None else z_near)
     z_far = float(getattr(dataset, "z_far", None) if z_far is None else z_far)
-    has_output = bool(output_dir and str(output_dir).strip())
     sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank = dist.get_rank() if sharded else 0
-    # Under a process group every rank runs this loop (each call's rays are cut over the ranks and every rank gets the whole
-    # frame back), but the output directory has ONE writer: rank 0 owns finish.txt and the PNGs; the other ranks start from
-    # rank 0's view of the file — broadcast once, so all ranks skip the same objects whatever the file system shows them —
-    # and keep their running means in memory.  The return value is the same on every rank.
-    log = None
-    if has_output:
-        if rank == 0:
-            log = FinishLog(os.path.join(output_dir, "finish.txt"))
-        if sharded:
-            box = [log.state() if rank == 0 else None]
-            dist.broadcast_object_list(box, src=0)
-            if rank != 0:
-                log = FinishLog(os.path.join(output_dir, "finish.txt"), state=box[0])
-    writes_files = has_output and rank == 0
-    from .parallel import frame_seed
-    base_seed = int(seed) if seed is not None else util.seed_from_torch()
-    if sharded and seed is None:
-        box = [base_seed]
-        dist.broadcast_object_list(box, src=0)
-        base_seed = int(box[0])
-    total_psnr, total_ssim, cnt = (log.total_psnr, log.total_ssim, log.cnt) if log else (0.0, 0.0, 0)
-    if log and log.cnt > 0 and verbose:
-        print("resume psnr", log.total_psnr / log.cnt, "ssim", log.total_ssim / log.cnt)
+    log = _open_log(output_dir, sharded, rank)
+    resumes = log.path is not None
+    writes_files = resumes and rank == 0
+    base_seed = _base_seed(seed, sharded)
+    if log.cnt > 0 and verbose:
+        print("resume psnr", log.mean()[0], "ssim", log.mean()[1])
 
     if isinstance(viewlist, str) and viewlist:
         viewlist = read_source_view_lut(viewlist)
-    use_lut = bool(viewlist)
-    fixed_source = None if use_lut else torch.tensor(sorted(int(x) for x in str(source).split()), dtype=torch.long)
+    fixed_source = None if viewlist else torch.tensor(sorted(int(x) for x in str(source).split()), dtype=torch.long)
     if isinstance(eval_view_list, str):
         eval_view_list = read_eval_view_list(eval_view_list)
-    render_par = None
-    if sharded:
-        # built directly: bind_parallel() only shards when the caller lists several gpu ids (eval.py:151 passes args.gpu_id),
-        # and a rank of a one-process-per-GPU job has exactly one
-        from .render.nerf import _ShardedRenderWrapper
-        render_par = _ShardedRenderWrapper(net, renderer, simple_output=True).eval()
-    pin = {}
-
-    def pinned(name, shape, dtype):
-        # metrics="device": the pinned host buffers of an object's outputs, kept for the next object of the same shape
-        t = pin.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = pin[name] = torch.empty(shape, dtype=dtype, pin_memory=True)
-        return t
+    render_par = _sharded_renderer(net, renderer) if sharded else None
+    o = SimpleNamespace(z_near=z_near, z_far=z_far, compare_gt=not no_compare_gt, write_images=write_images,
+                        write_compare=write_compare, write_depth=write_depth, depth_png=depth_png, lut=lut)
+    back = _DeviceBackEnd(o, dev) if metrics == "device" else _HostBackEnd(o, renderer.frame_to_host_async)
     was_training = net.training
     net.eval()
     try:
@@ -251,174 +452,34 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
                 obj_name = cat_name + "_" + obj_base if multicat else obj_base
                 if verbose:
                     print("OBJECT", obj_idx, "OF", len(dataset), dpath)
-                if log and obj_name in log.finished:
+                if resumes and obj_name in log.finished:
                     if verbose:
                         print("(skip)")
                     continue
                 images = data["images"]                                       # (NV, 3, H, W)
-                NV, _, H, W = images.shape
-                if scale != 1.0:
-                    Ht, Wt = int(H * scale), int(W * scale)
-                    if abs(Ht / scale - H) > 1e-10 or abs(Wt / scale - W) > 1e-10:
-                        import warnings
-                        warnings.warn(f"Inexact scaling, please check {scale} times ({H}, {W}) is integral")
-                    H, W = Ht, Wt
-                if metrics == "device" and not no_compare_gt and (H, W) != tuple(images.shape[-2:]):
-                    raise ValueError(f"metrics='device' compares a {H} x {W} render with {tuple(images.shape[-2:])} ground truth: "
-                                     "use scale=1 or no_compare_gt")
-                src = viewlist[cat_name + "/" + obj_base] if use_lut else fixed_source
-                src_mask = torch.zeros(NV, dtype=torch.bool)
-                src_mask[src] = True
-                tgt_mask = torch.ones(NV, dtype=torch.bool)
-                if eval_view_list is not None:
-                    tgt_mask = torch.zeros(NV, dtype=torch.bool)
-                    tgt_mask[torch.as_tensor(eval_view_list, dtype=torch.long)] = True
-                if not include_src:
-                    tgt_mask = tgt_mask & ~src_mask
-                novel = tgt_mask.nonzero(as_tuple=False).reshape(-1)
-                focal = data["focal"]
-                focal = torch.tensor(focal, dtype=torch.float32) if isinstance(focal, float) else torch.as_tensor(focal).float()
-                c = data.get("c")
-                c = None if c is None else torch.as_tensor(c).float()
-                poses = torch.as_tensor(data["poses"]).float()
-                net.encode(images[src_mask].to(dev).unsqueeze(0), poses[src_mask].to(dev).unsqueeze(0), focal[None].to(dev),
-                           c=None if c is None else c.to(dev).unsqueeze(0))
-                if sharded:
-                    # every rank ran the trunk on the same images, but a convolution library may pick different algorithms in
-                    # different processes (last-bit differences): rank 0's maps are THE maps, so that the gathered frame is one
-                    # consistent render (64 KB ... 6 MB per object, once — SURVEY 8e)
-                    maps = [m.detach().clone() for m in net.encoder.level_maps()]
-                    for m in maps:
-                        if dist.get_backend() == "nccl":
-                            dist.broadcast(m, src=0)
-                        else:
-                            h = m.cpu()
-                            dist.broadcast(h, src=0)
-                            m.copy_(h)
-                    net.encoder.set_latents(maps)
-
-                def render_view(vi):
-                    # keyed by (object, view), not by a running count: a resumed run draws what the uninterrupted run drew
-                    view_seed = frame_seed(frame_seed(base_seed, obj_idx), vi)
-                    if render_par is None:
-                        keep_seed, renderer.forced_seed = renderer.forced_seed, view_seed
-                        try:
-                            return renderer.render_image(net, poses[vi], W, H, focal * scale, z_near, z_far,
-                                                         c=None if c is None else c * scale)
-                        finally:
-                            renderer.forced_seed = keep_seed
-                    rays = util.gen_rays_device(poses[vi], W, H, focal * scale, z_near, z_far,
-                                                c=None if c is None else c * scale, device=dev)
-                    parts, at = [], 0
-                    for r in torch.split(rays, ray_batch_size, dim=0):
-                        parts.append(render_par(r[None], ray_index_base=at, seed=view_seed))
-                        at += r.shape[0]
-                    return (torch.cat([p[0][0] for p in parts], 0).reshape(H, W, 3),
-                            torch.cat([p[1][0] for p in parts], 0).reshape(H, W))
-
-                obj_out = os.path.join(output_dir, obj_name) if writes_files else None
-                if metrics == "device":
-                    views = novel.tolist()
-                    n_gen = len(views)
-                    compare = not no_compare_gt and n_gen > 0
-                    want_u8, want_cmp = writes_files and write_images, writes_files and write_compare and compare
-                    want_dn = writes_files and write_depth
-                    gt_dev = util.upload(images[tgt_mask].float().contiguous(), dev) if compare else None
-                    pairs = torch.empty(n_gen, 2, dtype=torch.float64, device=dev) if compare else None
-                    u8_h = pinned("u8", (n_gen, H, W, 3), torch.uint8) if want_u8 else None
-                    cmp_h = pinned("cmp", (n_gen, H, 2 * W, 3), torch.uint8) if want_cmp else None
-                    dn_h = pinned("dn", (n_gen, H, W), torch.float32) if want_dn else None
-                    want_dpng = want_dn and depth_png
-                    dpng_h = pinned("dpng", (n_gen, H, W, 3), torch.uint8) if want_dpng else None
-                    for i, vi in enumerate(views):
-                        rgb, depth = render_view(vi)
-                        u8, cmp, dn, _ = util.eval_frame(rgb, depth if want_dn else None, gt_dev[i] if compare else None,
-                                                         z_near=z_near, z_far=z_far, want_u8=want_u8, want_compare=want_cmp,
-                                                         want_depth=want_dn, want_metrics=compare,
-                                                         metrics_out=pairs[i] if compare else None)
-                        dpng = util.cmap_device(dn, lut)[0] if want_dpng else None
-                        for dst, src_t in ((u8_h, u8), (cmp_h, cmp), (dn_h, dn), (dpng_h, dpng)):
-                            if dst is not None:
-                                dst[i].copy_(src_t, non_blocking=True)
-                    pairs_h = None
-                    if compare:
-                        pairs_h = pinned("pairs", (n_gen, 2), torch.float64)
-                        pairs_h.copy_(pairs, non_blocking=True)
-                    if n_gen:
-                        done = torch.cuda.Event()
-                        done.record(torch.cuda.current_stream(dev))
-                        done.synchronize()                                  # the one wait of this object
-                    if writes_files and n_gen and (want_u8 or want_cmp or want_dn):
-                        os.makedirs(obj_out, exist_ok=True)
-                    curr_psnr = curr_ssim = 0.0
-                    for i, vi in enumerate(views):
-                        if want_u8:
-                            write_png(os.path.join(obj_out, "{:06}.png".format(vi)), u8_h[i].numpy())
-                        if want_dn:
-                            np.save(os.path.join(obj_out, "{:06}_depth.npy".format(vi)), dn_h[i].numpy())
-                        if want_dpng:
-                            write_png(os.path.join(obj_out, "{:06}_depth_norm.png".format(vi)), dpng_h[i].numpy())
-                        if compare:
-                            mse, s = (float(x) for x in pairs_h[i])
-                            curr_ssim += s
-                            curr_psnr += float("inf") if mse == 0.0 else 10.0 * math.log10(1.0 / mse) if mse > 0.0 else float("nan")
-                            if want_cmp:
-                                write_png(os.path.join(obj_out, "{:06}_compare.png".format(vi)), cmp_h[i].numpy())
-                    if compare:
-                        curr_psnr /= n_gen
-                        curr_ssim /= n_gen
-                else:
-                    frames, depths, pending = [], [], None
-                    for vi in novel.tolist():
-                        rgb, depth = render_view(vi)
-                        nxt = renderer.frame_to_host_async(rgb, depth)          # D2H overlaps the next view's render
-                        if pending is not None:
-                            pending[2].synchronize()
-                            frames.append(pending[0])
-                            depths.append(pending[1])
-                        pending = nxt
-                    if pending is not None:
-                        pending[2].synchronize()
-                        frames.append(pending[0])
-                        depths.append(pending[1])
-                    all_rgb = torch.clamp(torch.stack(frames), 0.0, 1.0).numpy() if frames else np.zeros((0, H, W, 3), np.float32)
-                    n_gen = len(frames)
-                    if writes_files and write_images:
-                        os.makedirs(obj_out, exist_ok=True)
-                        for i in range(n_gen):
-                            write_png(os.path.join(obj_out, "{:06}.png".format(int(novel[i]))), quantize_uint8(all_rgb[i]))
-                    if writes_files and write_depth and n_gen:
-                        os.makedirs(obj_out, exist_ok=True)
-                        all_depth = ((torch.stack(depths) - z_near) / (z_far - z_near)).numpy()       # eval.py:288-289
-                        for i in range(n_gen):
-                            np.save(os.path.join(obj_out, "{:06}_depth.npy".format(int(novel[i]))), all_depth[i])
-                            if depth_png:
-                                write_png(os.path.join(obj_out, "{:06}_depth_norm.png".format(int(novel[i]))),
-                                          util.cmap(all_depth[i], lut))
-                    curr_psnr = curr_ssim = 0.0
-                    if not no_compare_gt and n_gen:
-                        gt = (images * 0.5 + 0.5)[tgt_mask].permute(0, 2, 3, 1).contiguous().numpy()
-                        for i in range(n_gen):
-                            curr_ssim += ssim(all_rgb[i], gt[i], data_range=1)
-                            curr_psnr += psnr(all_rgb[i], gt[i], data_range=1)
-                            if writes_files and write_compare:
-                                write_png(os.path.join(output_dir, obj_name, "{:06}_compare.png".format(int(novel[i]))),
-                                          quantize_uint8(np.hstack((all_rgb[i], gt[i]))))
-                        curr_psnr /= n_gen
-                        curr_ssim /= n_gen
-                total_psnr += curr_psnr
-                total_ssim += curr_ssim
-                cnt += 1
+                H, W = _render_size(images, scale)
+                back.check_size(H, W, images)                                 # before anything is rendered or created
+                src = viewlist[cat_name + "/" + obj_base] if viewlist else fixed_source
+                src_mask, tgt_mask, novel = target_views(images.shape[0], src, eval_view_list, include_src)
+                poses, focal, c = _encode_object(net, data, src_mask, dev, sharded)
+                focal, c = focal * scale, None if c is None else c * scale
+                # the jitter is keyed by (object, view), not by a running count: a resumed run draws what the uninterrupted run drew
+                obj_seed = frame_seed(base_seed, obj_idx)
+                views = novel.tolist()
+                back.begin(os.path.join(output_dir, obj_name) if writes_files else None, images, tgt_mask, views, H, W)
+                for i, vi in enumerate(views):
+                    rgb, depth = _render_view(net, renderer, render_par, frame_seed(obj_seed, vi), poses[vi], W, H, focal, c,
+                                              z_near, z_far, ray_batch_size)
+                    back.frame(i, vi, rgb, depth)
+                curr_psnr, curr_ssim = back.finish()
+                log.append(obj_name, curr_psnr, curr_ssim, 1)
                 if verbose and not no_compare_gt:
-                    print("curr psnr", curr_psnr, "ssim", curr_ssim, "running psnr", total_psnr / cnt, "running ssim", total_ssim / cnt)
-                if log:
-                    log.append(obj_name, curr_psnr, curr_ssim, 1)
+                    print("curr psnr", curr_psnr, "ssim", curr_ssim, "running psnr", log.mean()[0], "running ssim", log.mean()[1])
     finally:
         net.train(was_training)
-        if log:
-            log.close()
+        log.close()
     if sharded:
         dist.barrier()              # rank 0's files are complete when any rank returns
-    if verbose and cnt:
-        print("final psnr", total_psnr / cnt, "ssim", total_ssim / cnt)
-    return (total_psnr / cnt, total_ssim / cnt, cnt) if cnt else (0.0, 0.0, 0)
+    if verbose and log.cnt:
+        print("final psnr", log.mean()[0], "ssim", log.mean()[1])
+    return (*log.mean(), log.cnt)

@@ -3,6 +3,7 @@ Host-side helpers around the render path: config access, camera/ray construction
 helpers the model protocol uses.  Names follow the reference's src/util/util.py so callers can switch
 imports; the implementations are this package's own.
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -153,7 +154,6 @@ def seed_from_torch():
 def gen_rays_device(pose, width, height, focal, z_near, z_far, c=None, device="cuda"):
     """gen_rays for ONE camera, computed on the GPU by libpnr_hip (pnr_gen_rays): pose (4,4) c2w on the host ->
     rays (H*W, 8) on `device`, never materialised on the host."""
-    import ctypes as C
     from . import _native as N
     f = torch.as_tensor(focal, dtype=torch.float32).flatten()
     fx, fy = float(f[0]), float(f[-1])
@@ -179,7 +179,6 @@ def gen_grid_device(c1, c2, reso, first=0, count=None, fake_viewdirs=False, devi
     """Points [first, first + count) of gen_grid(*zip(c1, c2, reso), ij_indexing=True), written on the GPU by libpnr_hip
     (pnr_grid_points) with the bits of the host version -> xyz (count, 3) [, viewdirs (count, 3) = -p / |p|, the fake view
     directions of recon.marching_cubes; (0, 0, 0) for a point of length 0] on `device`."""
-    import ctypes as C
     from . import _native as N
     if len(c1) != 3 or len(c2) != 3 or len(reso) != 3:
         raise ValueError("c1, c2 and reso must have 3 entries each")
@@ -252,19 +251,30 @@ def train_batch(images, poses, focal, c, pix_inds, z_near, z_far):
     return rays, rgb_gt
 
 
-def _pixel_stride(t, H, W, last, name):
-    """Floats per pixel of a frame that is dense or a regular view into a per-pixel record (row-major pixels, unit stride
-    inside the pixel): (H, W, 3) with strides (W s, s, 1), or (H, W) with strides (W s, s)."""
-    want = (H, W, last) if last else (H, W)
+def _record_stride(t, lead, last, name):
+    """Floats per element of a tensor of shape lead [+ (last,)] — lead = (H, W) for a frame, (n,) for per-ray outputs — that is
+    dense or a regular view into a packed per-element record: unit stride inside the element and, for a frame, row-major
+    pixels ((H, W, 3) with strides (W s, s, 1), (H, W) with (W s, s); (n, last) with (s, 1), (n,) with s)."""
+    want = (*lead, last) if last else tuple(lead)
     if tuple(t.shape) != want or t.dtype != torch.float32:
         raise ValueError(f"{name} must be float32 {want}, got {t.dtype} {tuple(t.shape)}")
     if t.is_contiguous():
         return max(last, 1)
-    st = t.stride()
-    s = st[1]
-    if s < max(last, 1) or (last and st[2] != 1) or (H > 1 and st[0] != W * s):
-        raise ValueError(f"{name} must be dense or a view into a per-pixel record, got strides {st}")
+    st, k = t.stride(), len(lead)
+    s = st[k - 1]
+    if s < max(last, 1) or (last > 1 and st[k] != 1) or (k == 2 and lead[0] > 1 and st[0] != lead[1] * s):
+        raise ValueError(f"{name} must be dense or a view into a per-{'pixel' if k == 2 else 'ray'} record, got strides {st}")
     return s
+
+
+def _workspace(nbytes, dev):
+    """The scratch of one native call: max(nbytes, 16) bytes.  torch's allocations are at least 256-byte aligned, which
+    covers the 4- and 8-byte alignment the entry points ask for."""
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+
+
+def _dp(t):
+    return None if t is None else t.data_ptr()
 
 
 def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True, want_compare=False, want_depth=False,
@@ -288,8 +298,8 @@ def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True,
     if not (want_compare or want_metrics):
         gt = None
     dev = N.same_device(rgb, depth, gt, metrics_out)
-    rs = _pixel_stride(rgb, H, W, 3, "rgb")
-    ds = 0 if depth is None else _pixel_stride(depth, H, W, 0, "depth")
+    rs = _record_stride(rgb, (H, W), 3, "rgb")
+    ds = 0 if depth is None else _record_stride(depth, (H, W), 0, "depth")
     if gt is not None:
         if tuple(gt.shape) != (3, H, W) or gt.dtype != torch.float32:
             raise ValueError(f"gt must be float32 (3, {H}, {W}), got {gt.dtype} {tuple(gt.shape)}")
@@ -304,16 +314,14 @@ def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True,
         if tuple(metrics.shape) != (2,) or metrics.dtype != torch.float64 or not metrics.is_contiguous():
             raise ValueError(f"metrics_out must be a contiguous float64 (2,), got {metrics.dtype} {tuple(metrics.shape)}")
         nbytes = int(N.lib.pnr_eval_frame_workspace_bytes(W, H))
-        ws = torch.empty(max(nbytes, 16) // 8, dtype=torch.float64, device=dev)
-    dp = lambda t: None if t is None else t.data_ptr()
-    N.check(N.lib.pnr_eval_frame(rgb.data_ptr(), rs, dp(depth), ds, dp(gt), W, H, float(z_near), float(z_far), dp(rgb_u8),
-                                 dp(compare_u8), dp(depth_norm), dp(metrics), dp(ws), nbytes, N.current_stream(dev)),
+        ws = _workspace(nbytes, dev)
+    N.check(N.lib.pnr_eval_frame(rgb.data_ptr(), rs, _dp(depth), ds, _dp(gt), W, H, float(z_near), float(z_far), _dp(rgb_u8),
+                                 _dp(compare_u8), _dp(depth_norm), _dp(metrics), _dp(ws), nbytes, N.current_stream(dev)),
             "pnr_eval_frame")
     return rgb_u8, compare_u8, depth_norm, metrics
 
 
 def _upsample_sizes(shapes):
-    import ctypes as C
     arr = lambda k: (C.c_int32 * len(shapes))(*[int(s[k]) for s in shapes])
     return arr(1), arr(2), arr(3)
 
@@ -324,7 +332,6 @@ class _UpsampleConcat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, half_dtype, *levels):
-        import ctypes as C
         from . import _native as N
         dev = N.same_device(*levels)
         shapes = [tuple(l.shape) for l in levels]
@@ -349,7 +356,6 @@ class _UpsampleConcat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out, *_):
-        import ctypes as C
         from . import _native as N
         shapes, dev = ctx.shapes, ctx.device
         grads = [torch.empty(s, device=dev, dtype=torch.float32) if need else None
@@ -449,14 +455,14 @@ def cmap_device(map, lut=None):
     if not torch.is_tensor(map) or map.dim() != 2:
         raise ValueError(f"map must be a float32 (H, W) tensor, got {tuple(getattr(map, 'shape', ()))}")
     H, W = int(map.shape[0]), int(map.shape[1])
-    stride = _pixel_stride(map, H, W, 0, "map")
+    stride = _record_stride(map, (H, W), 0, "map")
     dev = N.same_device(map)
     lut = _device_lut(lut, dev)
     N.same_device(map, lut)
     u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
     minmax = torch.empty(2, dtype=torch.float32, device=dev)
     nbytes = int(N.lib.pnr_cmap_workspace_bytes(W, H))
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dev)
+    ws = _workspace(nbytes, dev)
     N.check(N.lib.pnr_cmap(map.data_ptr(), stride, W, H, lut.data_ptr(), u8.data_ptr(), minmax.data_ptr(), ws.data_ptr(),
                            nbytes, N.current_stream(dev)), "pnr_cmap")
     return u8, minmax
@@ -472,20 +478,6 @@ class VisPanel:
         self.panel, self.panel_u8, self.alpha, self.stats, self.mse, self.psnr = panel, panel_u8, alpha, stats, mse, psnr
 
 
-def _ray_stride(t, n, last, name):
-    """Floats per ray of a per-ray output that is dense or a column range of a packed per-ray record: (n, last) with strides
-    (s, 1), or (n,) with stride s."""
-    want = (n, last) if last else (n,)
-    if tuple(t.shape) != want or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32 {want}, got {t.dtype} {tuple(t.shape)}")
-    if t.is_contiguous():
-        return max(last, 1)
-    st = t.stride()
-    if st[0] < max(last, 1) or (last and last > 1 and st[1] != 1):
-        raise ValueError(f"{name} must be dense or a view into a per-ray record, got strides {st}")
-    return st[0]
-
-
 def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, want_u8=False, want_alpha=False):
     """The picture of the reference's vis_step (train/train.py:497-526) for one target view, on the GPU by libpnr_hip
     (pnr_vis_panel): per pass one row [source views | ground truth | cmap(depth) | rgb | cmap(alpha)], coarse over fine.
@@ -493,7 +485,6 @@ def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, wa
     of one or two (rgb (H W, 3), depth (H W), weights (H W, K)), float32, dense or views into a packed per-ray record.
     -> VisPanel; everything stays on the device and nothing waits.  lut as in cmap_device.  include/pnr.h fixes the arithmetic
     (alpha is an fp64 sum in ascending k, not torch's .sum(-1); the default table is parity unpinned)."""
-    import ctypes as C
     from . import _native as N
     if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
         raise ValueError(f"images must be float32 (NV, 3, H, W), got {images.dtype} {tuple(images.shape)}")
@@ -514,9 +505,9 @@ def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, wa
             raise ValueError(f"weights must be (H*W, K), got {tuple(weights.shape)}")
         K = int(weights.shape[1])
         arr[i].rgb, arr[i].depth, arr[i].weights = rgb.data_ptr(), depth.data_ptr(), weights.data_ptr()
-        arr[i].rgb_stride = _ray_stride(rgb, H * W, 3, "rgb")
-        arr[i].depth_stride = _ray_stride(depth, H * W, 0, "depth")
-        arr[i].weights_stride = _ray_stride(weights, H * W, K, "weights")
+        arr[i].rgb_stride = _record_stride(rgb, (H * W,), 3, "rgb")
+        arr[i].depth_stride = _record_stride(depth, (H * W,), 0, "depth")
+        arr[i].weights_stride = _record_stride(weights, (H * W,), K, "weights")
         arr[i].K = K
     panel = torch.empty(n_pass * H, (NS + 4) * W, 3, dtype=torch.float32, device=dev) if want_f32 else None
     panel_u8 = torch.empty(n_pass * H, (NS + 4) * W, 3, dtype=torch.uint8, device=dev) if want_u8 else None
@@ -524,9 +515,8 @@ def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, wa
     stats = torch.empty(n_pass, 6, dtype=torch.float32, device=dev)
     mse = torch.empty((), dtype=torch.float64, device=dev)
     nbytes = int(N.lib.pnr_vis_panel_workspace_bytes(W, H, n_pass))
-    ws = torch.empty(max(nbytes, 16) // 8 + 1, dtype=torch.float64, device=dev)
-    dp = lambda t: None if t is None else t.data_ptr()
+    ws = _workspace(nbytes, dev)
     N.check(N.lib.pnr_vis_panel(images.data_ptr(), NV, (C.c_int32 * NS)(*src), NS, int(gt_view), arr, n_pass, W, H,
-                                lut.data_ptr(), dp(panel), dp(panel_u8), dp(alpha), stats.data_ptr(), mse.data_ptr(),
+                                lut.data_ptr(), _dp(panel), _dp(panel_u8), _dp(alpha), stats.data_ptr(), mse.data_ptr(),
                                 ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_vis_panel")
     return VisPanel(panel, panel_u8, alpha, stats, mse, -10.0 * torch.log10(mse))

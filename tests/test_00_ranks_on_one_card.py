@@ -155,14 +155,14 @@ def _eval_setup():
     import golden_util as gu
     from hip_util import model_conf
     from pixel_nerf_multiscale_amd import NeRFRenderer, PixelNeRFNet
-    from test_gpu_eval_loop import _make_dataset
+    from eval_util import make_dataset
     spec = dict(gu.CASES["full_ns1"])
     torch.manual_seed(0)
     net = PixelNeRFNet(model_conf(spec, "fp32")).cuda().eval()
     for which, mlp in (("coarse", net.mlp_coarse), ("fine", net.mlp_fine)):
         mlp.load_state_dict({k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, which).items()})
     rend = NeRFRenderer(n_coarse=32, n_fine=16, n_fine_depth=8, white_bkgd=True).cuda().eval()
-    data = _make_dataset(net, rend, 2, 4, 32, 32, 33.0, seed=99)
+    data = make_dataset(net, rend, 2, 4, 32, 32, 33.0, seed=99)
     net.precision = "fp16"
     return net, rend, data
 

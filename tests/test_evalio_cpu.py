@@ -91,3 +91,64 @@ def test_write_png_round_trip(tmp_path):
     rows = zlib.decompress(chunks[1][1])
     back = np.frombuffer(rows, np.uint8).reshape(13, 1 + 7 * 3)
     assert (back[:, 0] == 0).all() and (back[:, 1:].reshape(13, 7, 3) == u8).all()
+
+
+def test_target_views():
+    """Source / target selection of evaluate() for NV = 5, against expectations written by hand."""
+    def sel(src, eval_view_list, include_src):
+        src_mask, tgt_mask, novel = evalio.target_views(5, torch.tensor(sorted(int(x) for x in src.split())), eval_view_list, include_src)
+        assert src_mask.dtype == torch.bool and tgt_mask.dtype == torch.bool and novel.dtype == torch.long
+        assert tgt_mask.nonzero().reshape(-1).tolist() == novel.tolist()
+        return src_mask.tolist(), novel.tolist()
+    assert sel("0", None, False) == ([True, False, False, False, False], [1, 2, 3, 4])
+    assert sel("1 3", None, False) == ([False, True, False, True, False], [0, 2, 4])
+    assert sel("0", [0, 2], False) == ([True, False, False, False, False], [2])
+    assert sel("0", [0, 2], True) == ([True, False, False, False, False], [0, 2])
+    assert sel("1 3", torch.tensor([4, 3, 0]), False) == ([False, True, False, True, False], [0, 4])     # a source in the eval list
+    assert sel("1 3", torch.tensor([4, 3, 0]), True) == ([False, True, False, True, False], [0, 3, 4])
+    assert sel("0", None, True)[1] == [0, 1, 2, 3, 4]
+
+
+def test_host_back_end_writes_and_scores_host_frames(tmp_path):
+    """The tail of evaluate(metrics="host") without a GPU: two 9 x 8 frames that are already on the host go through
+    begin / frame / finish with every output on."""
+    from types import SimpleNamespace
+    from eval_util import read_png
+    H, W, NV, zn, zf = 9, 8, 4, 1.25, 2.75
+    rng = np.random.default_rng(3)
+    images = torch.from_numpy(rng.uniform(-1, 1, (NV, 3, H, W)).astype(np.float32))
+    _, tgt_mask, novel = evalio.target_views(NV, torch.tensor([0]), [1, 3], False)
+    views = novel.tolist()
+    assert views == [1, 3]
+    rgbs = [rng.uniform(-0.2, 1.2, (H, W, 3)).astype(np.float32) for _ in views]          # leaves [0, 1] in places
+    depths = [rng.uniform(zn, zf, (H, W)).astype(np.float32) for _ in views]
+    assert all((x < 0).any() and (x > 1).any() for x in rgbs)
+
+    class Copied:
+        def synchronize(self):
+            pass
+    o = SimpleNamespace(z_near=zn, z_far=zf, compare_gt=True, write_images=True, write_compare=True, write_depth=True,
+                        depth_png=False, lut=None)
+    back = evalio._HostBackEnd(o, lambda rgb, depth: (rgb, depth, Copied()))
+    obj = str(tmp_path / "out" / "obj000")
+    back.begin(obj, images, tgt_mask, views, H, W)
+    for i, vi in enumerate(views):
+        back.frame(i, vi, torch.from_numpy(rgbs[i]), torch.from_numpy(depths[i]))
+    got = back.finish()
+    assert sorted(os.listdir(obj)) == sorted(f"{v:06}{suffix}" for v in views for suffix in (".png", "_compare.png", "_depth.npy"))
+    g01 = (images * 0.5 + 0.5).permute(0, 2, 3, 1).contiguous().numpy()
+    psnr = ssim = 0.0
+    for i, v in enumerate(views):
+        xc = np.clip(rgbs[i], 0.0, 1.0)
+        assert np.array_equal(read_png(os.path.join(obj, f"{v:06}.png")), evalio.quantize_uint8(xc))
+        assert np.array_equal(read_png(os.path.join(obj, f"{v:06}_compare.png")), evalio.quantize_uint8(np.hstack((xc, g01[v]))))
+        dn = np.load(os.path.join(obj, f"{v:06}_depth.npy"))
+        assert dn.dtype == np.float32 and np.array_equal(dn, (depths[i] - np.float32(zn)) / np.float32(zf - zn))
+        psnr += evalio.psnr(xc, g01[v])
+        ssim += evalio.ssim(xc, g01[v])
+    assert got == (psnr / len(views), ssim / len(views))
+    # a rank that writes nothing: the same pair, no directory
+    back.begin(None, images, tgt_mask, views, H, W)
+    for i, vi in enumerate(views):
+        back.frame(i, vi, torch.from_numpy(rgbs[i]), torch.from_numpy(depths[i]))
+    assert back.finish() == got and os.listdir(str(tmp_path / "out")) == ["obj000"]

@@ -13,12 +13,12 @@ Bounds (all fixed by the formats, none by what the kernel gives):
 import functools
 import math
 import os
-import struct
-import zlib
 
 import numpy as np
 import pytest
 import torch
+
+from eval_util import make_dataset, read_png
 
 pytestmark = pytest.mark.gpu
 
@@ -164,40 +164,6 @@ def test_normalised_depth(zn, zf):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the loop
-class _Objects(list):
-    z_near, z_far, lindisp = 1.25, 2.75, False
-
-
-def _make_dataset(net32, rend, n_obj, NV, W, H, focal, seed=777):
-    """The two-object dataset of tests/test_gpu_eval_loop.py (a local copy of its helper): ground truth = this package's
-    fp32-path render of every target view with the jitter evaluate(seed=seed) will draw for that (object, view)."""
-    import golden_util as gu
-    from pixel_nerf_multiscale_amd.parallel import frame_seed
-    data = _Objects()
-    for o in range(n_obj):
-        poses = torch.from_numpy(np.stack([gu.pose_spherical(40.0 * v + 13.0 * o, -20.0 - 3.0 * o, 2.0) for v in range(NV)]))
-        g = torch.Generator().manual_seed(100 + o)
-        src_img = torch.rand(1, 3, H, W, generator=g) * 2 - 1
-        images = torch.zeros(NV, 3, H, W)
-        images[0] = src_img[0]
-        net32.encode(src_img.cuda()[None], poses[:1].cuda()[None], torch.tensor(focal)[None].cuda())
-        for v in range(1, NV):
-            rend.forced_seed = frame_seed(frame_seed(seed, o), v)
-            rgb, _ = rend.render_image(net32, poses[v], W, H, focal, data.z_near, data.z_far)
-            images[v] = (rgb.clamp(0, 1).permute(2, 0, 1) * 2 - 1).cpu()
-        data.append(dict(path=f"/data/cat{o % 2}/obj{o:03d}", images=images, poses=poses, focal=focal))
-    rend.forced_seed = None
-    return data
-
-
-def _read_png(path):
-    raw = open(path, "rb").read()
-    w, h = struct.unpack(">II", raw[16:24])
-    at = raw.index(b"IDAT")
-    n = struct.unpack(">I", raw[at - 4:at])[0]
-    return np.frombuffer(zlib.decompress(raw[at + 4:at + 4 + n]), np.uint8).reshape(h, 1 + 3 * w)[:, 1:].reshape(h, w, 3)
-
-
 def test_evaluate_on_the_device_back_end(tmp_path):
     import golden_util as gu
     from hip_util import model_conf
@@ -210,7 +176,7 @@ def test_evaluate_on_the_device_back_end(tmp_path):
     for which, mlp in (("coarse", net.mlp_coarse), ("fine", net.mlp_fine)):
         mlp.load_state_dict({k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, which).items()})
     rend = NeRFRenderer(n_coarse=32, n_fine=16, n_fine_depth=8, white_bkgd=True).cuda().eval()
-    data = _make_dataset(net, rend, 2, NV, W, H, focal)
+    data = make_dataset(net, rend, 2, NV, W, H, focal)
     out = str(tmp_path / "eval_out")
     net.precision = "fp16"
 
@@ -240,8 +206,8 @@ def test_evaluate_on_the_device_back_end(tmp_path):
             for i, v in enumerate(range(1, NV)):
                 rgb, depth = frames[o * (NV - 1) + i]
                 xc = rgb.clamp(0, 1).cpu().numpy()
-                assert np.array_equal(_read_png(os.path.join(obj, f"{v:06}.png")), evalio.quantize_uint8(xc))
-                assert np.array_equal(_read_png(os.path.join(obj, f"{v:06}_compare.png")),
+                assert np.array_equal(read_png(os.path.join(obj, f"{v:06}.png")), evalio.quantize_uint8(xc))
+                assert np.array_equal(read_png(os.path.join(obj, f"{v:06}_compare.png")),
                                       evalio.quantize_uint8(np.hstack((xc, g01[v]))))
                 dn = np.load(os.path.join(obj, f"{v:06}_depth.npy"))
                 assert dn.dtype == np.float32 and dn.shape == (H, W)
@@ -267,7 +233,7 @@ def test_evaluate_on_the_device_back_end(tmp_path):
                                                                            for suffix in (".png", "_depth.npy"))
         for i, v in enumerate(range(1, NV)):
             rgb, depth = frames[i]
-            assert np.array_equal(_read_png(os.path.join(out_h, "obj000", f"{v:06}.png")),
+            assert np.array_equal(read_png(os.path.join(out_h, "obj000", f"{v:06}.png")),
                                   evalio.quantize_uint8(rgb.clamp(0, 1).cpu().numpy()))
             dn = np.load(os.path.join(out_h, "obj000", f"{v:06}_depth.npy"))
             assert dn.dtype == np.float32 and dn.shape == (H, W)

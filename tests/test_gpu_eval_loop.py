@@ -8,33 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from eval_util import make_dataset, read_png
+
 pytestmark = pytest.mark.gpu
-
-
-class _Objects(list):
-    z_near, z_far, lindisp = 1.25, 2.75, False
-
-
-def _make_dataset(net32, rend, n_obj, NV, W, H, focal, seed=777):
-    """Ground truth = this package's fp32-path render of every target view with the jitter evaluate(seed=seed) will draw for
-    that (object, view): evalio keys the per-view seed by frame_seed(frame_seed(seed, object), view)."""
-    import golden_util as gu
-    from pixel_nerf_multiscale_amd.parallel import frame_seed
-    data = _Objects()
-    for o in range(n_obj):
-        poses = torch.from_numpy(np.stack([gu.pose_spherical(40.0 * v + 13.0 * o, -20.0 - 3.0 * o, 2.0) for v in range(NV)]))
-        g = torch.Generator().manual_seed(100 + o)
-        src_img = torch.rand(1, 3, H, W, generator=g) * 2 - 1                 # the source view is a random image: only the
-        images = torch.zeros(NV, 3, H, W)                                       # trunk sees it
-        images[0] = src_img[0]
-        net32.encode(src_img.cuda()[None], poses[:1].cuda()[None], torch.tensor(focal)[None].cuda())
-        for v in range(1, NV):
-            rend.forced_seed = frame_seed(frame_seed(seed, o), v)               # the same jitter in ground truth and evaluation
-            rgb, _ = rend.render_image(net32, poses[v], W, H, focal, data.z_near, data.z_far)
-            images[v] = (rgb.clamp(0, 1).permute(2, 0, 1) * 2 - 1).cpu()
-        data.append(dict(path=f"/data/cat{o % 2}/obj{o:03d}", images=images, poses=poses, focal=focal))
-    rend.forced_seed = None
-    return data
 
 
 def test_evaluate_two_objects_resume_and_lut(tmp_path):
@@ -49,7 +25,7 @@ def test_evaluate_two_objects_resume_and_lut(tmp_path):
     for which, mlp in (("coarse", net.mlp_coarse), ("fine", net.mlp_fine)):
         mlp.load_state_dict({k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, which).items()})
     rend = NeRFRenderer(n_coarse=32, n_fine=16, n_fine_depth=8, white_bkgd=True).cuda().eval()
-    data = _make_dataset(net, rend, 2, NV, W, H, focal)
+    data = make_dataset(net, rend, 2, NV, W, H, focal)
     out = str(tmp_path / "eval_out")
 
     # pass 1: only the first object (max_objects = 1), fixed source view "0", fp16 kernel
@@ -97,11 +73,7 @@ def test_evaluate_two_objects_resume_and_lut(tmp_path):
     assert m4 == (0.0, 0.0, 2)
 
     # the PNGs hold the truncating quantisation of the clamped render (eval.py:301)
-    import struct, zlib
-    raw = open(os.path.join(out, "obj001", "000002.png"), "rb").read()
-    idat = raw[raw.index(b"IDAT") + 4:]
-    n = struct.unpack(">I", raw[raw.index(b"IDAT") - 4:raw.index(b"IDAT")])[0]
-    px = np.frombuffer(zlib.decompress(idat[:n]), np.uint8).reshape(H, 1 + 3 * W)[:, 1:].reshape(H, W, 3)
+    px = read_png(os.path.join(out, "obj001", "000002.png"))
     # the frame evaluate() rendered for that file (object 1's targets are views 1, 2, 3: the second call of pass 2) — not a
     # second encode + render: the trunk goes through MIOpen, whose algorithm choice (and with it the latent's last bits) may
     # differ from call to call

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import optim_util as ou
+from eval_util import sync_debug_mode_works
 
 pytestmark = pytest.mark.gpu
 
@@ -357,23 +358,6 @@ def test_step_lr_changes_the_applied_lr():
 
 
 # ------------------------------------------------------------------------------------------------- train.train_step
-def _sync_debug_mode_works():
-    """Whether torch.cuda.set_sync_debug_mode("error") turns a host read of the device into an error under this build."""
-    x = torch.ones(1, device="cuda")
-    torch.cuda.synchronize()
-    try:
-        torch.cuda.set_sync_debug_mode("error")
-        try:
-            x.item()
-        except RuntimeError:
-            return True
-        return False
-    except Exception:
-        return False
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-
-
 def test_train_step_end_to_end():
     """One step on the smallest golden case of test_gpu_train_front (tiny_ns2_codeview, 2 objects x 32 rays) by two routes
     from the same seeds: train.train_step with DeviceAdam, and calc_losses, backward, clip_grad_norm_,
@@ -413,7 +397,7 @@ def test_train_step_end_to_end():
     torch.manual_seed(3); np.random.seed(3)
     with torch.no_grad():
         train.calc_losses(net2, render_par, data2, **kw)            # warm-up of the front end: allocations, code objects
-    works = _sync_debug_mode_works()
+    works = sync_debug_mode_works()
     print(f'torch.cuda.set_sync_debug_mode("error") works under this build: {works}')
     torch.manual_seed(7); np.random.seed(7)
     if works:

@@ -16,13 +16,16 @@ import numpy as np
 import pytest
 import torch
 
+import eval_util as eu
 import golden_util as gu
 import hip_util as hu
 import vis_util as vu
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1), (16, 16), (17, 16), (19, 13), (33, 17)]     # one tile, exact tiles, one extra column, ragged, several tiles
+# one tile, exact tiles, one extra column, ragged, several tiles; 257 tiles of one ragged row: thread 0 of the one-workgroup
+# folds takes two partials
+SHAPES = [(1, 1), (16, 16), (17, 16), (19, 13), (33, 17), (4097, 1)]
 COMBOS = [(K, NS, n_pass) for K in (1, 3, 24, 65) for NS in (1, 3) for n_pass in (1, 2)]
 IDENT = np.arange(256, dtype=np.uint8)[:, None].repeat(3, axis=1)
 
@@ -352,7 +355,7 @@ def test_vis_step_does_not_wait_for_the_device():
     kw = dict(nviews=[3], z_near=Z_NEAR, z_far=Z_FAR)
     torch.manual_seed(3); np.random.seed(3)
     train.vis_step(net, rend, render_par, data, **kw)           # warm-up: allocations, code objects, the cached table
-    works = vu.sync_debug_mode_works()
+    works = eu.sync_debug_mode_works()
     print(f'torch.cuda.set_sync_debug_mode("error") works under this build: {works}')
     if not works:
         print("vis_step's freedom from host waits could not be checked under this build")
@@ -402,29 +405,11 @@ def test_eval_step_and_validate():
 
 
 # ---------------------------------------------------------------------------------------------- evaluate(depth_png=True)
-class _Objects(list):
-    z_near, z_far, lindisp = Z_NEAR, Z_FAR, False
-
-
-def _decode_png(path):
-    try:
-        from PIL import Image
-        return np.asarray(Image.open(path).convert("RGB"))
-    except ImportError:
-        import struct
-        import zlib
-        raw = open(path, "rb").read()
-        w, h = struct.unpack(">II", raw[16:24])
-        at = raw.index(b"IDAT")
-        n = struct.unpack(">I", raw[at - 4:at])[0]
-        return np.frombuffer(zlib.decompress(raw[at + 4:at + 4 + n]), np.uint8).reshape(h, 1 + 3 * w)[:, 1:].reshape(h, w, 3)
-
-
 @pytest.mark.parametrize("metrics", ["host", "device"])
 def test_evaluate_writes_the_depth_png(metrics, tmp_path):
     from pixel_nerf_multiscale_amd import evalio, util
     net, rend, data = _setup()
-    toy = _Objects([dict(path="/data/cat0/obj000", images=data["images"][0][:2], poses=data["poses"][0][:2], focal=18.0)])
+    toy = eu.Objects([dict(path="/data/cat0/obj000", images=data["images"][0][:2], poses=data["poses"][0][:2], focal=18.0)])
     kw = dict(source="0", verbose=False, seed=777, metrics=metrics, no_compare_gt=True)
     plain = str(tmp_path / "plain")
     evalio.evaluate(net, rend, toy, plain, write_depth=True, **kw)
@@ -434,12 +419,12 @@ def test_evaluate_writes_the_depth_png(metrics, tmp_path):
     assert sorted(os.listdir(os.path.join(out, "obj000"))) == ["000001.png", "000001_depth.npy", "000001_depth_norm.png"]
     dn = np.load(os.path.join(out, "obj000", "000001_depth.npy"))
     assert dn.shape == (H, W) and np.array_equal(dn, np.load(os.path.join(plain, "obj000", "000001_depth.npy")))
-    png = _decode_png(os.path.join(out, "obj000", "000001_depth_norm.png"))
+    png = eu.read_png(os.path.join(out, "obj000", "000001_depth_norm.png"))
     assert png.shape == (H, W, 3) and np.array_equal(png, util.cmap(dn)) and len(np.unique(png.reshape(-1, 3), axis=0)) >= 2
     # an explicit table; and depth_png without write_depth writes nothing new
     out2 = str(tmp_path / "ident")
     evalio.evaluate(net, rend, toy, out2, write_depth=True, depth_png=True, lut=IDENT, **kw)
-    png2 = _decode_png(os.path.join(out2, "obj000", "000001_depth_norm.png"))
+    png2 = eu.read_png(os.path.join(out2, "obj000", "000001_depth_norm.png"))
     assert np.array_equal(png2, util.cmap(np.load(os.path.join(out2, "obj000", "000001_depth.npy")), IDENT))
     out3 = str(tmp_path / "no_depth")
     evalio.evaluate(net, rend, toy, out3, depth_png=True, **kw)

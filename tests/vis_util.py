@@ -104,22 +104,3 @@ def panel_model(images, src_views, gt_view, passes, lut):
     sq = ((x - g) ** 2).reshape(-1)
     mse = float(np.cumsum(sq)[-1] / (3.0 * H * W)) if not np.isnan(sq).any() else float("nan")
     return dict(panel=panel, panel_u8=to_u8(panel), alpha=np.stack(alphas), stats=stats, mse=mse)
-
-
-def sync_debug_mode_works():
-    """Whether torch.cuda.set_sync_debug_mode("error") turns a host read of the device into an error under this build
-    (the probe of tests/test_gpu_optim.py, restated)."""
-    import torch
-    x = torch.ones(1, device="cuda")
-    torch.cuda.synchronize()
-    try:
-        torch.cuda.set_sync_debug_mode("error")
-        try:
-            x.item()
-        except RuntimeError:
-            return True
-        return False
-    except Exception:
-        return False
-    finally:
-        torch.cuda.set_sync_debug_mode("default")

@@ -22,15 +22,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-class _Objects(list):
-    z_near, z_far, lindisp = 1.25, 2.75, False
-
-
 def worker(a):
-    import numpy as np
     import torch
 
     import golden_util as gu
+    from eval_util import make_dataset
     from hip_util import model_conf
     from pixel_nerf_multiscale_amd import NeRFRenderer, PixelNeRFNet, evalio
     from pixel_nerf_multiscale_amd.parallel import frame_seed
@@ -42,19 +38,7 @@ def worker(a):
     for which, mlp in (("coarse", net.mlp_coarse), ("fine", net.mlp_fine)):
         mlp.load_state_dict({k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, which).items()})
     rend = NeRFRenderer(n_coarse=64, n_fine=32, n_fine_depth=16, white_bkgd=True).cuda().eval()
-    data = _Objects()
-    for o in range(a.objects):
-        poses = torch.from_numpy(np.stack([gu.pose_spherical(360.0 * v / NV + 13.0 * o, -20.0 - 3.0 * o, 2.0) for v in range(NV)]))
-        g = torch.Generator().manual_seed(100 + o)
-        images = torch.zeros(NV, 3, H, W)
-        images[0] = torch.rand(3, H, W, generator=g) * 2 - 1
-        net.encode(images[:1].cuda()[None], poses[:1].cuda()[None], torch.tensor(focal)[None].cuda())
-        for v in range(1, NV):
-            rend.forced_seed = frame_seed(frame_seed(seed, o), v)
-            rgb, _ = rend.render_image(net, poses[v], W, H, focal, data.z_near, data.z_far)
-            images[v] = (rgb.clamp(0, 1).permute(2, 0, 1) * 2 - 1).cpu()
-        data.append(dict(path=f"/data/cat{o % 2}/obj{o:03d}", images=images, poses=poses, focal=focal))
-    rend.forced_seed = None
+    data = make_dataset(net, rend, a.objects, NV, W, H, focal, seed=seed, angle_step=360.0 / NV)
     net.precision = "fp16"
     n_views = a.objects * a.views
     tmp = tempfile.mkdtemp(prefix="bench_eval_")
