@@ -28,7 +28,8 @@ extern "C" {
                                   * the evaluation back end, pnr_eval_frame / pnr_eval_frame_workspace_bytes; mesh extraction,
                                   * pnr_grid_points / pnr_mc_workspace_bytes / pnr_mc_count / pnr_mc_emit; the training back end, pnr_optim_chunk_elems /
                                   * pnr_optim_plan / pnr_optim_workspace_bytes / pnr_adam_step; the visualisation panel and the colour map, pnr_cmap_workspace_bytes /
-                                  * pnr_cmap / pnr_vis_panel_workspace_bytes / pnr_vis_panel */
+                                  * pnr_cmap / pnr_vis_panel_workspace_bytes / pnr_vis_panel; the video drivers' ends, pnr_video_frames /
+                                  * pnr_view_strip / pnr_image_to_tensor */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -453,6 +454,53 @@ int32_t  pnr_vis_panel(const float* images /* device, (NV, 3, H, W) in [-1, 1] *
                        const uint8_t* lut, float* panel_f32, uint8_t* panel_u8 /* either may be NULL */,
                        float* alpha /* (n_pass, H, W) or NULL */, float* stats /* n_pass x 6 or NULL */,
                        double* mse /* 1 double or NULL */, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* ---- novel-view video: the two ends of eval/gen_video.py and eval/eval_real.py on the device, csrc/video.hip ------------------
+ * byte(p), the quantisation of a product p shared by pnr_video_frames and pnr_view_strip:
+ *   in range      -1 < p < 256: truncation toward zero, numpy's astype(np.uint8) wherever numpy's cast is defined; a small
+ *                 negative product and -0.0 give 0
+ *   out of range  everything else, NaN included, where numpy's cast is undefined and the drivers do not clamp: the byte
+ *                 saturates, 0 for p <= -1 and for NaN, 255 for p >= 256
+ *
+ * pnr_video_frames: F rendered frames to bytes in ONE launch — (frames.cpu().numpy() * 255).astype(np.uint8), gen_video.py:236,
+ * eval_real.py:151.  out_u8 (F, H, W, 3) = byte(x * 255.0f): ONE fp32 product contracted with nothing, then byte().  rgb holds
+ * F H W pixels, `rgb_stride` floats apart (0 = dense: 3; 4 = the packed per-ray record of pnr_outputs.rgb_stride, where a
+ * camera path is rendered frame after frame).  out_u8 may start at ANY byte: the kernel is flat over the byte stream, a thread
+ * owns three whole dwords (four pixels), and the up to three bytes in front of the first whole dword and behind the last are
+ * written one by one, so nothing outside the 3 F H W bytes is touched.  float4 loads are used only for a dense rgb whose base is
+ * 16-byte aligned under a dword-aligned out_u8; the bytes do not depend on the route.
+ *   n_out_of_range  optional device int64, SET by the call (zeroed on the stream, then integer atomic adds, at most one per
+ *                   workgroup): the number of out-of-range components over all frames.  Exact, whatever the order.
+ * Checks, all before any launch:
+ *   PNR_E_NULL   rgb or out_u8 NULL
+ *   PNR_E_SHAPE  F, W or H < 1, W * H >= 2^31 or F * W * H >= 2^31; a stride below 3
+ *   PNR_E_ALIGN  rgb not 4-byte aligned, n_out_of_range not 8-byte aligned
+ *
+ * pnr_view_strip: the picture of the source views, gen_video.py:239-241.  images (NS, 3, H, W) fp32 -> out_u8 (H, NS W, 3), laid
+ * out as np.hstack over the views, = byte(((x * scale) + lo) * 255.0f): three separately rounded fp32 operations in that order.
+ * scale = lo = 0.5 is the reference's images * 0.5 + 0.5 for a [-1, 1] input; scale = 1, lo = 0 serves a [0, 1] input.
+ *   PNR_E_NULL   images or out_u8 NULL
+ *   PNR_E_SHAPE  NS, W or H < 1, W * H >= 2^31 or NS * W * H >= 2^31
+ *   PNR_E_ALIGN  images not 4-byte aligned
+ *
+ * pnr_image_to_tensor: an 8-bit image (H, W, 3) on the device -> the network's input (3, H, W) fp32.
+ *   balanced = 0  float(b) / 255.0f, one correctly rounded fp32 division: torchvision's ToTensor, which is all that the
+ *                 reference fork's get_image_to_tensor_balanced does (src/util/util.py:68-79)
+ *   balanced = 1  (float(b) / 255.0f - 0.5f) / 0.5f, each operation rounded on its own: ToTensor + Normalize(0.5, 0.5), upstream
+ *                 pixelNeRF's version, range [-1, 1]
+ * Pinned to torch's own arithmetic, t.float().div(255)[.sub(0.5).div(0.5)] on the CPU; PARITY UNPINNED against torchvision
+ * itself, which is not importable where this library is developed.
+ *   PNR_E_NULL   img_u8 or out NULL
+ *   PNR_E_SHAPE  W or H < 1, W * H >= 2^31; balanced not 0 or 1
+ *   PNR_E_ALIGN  out not 4-byte aligned
+ * None of the three reads anything back or allocates. */
+int32_t pnr_video_frames(const float* rgb, int32_t rgb_stride /* floats per pixel, 0 = 3 */, int32_t F, int32_t W, int32_t H,
+                         uint8_t* out_u8 /* (F, H, W, 3), any byte alignment */,
+                         int64_t* n_out_of_range /* device, 1 int64, or NULL */, void* stream);
+int32_t pnr_view_strip(const float* images /* (NS, 3, H, W) */, int32_t NS, int32_t W, int32_t H, float scale, float lo,
+                       uint8_t* out_u8 /* (H, NS W, 3) */, void* stream);
+int32_t pnr_image_to_tensor(const uint8_t* img_u8 /* (H, W, 3) */, int32_t W, int32_t H, int32_t balanced,
+                            float* out /* (3, H, W) */, void* stream);
 
 /* Mesh extraction (util/recon.py: marching_cubes, with util.gen_grid util.py:98-115 and PyMCubes behind it), csrc/mesh.hip.
  *

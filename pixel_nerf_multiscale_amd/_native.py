@@ -160,6 +160,9 @@ PROTOTYPES = {
     "pnr_vis_panel_workspace_bytes": (_u64, [_i32, _i32, _i32]),
     "pnr_vis_panel": (_i32, [_fp, _i32, C.POINTER(_i32), _i32, _i32, C.POINTER(pnr_vis_pass), _i32, _i32, _i32, _fp, _fp, _fp,
                              _fp, _fp, _fp, _fp, _u64, _fp]),         # src_views and passes: HOST addresses
+    "pnr_video_frames": (_i32, [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
+    "pnr_view_strip": (_i32, [_fp, _i32, _i32, _i32, _f, _f, _fp, _fp]),
+    "pnr_image_to_tensor": (_i32, [_fp, _i32, _i32, _i32, _fp, _fp]),
     "pnr_grid_points": (_i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _i64, _i64, _i32, _fp, _fp, _fp]),
     "pnr_mc_workspace_bytes": (_u64, [_i32, _i32, _i32]),
     "pnr_mc_count": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, _fp, _u64, _fp, _fp]),

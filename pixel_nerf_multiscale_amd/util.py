@@ -84,9 +84,21 @@ def psnr(pred, target):
     return -10.0 * math.log10(mse)
 
 
-def pose_spherical(theta, phi, radius):
+def pose_spherical(theta, phi, radius, reference_order=False):
     """c2w (4,4) of a camera at spherical position (theta, phi in degrees) looking at the origin
-    (reference util.py:314-328 conventions: camera looks down -z, world z up after the axis flip)."""
+    (reference util.py:314-328 conventions: camera looks down -z, world z up after the axis flip).
+    reference_order=True (the camera paths of video.py): the reference's own operation order — angle / 180 * pi in fp64,
+    numpy's cos / sin rounded to fp32, the four fp32 matrices multiplied from the right, flip @ (rot_theta @ (rot_phi @
+    trans)) — which reproduces its poses bit for bit (tests/golden/video_paths.npz); the default is within an ulp of it."""
+    if reference_order:
+        th, ph = theta / 180.0 * np.pi, phi / 180.0 * np.pi
+        t = torch.tensor([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, radius], [0, 0, 0, 1]], dtype=torch.float32)
+        rp = torch.tensor([[1, 0, 0, 0], [0, np.cos(ph), -np.sin(ph), 0], [0, np.sin(ph), np.cos(ph), 0], [0, 0, 0, 1]],
+                          dtype=torch.float32)
+        rt = torch.tensor([[np.cos(th), 0, -np.sin(th), 0], [0, 1, 0, 0], [np.sin(th), 0, np.cos(th), 0], [0, 0, 0, 1]],
+                          dtype=torch.float32)
+        flip = torch.tensor([[-1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], dtype=torch.float32)
+        return flip @ (rt @ (rp @ t))
     th, ph = math.radians(theta), math.radians(phi)
     t = torch.eye(4)
     t[2, 3] = radius
@@ -96,6 +108,27 @@ def pose_spherical(theta, phi, radius):
     rt[0, 0], rt[0, 2], rt[2, 0], rt[2, 2] = math.cos(th), -math.sin(th), math.sin(th), math.cos(th)
     flip = torch.tensor([[-1.0, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]])
     return (flip @ rt @ rp @ t).float()
+
+
+def coord_from_blender(dtype=torch.float32, device="cpu"):
+    """(4, 4) Blender (x right, y in, z up) -> standard (x right, y up, z out of the screen) axes (reference util.py:151-162)."""
+    return torch.tensor([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], dtype=dtype, device=device)
+
+
+def coord_to_blender(dtype=torch.float32, device="cpu"):
+    """(4, 4) standard -> Blender axes, the inverse of coord_from_blender (reference util.py:165-176)."""
+    return torch.tensor([[1, 0, 0, 0], [0, 0, -1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], dtype=dtype, device=device)
+
+
+def quat_to_rot(q):
+    """q (B, 4) = (r, i, j, k), any length -> rotation matrices (B, 3, 3) of the normalised quaternions (reference
+    util.py:489-509): F.normalize along dim 1, then the entries in the reference's operation order, so the bits are its bits."""
+    q = torch.nn.functional.normalize(q, dim=1)
+    r, i, j, k = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    rows = ((1 - 2 * (j ** 2 + k ** 2), 2 * (j * i - k * r), 2 * (i * k + r * j)),
+            (2 * (j * i + k * r), 1 - 2 * (i ** 2 + k ** 2), 2 * (j * k - i * r)),
+            (2 * (k * i - j * r), 2 * (j * k + i * r), 1 - 2 * (i ** 2 + j ** 2)))
+    return torch.stack([torch.stack(row, dim=-1) for row in rows], dim=1)
 
 
 def unproj_map(width, height, f, c=None, device="cpu"):
@@ -520,3 +553,78 @@ def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, wa
                                 lut.data_ptr(), _dp(panel), _dp(panel_u8), _dp(alpha), stats.data_ptr(), mse.data_ptr(),
                                 ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_vis_panel")
     return VisPanel(panel, panel_u8, alpha, stats, mse, -10.0 * torch.log10(mse))
+
+
+# ------------------------------------------------------------------------------------------- the ends of the video drivers
+def video_frames(rgb, F, H, W, out=None, count=None):
+    """(frames * 255).astype(np.uint8) of the video drivers (eval/gen_video.py:236, eval/eval_real.py:151) for a stack of F
+    rendered frames, on the GPU by libpnr_hip in ONE launch (pnr_video_frames).  rgb: F*H*W pixels, float32, UNclamped — a
+    contiguous tensor of 3 F H W elements in any shape, or (F*H*W, 3) as a view into the packed (F*H*W, 4) per-ray record.
+    -> (frames_u8 (F, H, W, 3) uint8, n_out_of_range 0-dim int64), both on the device.  In range (-1 < x * 255 < 256) the
+    byte is numpy's; elsewhere (NaN included) numpy's cast is undefined, the byte saturates to 0 / 255 and the component is
+    counted.  out: a contiguous uint8 tensor of 3 F H W elements to write into, at any byte offset of a larger buffer;
+    count: a contiguous int64 device tensor of one element, set by the call.  Nothing here waits for the device."""
+    from . import _native as N
+    F, H, W = int(F), int(H), int(W)
+    P = F * H * W
+    if not torch.is_tensor(rgb) or rgb.dtype != torch.float32:
+        raise ValueError(f"rgb must be a float32 tensor, got {getattr(rgb, 'dtype', type(rgb))}")
+    if rgb.is_contiguous() and rgb.numel() == 3 * P:
+        stride = 3
+    else:
+        stride = _record_stride(rgb, (P,), 3, "rgb")
+    dev = N.same_device(rgb, out, count)
+    if out is None:
+        out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.numel() != 3 * P or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor of {3 * P} elements, got {out.dtype} {tuple(out.shape)}")
+    if count is None:
+        count = torch.empty((), dtype=torch.int64, device=dev)
+    elif count.dtype != torch.int64 or count.numel() != 1 or not count.is_contiguous():
+        raise ValueError(f"count must be a contiguous int64 tensor of one element, got {count.dtype} {tuple(count.shape)}")
+    N.check(N.lib.pnr_video_frames(rgb.data_ptr(), stride, F, W, H, out.data_ptr(), count.data_ptr(), N.current_stream(dev)),
+            "pnr_video_frames")
+    return out.view(F, H, W, 3), count
+
+
+def view_strip(images, scale=0.5, lo=0.5, out=None):
+    """The picture of the source views the reference writes next to a video (eval/gen_video.py:239-241), on the GPU by
+    libpnr_hip (pnr_view_strip): images (NS, 3, H, W) float32 on the device -> (H, NS*W, 3) uint8 =
+    np.hstack of ((x * scale + lo) * 255).astype(np.uint8) over the views, with video_frames' saturation outside numpy's
+    range.  scale = lo = 0.5 for a [-1, 1] input, scale = 1, lo = 0 for [0, 1]."""
+    from . import _native as N
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"images must be a float32 (NS, 3, H, W) tensor, got {getattr(images, 'dtype', None)} "
+                         f"{tuple(getattr(images, 'shape', ()))}")
+    NS, _, H, W = (int(s) for s in images.shape)
+    images = images.contiguous()
+    dev = N.same_device(images, out)
+    if out is None:
+        out = torch.empty(H, NS * W, 3, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (H, NS * W, 3) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 ({H}, {NS * W}, 3), got {out.dtype} {tuple(out.shape)}")
+    N.check(N.lib.pnr_view_strip(images.data_ptr(), NS, W, H, float(scale), float(lo), out.data_ptr(), N.current_stream(dev)),
+            "pnr_view_strip")
+    return out
+
+
+def image_to_tensor(img_u8, balanced=False, device="cuda"):
+    """An 8-bit RGB image (H, W, 3) -> the network's input (3, H, W) float32 on the device, by libpnr_hip
+    (pnr_image_to_tensor).  balanced=False: byte / 255 in [0, 1], torchvision's ToTensor, which is what the reference fork's
+    get_image_to_tensor_balanced does (src/util/util.py:68-79); balanced=True: (byte / 255 - 0.5) / 0.5 in [-1, 1], upstream
+    pixelNeRF's ToTensor + Normalize(0.5, 0.5).  Pinned to torch's own division; parity unpinned against torchvision itself.
+    img_u8: a uint8 device tensor, or a numpy array / host tensor that is uploaded to `device` first."""
+    from . import _native as N
+    if not torch.is_tensor(img_u8):
+        img_u8 = torch.from_numpy(np.ascontiguousarray(img_u8))
+    if img_u8.dim() != 3 or img_u8.shape[2] != 3 or img_u8.dtype != torch.uint8:
+        raise ValueError(f"img_u8 must be uint8 (H, W, 3), got {img_u8.dtype} {tuple(img_u8.shape)}")
+    if not img_u8.is_cuda:
+        img_u8 = upload(img_u8.contiguous(), torch.device(device))
+    img_u8 = img_u8.contiguous()
+    dev = N.same_device(img_u8)
+    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+    out = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+    N.check(N.lib.pnr_image_to_tensor(img_u8.data_ptr(), W, H, int(bool(balanced)), out.data_ptr(), N.current_stream(dev)),
+            "pnr_image_to_tensor")
+    return out
