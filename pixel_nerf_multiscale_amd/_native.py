@@ -250,8 +250,17 @@ def check(rc, what):
         raise PnrError(f"{what}: {msg} (code {rc})")
 
 
+def dptr(t):
+    """Device address of a tensor of any dtype for the C ABI (None -> NULL); dtype and layout are the caller's to check."""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError("libpnr_hip needs tensors on a HIP device (cuda:N); got a CPU tensor")
+    return t.data_ptr()
+
+
 def ptr(t):
-    """Device pointer of a tensor for the C ABI (None -> NULL)."""
+    """dptr of a contiguous float32 (or uint8) tensor; written out flat, it is called several times per render."""
     if t is None:
         return None
     if not t.is_cuda:
@@ -261,6 +270,12 @@ def ptr(t):
     if not t.is_contiguous():
         raise ValueError("tensor must be contiguous")
     return t.data_ptr()
+
+
+def scratch(nbytes, device):
+    """The scratch of one native call that keeps none: max(nbytes, 16) bytes.  torch's allocations are at least 256-byte
+    aligned, which covers the 4- and 8-byte alignment the entry points ask for."""
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
 def f32c(t, device=None):

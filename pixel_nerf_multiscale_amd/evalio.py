@@ -235,11 +235,8 @@ def _render_view(net, renderer, render_par, view_seed, pose, W, H, focal, c, z_n
     """-> (rgb (H, W, 3), depth (H, W)) of one view on the device: ONE renderer.render_image call (looked up here, per call:
     a caller may have wrapped it on the instance), or chunks of ray_batch_size through the sharded wrapper render_par."""
     if render_par is None:
-        keep_seed, renderer.forced_seed = renderer.forced_seed, view_seed
-        try:
+        with renderer.keyed(view_seed):
             return renderer.render_image(net, pose, W, H, focal, z_near, z_far, c=c)
-        finally:
-            renderer.forced_seed = keep_seed
     rays = util.gen_rays_device(pose, W, H, focal, z_near, z_far, c=c, device=net.poses.device)
     parts, at = [], 0
     for r in torch.split(rays, ray_batch_size, dim=0):

@@ -4,6 +4,7 @@ variant — SURVEY.md D3): same constructor / encode / forward / load_weights / 
 state-dict keys.  forward() and the renderer's fused path evaluate the network in libpnr_hip.so.
 """
 import ctypes as C
+import functools
 import os
 import os.path as osp
 import warnings
@@ -187,26 +188,7 @@ class PixelNeRFNet(torch.nn.Module):
         return (mp.data_ptr(), mp._version, tuple(mp.shape), int(self.num_views_per_obj), len(self.encoder.level_maps()))
 
     def _build_mlp_struct(self, mlp, precision, views=None):
-        if mlp.n_blocks > N.PNR_MAX_BLOCKS:
-            raise ValueError(f"ResnetFC with {mlp.n_blocks} blocks: the native library holds at most {N.PNR_MAX_BLOCKS}")
-        m = N.pnr_mlp()
-        m.d_in, m.d_latent, m.d_hidden, m.d_out = mlp.d_in, mlp.d_latent, mlp.d_hidden, mlp.d_out
-        m.n_blocks, m.combine_layer, m.combine_type = mlp.n_blocks, mlp.combine_layer, N.COMBINE[mlp.combine_type]
-        keep = []
-
-        def P(t):
-            t = N.f32c(t.detach())
-            keep.append(t)
-            return N.ptr(t)
-
-        m.lin_in_w, m.lin_in_b = P(mlp.lin_in.weight), P(mlp.lin_in.bias)
-        m.lin_out_w, m.lin_out_b = P(mlp.lin_out.weight), P(mlp.lin_out.bias)
-        for b, blk in enumerate(mlp.blocks):
-            m.fc0_w[b], m.fc0_b[b] = P(blk.fc_0.weight), P(blk.fc_0.bias)
-            m.fc1_w[b], m.fc1_b[b] = P(blk.fc_1.weight), P(blk.fc_1.bias)
-        if mlp.d_latent:
-            for b, lz in enumerate(mlp.lin_z):
-                m.lin_z_w[b], m.lin_z_b[b] = P(lz.weight), P(lz.bias)
+        m, keep = mlp_struct_from(mlp, mlp_tensors(mlp))
         if precision != "fp32":
             proj_bytes, lat_key = 0, None
             if views is not None and self.project_latent:
@@ -436,15 +418,53 @@ def views_from(poses, focal, c, num_views_per_obj, maps, uv_scale=None):
     return v, keep
 
 
+# THE order of an MLP's parameters — the autograd inputs of the training Functions, and the slots of pnr_mlp and of
+# pnr_mlp_grads, which share their field names: (repeated per, ((struct field stem, layer of a ResnetFC), ...))
+MLP_FIELD_TABLE = (
+    (None, (("lin_in", lambda m, b: m.lin_in), ("lin_out", lambda m, b: m.lin_out))),
+    ("block", (("fc0", lambda m, b: m.blocks[b].fc_0), ("fc1", lambda m, b: m.blocks[b].fc_1))),
+    ("lin_z", (("lin_z", lambda m, b: m.lin_z[b]),)),
+)
+
+
+@functools.lru_cache(maxsize=None)
+def mlp_slots(n_blocks, n_lin_z):
+    """MLP_FIELD_TABLE written out for an MLP of n_blocks blocks and n_lin_z lin_z layers: one (struct field, block index or
+    None, layer getter, parameter name) per parameter, in THE order."""
+    reps = {None: (None,), "block": range(n_blocks), "lin_z": range(n_lin_z)}
+    return tuple((stem + sfx, b, layer, par) for per, group in MLP_FIELD_TABLE for b in reps[per] for stem, layer in group
+                 for sfx, par in (("_w", "weight"), ("_b", "bias")))
+
+
+def n_lin_z(mlp):
+    return len(mlp.lin_z) if mlp.d_latent else 0
+
+
 def mlp_tensors(mlp):
-    """The MLP parameters in a fixed order (autograd inputs of the training Functions)."""
-    ts = [mlp.lin_in.weight, mlp.lin_in.bias, mlp.lin_out.weight, mlp.lin_out.bias]
-    for blk in mlp.blocks:
-        ts += [blk.fc_0.weight, blk.fc_0.bias, blk.fc_1.weight, blk.fc_1.bias]
-    if mlp.d_latent:
-        for lz in mlp.lin_z:
-            ts += [lz.weight, lz.bias]
-    return ts
+    """The MLP parameters in THE order (autograd inputs of the training Functions)."""
+    return [getattr(layer(mlp, b), par) for _, b, layer, par in mlp_slots(mlp.n_blocks, n_lin_z(mlp))]
+
+
+def fill_mlp_slots(struct, n_blocks, n_lin_z, ptrs):
+    """struct (a pnr_mlp or a pnr_mlp_grads) <- one address per slot of mlp_slots(n_blocks, n_lin_z), in THE order."""
+    for (field, b, _, _), p in zip(mlp_slots(n_blocks, n_lin_z), ptrs, strict=True):
+        if b is None:
+            setattr(struct, field, p)
+        else:
+            getattr(struct, field)[b] = p
+    return struct
+
+
+def mlp_struct_from(mlp, tensors):
+    """pnr_mlp of the ResnetFC `mlp` over `tensors`, its parameters (or stand-ins for them) in mlp_tensors() order.
+    Returns (struct, keepalive): the float32 contiguous tensors the struct points at, in that order."""
+    if mlp.n_blocks > N.PNR_MAX_BLOCKS:
+        raise ValueError(f"ResnetFC with {mlp.n_blocks} blocks: the native library holds at most {N.PNR_MAX_BLOCKS}")
+    m = N.pnr_mlp()
+    m.d_in, m.d_latent, m.d_hidden, m.d_out = mlp.d_in, mlp.d_latent, mlp.d_hidden, mlp.d_out
+    m.n_blocks, m.combine_layer, m.combine_type = mlp.n_blocks, mlp.combine_layer, N.COMBINE[mlp.combine_type]
+    keep = [N.f32c(t.detach()) for t in tensors]
+    return fill_mlp_slots(m, mlp.n_blocks, n_lin_z(mlp), [N.ptr(t) for t in keep]), keep
 
 
 def mfma_supported(mlp, net):

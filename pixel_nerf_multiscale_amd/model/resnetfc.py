@@ -62,26 +62,8 @@ class ResnetFC(nn.Module):
     def native_struct(self):
         """pnr_mlp over this module's parameter storage (fp32 weights only; the packed MFMA stream is owned by
         PixelNeRFNet.mlp_struct).  Returns (struct, keepalive)."""
-        from .. import _native as N
-        m = N.pnr_mlp()
-        m.d_in, m.d_latent, m.d_hidden, m.d_out = self.d_in, self.d_latent, self.d_hidden, self.d_out
-        m.n_blocks, m.combine_layer, m.combine_type = self.n_blocks, self.combine_layer, N.COMBINE[self.combine_type]
-        keep = []
-
-        def P(t):
-            t = N.f32c(t.detach())
-            keep.append(t)
-            return N.ptr(t)
-
-        m.lin_in_w, m.lin_in_b = P(self.lin_in.weight), P(self.lin_in.bias)
-        m.lin_out_w, m.lin_out_b = P(self.lin_out.weight), P(self.lin_out.bias)
-        for b, blk in enumerate(self.blocks):
-            m.fc0_w[b], m.fc0_b[b] = P(blk.fc_0.weight), P(blk.fc_0.bias)
-            m.fc1_w[b], m.fc1_b[b] = P(blk.fc_1.weight), P(blk.fc_1.bias)
-        if self.d_latent:
-            for b, lz in enumerate(self.lin_z):
-                m.lin_z_w[b], m.lin_z_b[b] = P(lz.weight), P(lz.bias)
-        return m, keep
+        from .models import mlp_struct_from, mlp_tensors
+        return mlp_struct_from(self, mlp_tensors(self))
 
     def forward(self, zx, combine_inner_dims=(1,), combine_index=None, dim_size=None):
         """ResnetFC.forward under the reference's profiler label (resnetfc.py:180)."""

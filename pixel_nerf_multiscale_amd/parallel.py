@@ -30,6 +30,47 @@ def frame_seed(base_seed, frame_idx):
     return (z ^ (z >> 31)) & 0x7FFFFFFFFFFFFFFF
 
 
+class ModelShard:
+    """The render_shard / render_into pair of ShardedRenderer for a NeRFRenderer bound to a net.  The records hold the levels
+    of the renderer's output that the binding returns — simple_output: fine if using_fine else coarse; else every level — as
+    [rgb(3), depth(1), weights(K) if want_weights] each; want_weights is set per call by the owner."""
+
+    def __init__(self, renderer, net, simple_output):
+        self.renderer, self.net, self.simple_output, self.want_weights = renderer, net, simple_output, False
+
+    def levels(self):
+        fine = self.renderer.using_fine
+        if self.simple_output:
+            return ("fine",) if fine else ("coarse",)
+        return ("coarse", "fine") if fine else ("coarse",)
+
+    def widths(self):
+        r, widths = self.renderer, []
+        for lv in self.levels():
+            K = int(r.n_coarse) + (int(r.n_fine) if lv == "fine" else 0)
+            widths += [3, 1] + ([K] if self.want_weights else [])
+        return widths
+
+    def render_shard(self, rays, base, seed, obj_stride=0):
+        """Fallback route (a renderer without packed outputs): returns the per-level tensors, the caller packs them."""
+        with self.renderer.keyed(seed, base, obj_stride):
+            out = self.renderer(self.net, rays, want_weights=self.want_weights)
+        cols = []
+        for lv in self.levels():
+            cols += [out[lv].rgb, out[lv].depth] + ([out[lv].weights] if self.want_weights else [])
+        return cols
+
+    def render_into(self, rays, base, seed, obj_stride, out):
+        """rays (SB, n, 8) -> out (SB, n, sum(widths)), this rank's slice of the gather buffer, written by the render launch
+        itself.  Returns False when this renderer / model pair has no packed route (the caller then uses render_shard)."""
+        from .model.models import PixelNeRFNet
+        if not (isinstance(self.net, PixelNeRFNet) and hasattr(self.renderer, "_forward_fused") and rays.is_cuda):
+            return False
+        with self.renderer.keyed(seed, base, obj_stride):
+            self.renderer.forward_packed(self.net, rays, out, self.levels(), self.want_weights)
+        return True
+
+
 class ShardedRenderer:
     """render_shard(rays (SB, n, 8), ray_index_base, seed[, obj_stride]) -> per-ray outputs of its range is the per-rank
     renderer; __call__(rays (SB, B, 8)) returns the full (rgb (SB,B,3), depth (SB,B)) on every rank.  gather() is the
@@ -60,28 +101,8 @@ class ShardedRenderer:
     @classmethod
     def for_model(cls, renderer, net, **kw):
         """Bind a NeRFRenderer + PixelNeRFNet (simple_output semantics: fine if using_fine else coarse)."""
-        def keyed(base, seed, obj_stride):
-            renderer.ray_index_base, renderer.forced_seed, renderer.ray_index_obj_stride = base, seed, obj_stride
-
-        def render_shard(rays, base, seed, obj_stride=0):
-            keyed(base, seed, obj_stride)
-            try:
-                out = renderer(net, rays)
-            finally:
-                keyed(0, None, 0)
-            lvl = out.fine if renderer.using_fine else out.coarse
-            return lvl.rgb, lvl.depth
-
-        def render_into(rays, base, seed, obj_stride, out):
-            if not (hasattr(renderer, "forward_packed") and rays.is_cuda and hasattr(net, "wants_grad")):
-                return False
-            keyed(base, seed, obj_stride)
-            try:
-                renderer.forward_packed(net, rays, out, ("fine",) if renderer.using_fine else ("coarse",), False)
-            finally:
-                keyed(0, None, 0)
-            return True
-        return cls(render_shard, render_into=render_into, **kw)
+        shard = ModelShard(renderer, net, simple_output=True)
+        return cls(shard.render_shard, render_into=shard.render_into, **kw)
 
     def gather(self, rays, widths, index_base=0, seed=None):
         """rays (SB, B, 8), cut along B: rank k renders rays[:, lo_k:hi_k] of EVERY object (nn.DataParallel(dim=1),

@@ -30,7 +30,7 @@ def extract_mesh(field, iso, origin=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0)):
     if len(origin) != 3 or len(scale) != 3:
         raise ValueError("origin and scale must have 3 entries each")
     nbytes = int(N.lib.pnr_mc_workspace_bytes(nx, ny, nz))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    ws = N.scratch(nbytes, dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     stream = N.current_stream(dev)
     N.check(N.lib.pnr_mc_count(field.data_ptr(), s, nx, ny, nz, float(iso), ws.data_ptr(), nbytes, counts.data_ptr(), stream),

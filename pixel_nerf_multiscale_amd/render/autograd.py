@@ -23,38 +23,17 @@ import ctypes as C
 import torch
 
 from .. import _native as N
-from ..model.models import mlp_tensors, views_from
+from ..model.models import fill_mlp_slots, mlp_struct_from, mlp_tensors, n_lin_z, views_from
 
 
 def _mlp_struct_from(hdr, tensors):
-    """pnr_mlp from the ordered parameter list of models.mlp_tensors()."""
-    m = N.pnr_mlp()
-    m.d_in, m.d_latent, m.d_hidden, m.d_out = hdr["d_in"], hdr["d_latent"], hdr["d_hidden"], hdr["d_out"]
-    m.n_blocks, m.combine_layer, m.combine_type = hdr["n_blocks"], hdr["combine_layer"], N.COMBINE[hdr["combine_type"]]
-    keep = [N.f32c(t.detach()) for t in tensors]
-    it = iter(keep)
-    m.lin_in_w, m.lin_in_b = N.ptr(next(it)), N.ptr(next(it))
-    m.lin_out_w, m.lin_out_b = N.ptr(next(it)), N.ptr(next(it))
-    for b in range(hdr["n_blocks"]):
-        m.fc0_w[b], m.fc0_b[b] = N.ptr(next(it)), N.ptr(next(it))
-        m.fc1_w[b], m.fc1_b[b] = N.ptr(next(it)), N.ptr(next(it))
-    for b in range(hdr["n_lin_z"]):
-        m.lin_z_w[b], m.lin_z_b[b] = N.ptr(next(it)), N.ptr(next(it))
-    return m, keep
+    """pnr_mlp of hdr's module over the ordered parameter list of models.mlp_tensors()."""
+    return mlp_struct_from(hdr["mlp"], tensors)
 
 
 def _grads_struct_from(hdr, grads):
-    g = N.pnr_mlp_grads()
-    it = iter(grads)
-    P = lambda t: None if t is None else t.data_ptr()
-    g.lin_in_w, g.lin_in_b = P(next(it)), P(next(it))
-    g.lin_out_w, g.lin_out_b = P(next(it)), P(next(it))
-    for b in range(hdr["n_blocks"]):
-        g.fc0_w[b], g.fc0_b[b] = P(next(it)), P(next(it))
-        g.fc1_w[b], g.fc1_b[b] = P(next(it)), P(next(it))
-    for b in range(hdr["n_lin_z"]):
-        g.lin_z_w[b], g.lin_z_b[b] = P(next(it)), P(next(it))
-    return g
+    """pnr_mlp_grads over one gradient tensor (or None) per parameter, in the same order."""
+    return fill_mlp_slots(N.pnr_mlp_grads(), hdr["n_blocks"], hdr["n_lin_z"], [N.dptr(t) for t in grads])
 
 
 def _train_params(net):
@@ -85,8 +64,7 @@ class PointMLP(torch.autograd.Function):
         if n_points % v.n_objs:
             raise ValueError("points do not divide evenly over the encoded objects")
         prm = hdr["prm"]
-        tape = torch.empty(int(N.lib.pnr_train_tape_bytes_for(C.byref(prm), C.byref(m), C.byref(v), n_points)), dtype=torch.uint8,
-                           device=dev)
+        tape = N.scratch(N.lib.pnr_train_tape_bytes_for(C.byref(prm), C.byref(m), C.byref(v), n_points), dev)
         out = torch.empty(n_points, 4, device=dev)
         args = (N.ptr(a), N.ptr(b), K, None, None) if rays_mode else (None, None, 0, N.ptr(a), N.ptr(b))
         N.check(N.lib.pnr_point_mlp_train_fwd(C.byref(prm), C.byref(m), C.byref(v), *args, n_points,
@@ -123,17 +101,15 @@ class PointMLP(torch.autograd.Function):
         elif not rays_mode and need[1]:
             d_pos = torch.empty_like(a)
         g = _grads_struct_from(hdr, g_par)
-        dl = (C.c_void_p * N.PNR_MAX_LEVELS)(*[None if t is None else t.data_ptr() for t in g_map])
-        ws = torch.empty(int(N.lib.pnr_train_bwd_workspace_bytes(C.byref(m), C.byref(v), n_points)), dtype=torch.uint8,
-                         device=dev)
+        dl = (C.c_void_p * N.PNR_MAX_LEVELS)(*[N.dptr(t) for t in g_map])
+        ws = N.scratch(N.lib.pnr_train_bwd_workspace_bytes(C.byref(m), C.byref(v), n_points), dev)
         d_out = N.f32c(d_out)
         K = b.shape[1] if rays_mode else 0
         args = (N.ptr(a), N.ptr(b), K, None, None) if rays_mode else (None, None, 0, N.ptr(a), N.ptr(b))
         N.check(N.lib.pnr_point_mlp_bwd(C.byref(hdr["prm"]), C.byref(m), C.byref(v), *args, n_points,
                                         n_points // v.n_objs, N.ptr(out), N.ptr(d_out), tape.data_ptr(), tape.numel(),
                                         C.byref(g), dl,
-                                        None if (rays_mode or d_pos is None) else N.ptr(d_pos),
-                                        N.ptr(d_pos) if (rays_mode and d_pos is not None) else None,
+                                        None if rays_mode else N.ptr(d_pos), N.ptr(d_pos) if rays_mode else None,
                                         ws.data_ptr(), ws.numel(), N.current_stream(dev)), "pnr_point_mlp_bwd")
         g_a = d_pos if not rays_mode else None
         g_b = d_pos if rays_mode else None
@@ -160,13 +136,11 @@ class Composite(torch.autograd.Function):
         rays, z, rgbs = ctx.saved_tensors
         B, K = z.shape
         dev = rays.device
-        P = lambda t: None if t is None else N.ptr(N.f32c(t))
         keep = [None if t is None else N.f32c(t) for t in (d_w, d_rgb, d_depth)]
         d_rgbs = torch.empty_like(rgbs)
         d_z = torch.empty_like(z) if ctx.needs_input_grad[1] else None
         N.check(N.lib.pnr_composite_bwd(N.ptr(rays), N.ptr(z), N.ptr(rgbs), B, K, ctx.white,
-                                        *[None if t is None else N.ptr(t) for t in keep],
-                                        N.ptr(d_rgbs), None if d_z is None else N.ptr(d_z), N.current_stream(dev)),
+                                        *[N.ptr(t) for t in keep], N.ptr(d_rgbs), N.ptr(d_z), N.current_stream(dev)),
                 "pnr_composite_bwd")
         return None, d_z, d_rgbs, None
 
@@ -182,11 +156,11 @@ class SampleFine(torch.autograd.Function):
         B = rays.shape[0]
         z = torch.empty(B, rend.n_coarse + rend.n_fine, device=dev)
         u, r, g = (None if noise is None or noise.get(k) is None else N.f32c(noise[k], dev) for k in ("u", "r", "g"))
-        P = lambda t: None if t is None else N.ptr(t)
         cfg = (int(rend.n_coarse), int(rend.n_fine), int(rend.n_fine_depth), float(rend.depth_std), int(bool(rend.lindisp)),
                int(seed), int(rend.ray_index_base))
         N.check(N.lib.pnr_sample_fine(N.ptr(rays), N.ptr(zc), N.ptr(w), N.ptr(d), B, cfg[0], cfg[1], cfg[2], cfg[3], cfg[4],
-                                      P(u), P(r), P(g), cfg[5], cfg[6], N.ptr(z), N.current_stream(dev)), "pnr_sample_fine")
+                                      N.ptr(u), N.ptr(r), N.ptr(g), cfg[5], cfg[6], N.ptr(z), N.current_stream(dev)),
+                "pnr_sample_fine")
         ctx.cfg = cfg
         ctx.g = g
         ctx.save_for_backward(rays, d, z)
@@ -201,8 +175,8 @@ class SampleFine(torch.autograd.Function):
         d_depth = torch.empty_like(d)
         d_z = N.f32c(d_z)
         N.check(N.lib.pnr_sample_fine_bwd(N.ptr(rays), N.ptr(d), rays.shape[0], Kc, Kf, Kfd, std,
-                                          None if ctx.g is None else N.ptr(ctx.g), seed, base, N.ptr(z), N.ptr(d_z),
-                                          N.ptr(d_depth), N.current_stream(rays.device)), "pnr_sample_fine_bwd")
+                                          N.ptr(ctx.g), seed, base, N.ptr(z), N.ptr(d_z), N.ptr(d_depth),
+                                          N.current_stream(rays.device)), "pnr_sample_fine_bwd")
         return None, None, None, None, d_depth, None, None
 
 
@@ -248,9 +222,7 @@ class RGBLoss(torch.autograd.Function):
 
 # ---------------------------------------------------------------------------------------------------------------
 def _header(net, mlp, rays_mode):
-    return dict(d_in=mlp.d_in, d_latent=mlp.d_latent, d_hidden=mlp.d_hidden, d_out=mlp.d_out, n_blocks=mlp.n_blocks,
-                combine_layer=mlp.combine_layer, combine_type=mlp.combine_type,
-                n_lin_z=len(mlp.lin_z) if mlp.d_latent else 0, n_params=len(mlp_tensors(mlp)),
+    return dict(mlp=mlp, n_blocks=mlp.n_blocks, n_lin_z=n_lin_z(mlp), n_params=len(mlp_tensors(mlp)),
                 n_views=int(net.num_views_per_obj), rays_mode=rays_mode, prm=_train_params(net),
                 uv_scale=net.uv_scales())
 

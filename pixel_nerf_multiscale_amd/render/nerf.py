@@ -45,56 +45,11 @@ class _ShardedRenderWrapper(torch.nn.Module):
 
     def __init__(self, net, renderer, simple_output, group=None):
         super().__init__()
-        from ..parallel import ShardedRenderer
+        from ..parallel import ModelShard, ShardedRenderer
         self.net, self.renderer, self.simple_output = net, renderer, simple_output
         self.local = _RenderWrapper(net, renderer, simple_output)
-        self._want_weights = False
-        self.sharded = ShardedRenderer(self._render_shard, group=group, render_into=self._render_into)
-
-    def _levels(self):
-        r = self.renderer
-        if self.simple_output:
-            return ("fine",) if r.using_fine else ("coarse",)
-        return ("coarse", "fine") if r.using_fine else ("coarse",)
-
-    def _sample_counts(self):
-        r = self.renderer
-        return {"coarse": int(r.n_coarse), "fine": int(r.n_coarse) + int(r.n_fine)}
-
-    def _widths(self):
-        widths = []
-        for lv in self._levels():
-            widths += [3, 1] + ([self._sample_counts()[lv]] if self._want_weights else [])
-        return widths
-
-    def _keyed(self, base, seed, obj_stride):
-        r = self.renderer
-        r.ray_index_base, r.forced_seed, r.ray_index_obj_stride = base, seed, obj_stride
-
-    def _render_shard(self, rays, base, seed, obj_stride=0):
-        """Fallback route (a renderer without packed outputs): returns the per-level tensors, the caller packs them."""
-        self._keyed(base, seed, obj_stride)
-        try:
-            out = self.renderer(self.net, rays, want_weights=self._want_weights)
-        finally:
-            self._keyed(0, None, 0)
-        cols = []
-        for lv in self._levels():
-            cols += [out[lv].rgb, out[lv].depth] + ([out[lv].weights] if self._want_weights else [])
-        return cols
-
-    def _render_into(self, rays, base, seed, obj_stride, out):
-        """rays (SB, n, 8) -> out (SB, n, sum(widths)), this rank's slice of the gather buffer, written by the render launch
-        itself.  Returns False when this renderer / model pair has no packed route (the caller then uses _render_shard)."""
-        from ..model.models import PixelNeRFNet
-        if not (isinstance(self.net, PixelNeRFNet) and hasattr(self.renderer, "_forward_fused") and rays.is_cuda):
-            return False
-        self._keyed(base, seed, obj_stride)
-        try:
-            self.renderer.forward_packed(self.net, rays, out, self._levels(), self._want_weights)
-        finally:
-            self._keyed(0, None, 0)
-        return True
+        self.shard = ModelShard(renderer, net, simple_output)
+        self.sharded = ShardedRenderer(self.shard.render_shard, group=group, render_into=self.shard.render_into)
 
     def forward(self, rays, want_weights=False, ray_index_base=0, seed=None):
         """ray_index_base / seed (this package's drivers only): the call's rays are a chunk of a frame rendered under
@@ -104,17 +59,36 @@ class _ShardedRenderWrapper(torch.nn.Module):
         if getattr(self.net, "wants_grad", None) is not None and self.net.wants_grad(rays):
             return self.local(rays, want_weights)          # training: rank-local, see the class docstring
         # per-sample weights (nested output only, nerf.py:33-41) travel in the same all_gather as rgb and depth
-        self._want_weights = bool(want_weights) and not self.simple_output
-        cols = self.sharded.gather(rays, self._widths(), index_base=ray_index_base, seed=seed)
+        sh = self.shard
+        sh.want_weights = bool(want_weights) and not self.simple_output
+        cols = self.sharded.gather(rays, sh.widths(), index_base=ray_index_base, seed=seed)
         if self.simple_output:
             return cols[0], cols[1]
-        per = 3 if self._want_weights else 2
+        per = 3 if sh.want_weights else 2
         out = {}
-        for i, lv in enumerate(self._levels()):
+        for i, lv in enumerate(sh.levels()):
             out[lv] = {"rgb": cols[per * i], "depth": cols[per * i + 1]}
-            if self._want_weights:
+            if sh.want_weights:
                 out[lv]["weights"] = cols[per * i + 2]
         return out
+
+
+class _Keyed:
+    """NeRFRenderer.keyed's scope.  A plain class that writes the three plain attributes into the renderer's __dict__:
+    a generator and nn.Module.__setattr__'s checks (six of them per scope) cost the host more than the rest of the scope."""
+    __slots__ = ("attrs", "key", "found")
+    NAMES = ("forced_seed", "ray_index_base", "ray_index_obj_stride")
+
+    def __init__(self, rend, seed, base, obj_stride):
+        self.attrs, self.key = rend.__dict__, (seed, base, obj_stride)
+
+    def __enter__(self):
+        d = self.attrs
+        self.found = {k: d[k] for k in self.NAMES}
+        d.update((k, v) for k, v in zip(self.NAMES, self.key) if v is not None or k == "forced_seed")
+
+    def __exit__(self, *exc):
+        self.attrs.update(self.found)
 
 
 class NeRFRenderer(torch.nn.Module):
@@ -156,6 +130,18 @@ class NeRFRenderer(torch.nn.Module):
     def _seed(self):
         self.last_seed = seed_from_torch() if self.forced_seed is None else int(self.forced_seed)
         return self.last_seed
+
+    def keyed(self, seed, base=None, obj_stride=None):
+        """Scope (`with`) whose calls are keyed to a frame: rendered under `seed` (None: drawn from torch's generator) and, where
+        given, as the rays from global index `base` on, `obj_stride` rays per object of the unsharded batch.  Leaving
+        restores forced_seed, ray_index_base and ray_index_obj_stride as they were found, also when the body raises."""
+        return _Keyed(self, seed, base, obj_stride)
+
+    def _apply_sched(self):
+        """The sample counts of the schedule stage a loaded state is in (nerf.py:265-267)."""
+        if self.sched is not None and self.last_sched.item() > 0:
+            stage = self.last_sched.item() - 1
+            self.n_coarse, self.n_fine = self.sched[1][stage], self.sched[2][stage]
 
     def sample_coarse(self, rays, seed=None):
         """rays (B,8) -> z (B,Kc): stratified, jittered in eval too (nerf.py:98-118)."""
@@ -226,9 +212,7 @@ class NeRFRenderer(torch.nn.Module):
             return self._forward_impl(model, rays, want_weights)
 
     def _forward_impl(self, model, rays, want_weights=False):
-        if self.sched is not None and self.last_sched.item() > 0:
-            self.n_coarse = self.sched[1][self.last_sched.item() - 1]
-            self.n_fine = self.sched[2][self.last_sched.item() - 1]
+        self._apply_sched()
         assert len(rays.shape) == 3
         if not rays.is_cuda:
             raise RuntimeError("NeRFRenderer runs on the HIP device only: move rays (and the model) to cuda")
@@ -248,23 +232,21 @@ class NeRFRenderer(torch.nn.Module):
         """forward() of a PixelNeRFNet with the outputs of `levels` written as ONE record per ray into out (SB, B, tot):
         per level [rgb(3), depth(1), weights(K) if want_weights] — by the render launch itself (pnr_outputs strides).
         What parallel.ShardedRenderer hands its rank's slice of the all_gather buffer to."""
-        if self.sched is not None and self.last_sched.item() > 0:
-            self.n_coarse = self.sched[1][self.last_sched.item() - 1]
-            self.n_fine = self.sched[2][self.last_sched.item() - 1]
+        self._apply_sched()
         if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape[:2] == rays.shape[:2]):
             raise ValueError("packed output must be a contiguous float32 (SB, B, tot) tensor on the rays' device")
         return self._forward_fused(net, rays, want_weights, packed=(out, tuple(levels)))
 
     def _forward_fused(self, net, rays, want_weights, camera=None, packed=None):
-        """rays (SB, B, 8) through pnr_render; or, with rays=None, the pixels of `camera` = (c2w 16 floats, W, H, fx, fy,
-        cx, cy, z_near, z_far, pix0, n) through pnr_render_camera (rays generated inside the render launch).
+        """rays (SB, B, 8) through pnr_render; or, with rays=None, the pixels of `camera` (a util.Camera, see util.camera)
+        through pnr_render_camera (rays generated inside the render launch).
         packed = (out (SB, B, tot), levels): see forward_packed."""
         if camera is None:
             SB, B, _ = rays.shape
             dev = N.same_device(rays, net.poses)
             rays_f = N.f32c(rays).reshape(-1, 8)
         else:
-            SB, B = 1, int(camera[10])
+            SB, B = 1, camera.n
             dev = net.poses.device
         n = SB * B
         Kc, Kf = int(self.n_coarse), int(self.n_fine) if self.using_fine else 0
@@ -279,42 +261,32 @@ class NeRFRenderer(torch.nn.Module):
         mf, k2 = net.mlp_struct(fine_mod, prec_c, v) if fine_mod is not None else (None, [])
         if v.n_objs != SB:
             raise ValueError(f"rays has {SB} objects but encode() saw {v.n_objs}")
-        o = N.pnr_outputs()
-        if packed is not None:
-            # one record per ray in the caller's buffer: the members of pnr_outputs point INTO it, with the record length as
-            # their row stride; levels that are not asked for stay NULL (the library keeps them in its workspace)
-            buf, levels = packed
-            tot, base, off = buf.shape[-1], buf.data_ptr(), 0
-            res = AttrDict()
-            for lv in levels:
-                if lv == "fine" and Kf == 0:
-                    raise ValueError("packed level 'fine' but the renderer has no fine pass")
-                K = Kc if lv == "coarse" else Kc + Kf
-                res[lv] = AttrDict(rgb=buf[..., off:off + 3], depth=buf[..., off + 3])
-                setattr(o, lv + "_rgb", base + 4 * off)
-                setattr(o, lv + "_depth", base + 4 * (off + 3))
-                off += 4
-                if want_weights:
-                    res[lv].weights = buf[..., off:off + K]
-                    setattr(o, lv + "_weights", base + 4 * off)
-                    off += K
+        # dense: one tensor per (level, member); packed: one record per ray in the caller's buffer, the members of pnr_outputs
+        # point INTO it with the record length as their row stride, and levels that are not asked for stay NULL (the library
+        # keeps them in its workspace)
+        buf, levels = packed if packed is not None else (None, ("coarse", "fine") if Kf > 0 else ("coarse",))
+        o, res, off = N.pnr_outputs(), AttrDict(), 0
+        for lv in levels:
+            if lv == "fine" and Kf == 0:
+                raise ValueError("packed level 'fine' but the renderer has no fine pass")
+            r = res[lv] = AttrDict()
+            members = (("rgb", 3), ("depth", 0), ("weights", Kc if lv == "coarse" else Kc + Kf))       # width 0: no last dim
+            for member, w in members[:3 if want_weights else 2]:
+                if buf is None:
+                    t = torch.empty(SB, B, w, device=dev) if w else torch.empty(SB, B, device=dev)
+                    setattr(o, lv + "_" + member, N.ptr(t))
+                else:
+                    t = buf[..., off:off + w] if w else buf[..., off]
+                    setattr(o, lv + "_" + member, buf.data_ptr() + 4 * off)
+                    off += w or 1
+                r[member] = t
+        if buf is not None:
+            tot = buf.shape[-1]
             if off != tot:
                 raise ValueError(f"packed record of {tot} floats, the levels {levels} need {off}")
             o.rgb_stride = o.depth_stride = o.coarse_weights_stride = o.fine_weights_stride = tot
             if Kf > 0 and "fine" not in levels:         # pnr_render needs somewhere to put the fine pixels
                 raise ValueError("a renderer with a fine pass packs its fine level (simple_output picks it)")
-        else:
-            res = AttrDict(coarse=AttrDict(rgb=torch.empty(SB, B, 3, device=dev), depth=torch.empty(SB, B, device=dev)))
-            o.coarse_rgb, o.coarse_depth = N.ptr(res.coarse.rgb), N.ptr(res.coarse.depth)
-            if want_weights:
-                res.coarse.weights = torch.empty(SB, B, Kc, device=dev)
-                o.coarse_weights = N.ptr(res.coarse.weights)
-            if Kf > 0:
-                res.fine = AttrDict(rgb=torch.empty(SB, B, 3, device=dev), depth=torch.empty(SB, B, device=dev))
-                o.fine_rgb, o.fine_depth = N.ptr(res.fine.rgb), N.ptr(res.fine.depth)
-                if want_weights:
-                    res.fine.weights = torch.empty(SB, B, Kc + Kf, device=dev)
-                    o.fine_weights = N.ptr(res.fine.weights)
         if getattr(self, "keep_samples", False) and packed is None:
             res.coarse.z = torch.empty(SB, B, Kc, device=dev)
             o.z_coarse = N.ptr(res.coarse.z)
@@ -334,11 +306,9 @@ class NeRFRenderer(torch.nn.Module):
                                      N.ptr(rays_f), n, B, C.byref(nz), self._seed(), int(self.ray_index_base), C.byref(o),
                                      ws.data_ptr(), ws.numel(), N.current_stream(dev)), "pnr_render")
         else:
-            m, W, H, fx, fy, cx, cy, zn, zf, pix0, _ = camera
             N.check(N.lib.pnr_render_camera(C.byref(prm), C.byref(mc), C.byref(mf) if mf is not None else None, C.byref(v),
-                                            (C.c_float * 16)(*m), W, H, fx, fy, cx, cy, zn, zf, pix0, n, C.byref(nz),
-                                            self._seed(), int(self.ray_index_base), C.byref(o), ws.data_ptr(), ws.numel(),
-                                            N.current_stream(dev)), "pnr_render_camera")
+                                            *camera.c_args(), C.byref(nz), self._seed(), int(self.ray_index_base), C.byref(o),
+                                            ws.data_ptr(), ws.numel(), N.current_stream(dev)), "pnr_render_camera")
         return res
 
     def _forward_generic(self, model, rays, want_weights):
@@ -369,16 +339,8 @@ class NeRFRenderer(torch.nn.Module):
             rays = util.gen_rays_device(pose, width, height, focal, z_near, z_far, c=c, device=dev)
             out = self(net, rays[None])
         else:
-            if self.sched is not None and self.last_sched.item() > 0:
-                self.n_coarse = self.sched[1][self.last_sched.item() - 1]
-                self.n_fine = self.sched[2][self.last_sched.item() - 1]
-            f = torch.as_tensor(focal, dtype=torch.float32).flatten()
-            cc = None if c is None else torch.as_tensor(c, dtype=torch.float32).flatten()
-            cx, cy = (width * 0.5, height * 0.5) if cc is None else (float(cc[0]), float(cc[1]))
-            m = [float(x) for x in torch.as_tensor(pose, dtype=torch.float32).cpu().flatten().tolist()]
-            cam = (m, int(width), int(height), float(f[0]), float(f[-1]), cx, cy, float(z_near), float(z_far), 0,
-                   int(width) * int(height))
-            out = self._forward_fused(net, None, False, camera=cam)
+            self._apply_sched()
+            out = self._forward_fused(net, None, False, camera=util.camera(pose, width, height, focal, z_near, z_far, c=c))
         lvl = out.fine if self.using_fine else out.coarse
         return lvl.rgb.reshape(height, width, 3), lvl.depth.reshape(height, width)
 

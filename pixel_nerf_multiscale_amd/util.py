@@ -5,6 +5,7 @@ imports; the implementations are this package's own.
 """
 import ctypes as C
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -131,15 +132,37 @@ def quat_to_rot(q):
     return torch.stack([torch.stack(row, dim=-1) for row in rows], dim=1)
 
 
+def intrinsics(focal, c, W, H):
+    """(fx, fy, cx, cy) as host floats: focal a scalar or (fx, fy), c = (cx, cy) or None for the image centre (W/2, H/2)."""
+    f = torch.as_tensor(focal, dtype=torch.float32).flatten()
+    if c is None:
+        return float(f[0]), float(f[-1]), W * 0.5, H * 0.5
+    c = torch.as_tensor(c, dtype=torch.float32).flatten()
+    return float(f[0]), float(f[-1]), float(c[0]), float(c[1])
+
+
+class Camera(namedtuple("Camera", "c2w16 W H fx fy cx cy z_near z_far pix0 n")):
+    """The camera of a fused render, host values only: c2w as 16 floats row-major, the image size, the intrinsics, the depth
+    range, and the pixels [pix0, pix0 + n) of the W x H image that the call renders."""
+    __slots__ = ()
+
+    def c_args(self):
+        """The camera arguments of pnr_render_camera and pnr_gen_rays, in the order both take them."""
+        return ((C.c_float * 16)(*self.c2w16), self.W, self.H, self.fx, self.fy, self.cx, self.cy, self.z_near, self.z_far,
+                self.pix0, self.n)
+
+
+def camera(pose, W, H, focal, z_near, z_far, c=None, pix0=0, n=None):
+    """Camera from a (4, 4) camera-to-world pose (tensor, array or nested list) and the intrinsics as intrinsics() takes
+    them; n=None: the whole image."""
+    W, H = int(W), int(H)
+    return Camera(torch.as_tensor(pose, dtype=torch.float32).cpu().flatten().tolist(), W, H, *intrinsics(focal, c, W, H),
+                  float(z_near), float(z_far), int(pix0), W * H if n is None else int(n))
+
+
 def unproj_map(width, height, f, c=None, device="cpu"):
     """(H, W, 3) unit camera-space ray directions of a pinhole camera (reference util.py:118-148)."""
-    if c is None:
-        cx, cy = width * 0.5, height * 0.5
-    else:
-        c = torch.as_tensor(c).flatten()
-        cx, cy = float(c[0]), float(c[1])
-    f = torch.as_tensor(f, dtype=torch.float32).flatten()
-    fx, fy = float(f[0]), float(f[-1])
+    fx, fy, cx, cy = intrinsics(f, c, width, height)
     ys = (torch.arange(height, dtype=torch.float32, device=device) - cy) / fy
     xs = (torch.arange(width, dtype=torch.float32, device=device) - cx) / fx
     Y, X = torch.meshgrid(ys, xs, indexing="ij")
@@ -188,14 +211,10 @@ def gen_rays_device(pose, width, height, focal, z_near, z_far, c=None, device="c
     """gen_rays for ONE camera, computed on the GPU by libpnr_hip (pnr_gen_rays): pose (4,4) c2w on the host ->
     rays (H*W, 8) on `device`, never materialised on the host."""
     from . import _native as N
-    f = torch.as_tensor(focal, dtype=torch.float32).flatten()
-    fx, fy = float(f[0]), float(f[-1])
-    cx, cy = (width * 0.5, height * 0.5) if c is None else (float(torch.as_tensor(c).flatten()[0]), float(torch.as_tensor(c).flatten()[1]))
+    cam = camera(pose, width, height, focal, z_near, z_far, c=c)
     dev = torch.device(device)
-    out = torch.empty(width * height, 8, device=dev, dtype=torch.float32)
-    m = (C.c_float * 16)(*[float(v) for v in torch.as_tensor(pose, dtype=torch.float32).cpu().flatten().tolist()])
-    N.check(N.lib.pnr_gen_rays(m, int(width), int(height), fx, fy, cx, cy, float(z_near), float(z_far), 0,
-                               width * height, N.ptr(out), N.current_stream(dev)), "pnr_gen_rays")
+    out = torch.empty(cam.n, 8, device=dev, dtype=torch.float32)
+    N.check(N.lib.pnr_gen_rays(*cam.c_args(), N.ptr(out), N.current_stream(dev)), "pnr_gen_rays")
     return out
 
 
@@ -223,7 +242,7 @@ def gen_grid_device(c1, c2, reso, first=0, count=None, fake_viewdirs=False, devi
     dirs = torch.empty_like(xyz) if fake_viewdirs else None
     N.check(N.lib.pnr_grid_points((C.c_double * 3)(*[float(v) for v in c1]), (C.c_double * 3)(*[float(v) for v in c2]),
                                   (C.c_int32 * 3)(*reso), int(first), count, int(bool(fake_viewdirs)), xyz.data_ptr(),
-                                  None if dirs is None else dirs.data_ptr(), N.current_stream(dev)), "pnr_grid_points")
+                                  N.dptr(dirs), N.current_stream(dev)), "pnr_grid_points")
     return (xyz, dirs) if fake_viewdirs else xyz
 
 
@@ -300,16 +319,6 @@ def _record_stride(t, lead, last, name):
     return s
 
 
-def _workspace(nbytes, dev):
-    """The scratch of one native call: max(nbytes, 16) bytes.  torch's allocations are at least 256-byte aligned, which
-    covers the 4- and 8-byte alignment the entry points ask for."""
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-
-
-def _dp(t):
-    return None if t is None else t.data_ptr()
-
-
 def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True, want_compare=False, want_depth=False,
                want_metrics=True, metrics_out=None):
     """What the evaluation loop does with a rendered frame (eval/eval.py:286-347), on the GPU by libpnr_hip (pnr_eval_frame):
@@ -347,10 +356,10 @@ def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True,
         if tuple(metrics.shape) != (2,) or metrics.dtype != torch.float64 or not metrics.is_contiguous():
             raise ValueError(f"metrics_out must be a contiguous float64 (2,), got {metrics.dtype} {tuple(metrics.shape)}")
         nbytes = int(N.lib.pnr_eval_frame_workspace_bytes(W, H))
-        ws = _workspace(nbytes, dev)
-    N.check(N.lib.pnr_eval_frame(rgb.data_ptr(), rs, _dp(depth), ds, _dp(gt), W, H, float(z_near), float(z_far), _dp(rgb_u8),
-                                 _dp(compare_u8), _dp(depth_norm), _dp(metrics), _dp(ws), nbytes, N.current_stream(dev)),
-            "pnr_eval_frame")
+        ws = N.scratch(nbytes, dev)
+    N.check(N.lib.pnr_eval_frame(rgb.data_ptr(), rs, N.dptr(depth), ds, N.dptr(gt), W, H, float(z_near), float(z_far),
+                                 N.dptr(rgb_u8), N.dptr(compare_u8), N.dptr(depth_norm), N.dptr(metrics), N.dptr(ws), nbytes,
+                                 N.current_stream(dev)), "pnr_eval_frame")
     return rgb_u8, compare_u8, depth_norm, metrics
 
 
@@ -379,8 +388,7 @@ class _UpsampleConcat(torch.autograd.Function):
             ptrs = (C.c_void_p * len(levels))(*[N.ptr(l) for l in levels])
             dt = N.PNR_F32 if half_dtype is None else (N.PNR_F16 if half_dtype == torch.float16 else N.PNR_BF16)
             N.check(N.lib.pnr_upsample_concat(ptrs, lat_c, lat_h, lat_w, len(levels), n, N.ptr(out),
-                                              None if out16 is None else out16.data_ptr(), dt, N.current_stream(dev)),
-                    "pnr_upsample_concat")
+                                              N.dptr(out16), dt, N.current_stream(dev)), "pnr_upsample_concat")
         ctx.shapes, ctx.device = shapes, dev
         if out16 is None:
             return out
@@ -395,7 +403,7 @@ class _UpsampleConcat(torch.autograd.Function):
                  for s, need in zip(shapes, ctx.needs_input_grad[1:])]
         if shapes[0][0] > 0 and any(g is not None for g in grads):
             lat_c, lat_h, lat_w = _upsample_sizes(shapes)
-            ptrs = (C.c_void_p * len(shapes))(*[None if g is None else g.data_ptr() for g in grads])
+            ptrs = (C.c_void_p * len(shapes))(*[N.dptr(g) for g in grads])
             d_out = N.f32c(d_out)
             N.check(N.lib.pnr_upsample_concat_bwd(N.ptr(d_out), lat_c, lat_h, lat_w, len(shapes), shapes[0][0], ptrs,
                                                   N.current_stream(dev)), "pnr_upsample_concat_bwd")
@@ -495,7 +503,7 @@ def cmap_device(map, lut=None):
     u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
     minmax = torch.empty(2, dtype=torch.float32, device=dev)
     nbytes = int(N.lib.pnr_cmap_workspace_bytes(W, H))
-    ws = _workspace(nbytes, dev)
+    ws = N.scratch(nbytes, dev)
     N.check(N.lib.pnr_cmap(map.data_ptr(), stride, W, H, lut.data_ptr(), u8.data_ptr(), minmax.data_ptr(), ws.data_ptr(),
                            nbytes, N.current_stream(dev)), "pnr_cmap")
     return u8, minmax
@@ -548,10 +556,10 @@ def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, wa
     stats = torch.empty(n_pass, 6, dtype=torch.float32, device=dev)
     mse = torch.empty((), dtype=torch.float64, device=dev)
     nbytes = int(N.lib.pnr_vis_panel_workspace_bytes(W, H, n_pass))
-    ws = _workspace(nbytes, dev)
+    ws = N.scratch(nbytes, dev)
     N.check(N.lib.pnr_vis_panel(images.data_ptr(), NV, (C.c_int32 * NS)(*src), NS, int(gt_view), arr, n_pass, W, H,
-                                lut.data_ptr(), _dp(panel), _dp(panel_u8), _dp(alpha), stats.data_ptr(), mse.data_ptr(),
-                                ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_vis_panel")
+                                lut.data_ptr(), N.dptr(panel), N.dptr(panel_u8), N.dptr(alpha), stats.data_ptr(),
+                                mse.data_ptr(), ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_vis_panel")
     return VisPanel(panel, panel_u8, alpha, stats, mse, -10.0 * torch.log10(mse))
 
 

@@ -92,33 +92,25 @@ def render_video(net, renderer, poses, W, H, focal, z_near, z_far, c=None, seed=
     HW = H * W
     seed = util.seed_from_torch() if seed is None else int(seed)
     dev = net.poses.device
-    keep_seed = renderer.forced_seed
-    try:
-        with torch.no_grad():
-            if isinstance(net, PixelNeRFNet) and net.num_objs == 1 and not net.wants_grad(net.poses):
-                if renderer.sched is not None and renderer.last_sched.item() > 0:
-                    renderer.n_coarse = renderer.sched[1][renderer.last_sched.item() - 1]
-                    renderer.n_fine = renderer.sched[2][renderer.last_sched.item() - 1]
-                f = torch.as_tensor(focal, dtype=torch.float32).flatten()
-                cc = None if c is None else torch.as_tensor(c, dtype=torch.float32).flatten()
-                cx, cy = (W * 0.5, H * 0.5) if cc is None else (float(cc[0]), float(cc[1]))
-                level = ("fine",) if renderer.using_fine else ("coarse",)
-                record = torch.empty(F * HW, 4, device=dev, dtype=torch.float32)
-                for i in range(F):
-                    cam = ([float(x) for x in poses[i].flatten().tolist()], W, H, float(f[0]), float(f[-1]), cx, cy,
-                           float(z_near), float(z_far), 0, HW)
-                    renderer.forced_seed = frame_seed(seed, i)
-                    renderer._forward_fused(net, None, False, camera=cam, packed=(record[i * HW:(i + 1) * HW].view(1, HW, 4), level))
-                rgb = record[:, :3]
-            else:
-                frames = []
-                for i in range(F):
-                    renderer.forced_seed = frame_seed(seed, i)
+    with torch.no_grad():
+        if isinstance(net, PixelNeRFNet) and net.num_objs == 1 and not net.wants_grad(net.poses):
+            renderer._apply_sched()
+            fx, fy, cx, cy = util.intrinsics(focal, c, W, H)          # read once: focal and c may live on the device
+            level = ("fine",) if renderer.using_fine else ("coarse",)
+            record = torch.empty(F * HW, 4, device=dev, dtype=torch.float32)
+            for i in range(F):
+                cam = util.camera(poses[i], W, H, (fx, fy), z_near, z_far, c=(cx, cy))
+                with renderer.keyed(frame_seed(seed, i)):
+                    renderer._forward_fused(net, None, False, camera=cam,
+                                            packed=(record[i * HW:(i + 1) * HW].view(1, HW, 4), level))
+            rgb = record[:, :3]
+        else:
+            frames = []
+            for i in range(F):
+                with renderer.keyed(frame_seed(seed, i)):
                     frames.append(renderer.render_image(net, poses[i], W, H, focal, z_near, z_far, c=c)[0])
-                rgb = torch.stack(frames, 0).contiguous()
-            return util.video_frames(rgb, F, H, W)
-    finally:
-        renderer.forced_seed = keep_seed
+            rgb = torch.stack(frames, 0).contiguous()
+        return util.video_frames(rgb, F, H, W)
 
 
 # ----------------------------------------------------------------------------------------------------------- the drivers

@@ -133,6 +133,7 @@ def test_whole_path_draws_equal_the_model(name, prec, n_rays):
     """pnr_render (the stages in sequence in fp32, the fused launch in bf16) and pnr_render_camera with pix0 > 0: positions,
     colours and depths with the in-kernel generator are bit-identical to the same call fed the model's noise_c, u, r."""
     from hip_util import setup
+    from pixel_nerf_multiscale_amd import util
     fx, spec, net, rend = setup(name, precision=prec)
     W, H = spec["image"]
     pix = torch.randperm(W * H, generator=torch.Generator().manual_seed(n_rays))[:n_rays].numpy()
@@ -143,8 +144,8 @@ def test_whole_path_draws_equal_the_model(name, prec, n_rays):
         _both(rend, lambda: rend(net, rays), seed, su.global_ray(base, n_rays), (name, "render", seed, base))
         # rays of one camera, generated in the launch: pixels pix0 .. pix0 + n of a 24 x 17 image
         pix0, n = 37, 131
-        m = [float(x) for x in torch.from_numpy(tgt).flatten().tolist()]
-        cam = (m, 24, 17, spec["focal"], spec["focal"] * 1.1, 12.0, 8.5, spec["z_near"], spec["z_far"], pix0, n)
+        cam = util.camera(tgt, 24, 17, (spec["focal"], spec["focal"] * 1.1), spec["z_near"], spec["z_far"], c=(12.0, 8.5),
+                          pix0=pix0, n=n)
         _both(rend, lambda: rend._forward_fused(net, None, False, camera=cam), seed, su.global_ray(base, n),
               (name, "camera", seed, base))
     rend.ray_index_base = 0

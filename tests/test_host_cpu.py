@@ -172,6 +172,7 @@ def test_training_and_projection_switches_host_logic():
     marks = [object() for _ in ts]
 
     class P:     # stand-in with a data_ptr, so the slot mapping can be checked without device memory
+        is_cuda = True
         def __init__(self, i): self.i = i
         def data_ptr(self): return 1000 + self.i
     g = ag._grads_struct_from(hdr, [P(i) for i in range(len(ts))])
@@ -319,3 +320,121 @@ def test_train_tape_bytes_are_pinned():
     assert len(got) == len(_TAPE_BYTES) == 540
     wrong = [(cfg, v, want) for (cfg, v), want in zip(got, _TAPE_BYTES) if v != want]
     assert not wrong, wrong[:5]
+
+
+# ----------------------------------------------------------------------------- the host layer of a render call
+_POSE = [[1.0, 0.0, 0.0, 0.5], [0.0, 0.0, -1.0, 2.0], [0.0, 1.0, 0.0, -0.25], [0.0, 0.0, 0.0, 1.0]]
+_POSE16 = [1.0, 0.0, 0.0, 0.5, 0.0, 0.0, -1.0, 2.0, 0.0, 1.0, 0.0, -0.25, 0.0, 0.0, 0.0, 1.0]
+
+
+@pytest.mark.parametrize("pose", [torch.tensor(_POSE), np.array(_POSE), np.array(_POSE, dtype=np.float32), _POSE],
+                         ids=["tensor", "float64 array", "float32 array", "nested list"])
+def test_camera_record_is_the_tuple_the_call_sites_built(pose):
+    """util.camera against the 11 values render_image, render_video and the sampler test spelled out by hand: (fx, fy) and
+    scalar focal, a given principal point and the image centre, a pixel range and the whole image."""
+    from pixel_nerf_multiscale_amd import util
+    cam = util.camera(pose, 24, 17, (30.0, 33.0), 1.25, 2.75, c=(12.0, 8.5), pix0=37, n=131)
+    assert cam == (_POSE16, 24, 17, 30.0, 33.0, 12.0, 8.5, 1.25, 2.75, 37, 131)
+    whole = (_POSE16, 24, 17, 30.0, 30.0, 12.0, 8.5, 1.25, 2.75, 0, 408)
+    assert util.camera(pose, 24, 17, 30.0, 1.25, 2.75) == whole                                 # c=None: (W / 2, H / 2); n=None: W H
+    assert util.camera(pose, 24.0, 17.0, torch.tensor([30.0]), np.float32(1.25), 2.75, c=None, n=None) == whole
+    assert util.camera(pose, 24, 17, torch.tensor([[30.0, 33.0]]), 1.25, 2.75, c=np.array([[12.0, 8.5]]))[3:7] == (30.0, 33.0, 12.0, 8.5)
+    assert (cam.c2w16, cam.W, cam.H, cam.fx, cam.fy, cam.cx, cam.cy, cam.z_near, cam.z_far, cam.pix0, cam.n) == tuple(cam)
+    # host values only: nothing in the record is a tensor, so building it cannot touch a device
+    assert [type(v) for v in cam] == [list, int, int, float, float, float, float, float, float, int, int]
+    assert all(type(x) is float for x in cam.c2w16)
+    args = cam.c_args()
+    assert list(args[0]) == _POSE16 and args[1:] == tuple(cam)[1:]
+
+
+@pytest.mark.parametrize("focal,c,want", [((30.0, 33.0), (12.0, 8.5), (30.0, 33.0, 12.0, 8.5)), (30.0, None, (30.0, 30.0, 12.0, 8.5)),
+                                          ((30.0, 33.0), (11.25, 9.0), (30.0, 33.0, 11.25, 9.0))])
+def test_intrinsics_are_what_unproj_map_uses(focal, c, want):
+    """util.intrinsics is the parse, and unproj_map's directions are to the bit those of the parse written out by hand."""
+    from pixel_nerf_multiscale_amd import util
+    W, H = 24, 17
+    assert util.intrinsics(focal, c, W, H) == want
+    assert util.intrinsics(torch.tensor(focal), None if c is None else np.array(c), W, H) == want
+    fx, fy, cx, cy = want
+    ys = (torch.arange(H, dtype=torch.float32) - cy) / fy
+    xs = (torch.arange(W, dtype=torch.float32) - cx) / fx
+    Y, X = torch.meshgrid(ys, xs, indexing="ij")
+    d = torch.stack((X, -Y, -torch.ones_like(X)), dim=-1)
+    assert torch.equal(util.unproj_map(W, H, focal, c=c), d / d.norm(dim=-1, keepdim=True))
+
+
+@pytest.mark.parametrize("d_latent", [8, 0])
+def test_mlp_field_table_is_the_one_order(d_latent):
+    """The slots of models.mlp_slots: as many as mlp_tensors() gives parameters, each a field of pnr_mlp AND of pnr_mlp_grads,
+    and in mlp_tensors' order — lin_in, lin_out, per block fc_0 and fc_1, then lin_z."""
+    from pixel_nerf_multiscale_amd import _native as N
+    from pixel_nerf_multiscale_amd.model import ResnetFC
+    from pixel_nerf_multiscale_amd.model import models as M
+    mlp = ResnetFC(42, n_blocks=3, d_latent=d_latent, d_hidden=32, combine_layer=2)
+    n_z = 2 if d_latent else 0
+    assert M.n_lin_z(mlp) == n_z
+    slots = M.mlp_slots(mlp.n_blocks, n_z)
+    ts = M.mlp_tensors(mlp)
+    want = [mlp.lin_in.weight, mlp.lin_in.bias, mlp.lin_out.weight, mlp.lin_out.bias]
+    for blk in mlp.blocks:
+        want += [blk.fc_0.weight, blk.fc_0.bias, blk.fc_1.weight, blk.fc_1.bias]
+    for b in range(n_z):
+        want += [mlp.lin_z[b].weight, mlp.lin_z[b].bias]
+    assert len(slots) == len(ts) == len(want) == 4 + 4 * 3 + 2 * n_z and all(a is b for a, b in zip(ts, want))
+    for struct_t in (N.pnr_mlp, N.pnr_mlp_grads):
+        fields = dict(struct_t._fields_)
+        for field, b, _, _ in slots:
+            assert field in fields and (b is None) == (fields[field] is ctypes.c_void_p), (struct_t.__name__, field, b)
+        st = M.fill_mlp_slots(struct_t(), mlp.n_blocks, n_z, range(1, len(ts) + 1))
+        assert [getattr(st, f) if b is None else getattr(st, f)[b] for f, b, _, _ in slots] == list(range(1, len(ts) + 1))
+        assert (st.lin_in_w, st.lin_out_b, st.fc0_w[0], st.fc1_b[2]) == (1, 4, 5, 16)
+        assert (st.lin_z_w[0], st.lin_z_b[1]) == ((17, 20) if d_latent else (None, None))
+        with pytest.raises(ValueError):
+            M.fill_mlp_slots(struct_t(), mlp.n_blocks, n_z, range(len(ts) - 1))       # one address short: an error, not a shift
+
+
+def test_keyed_scope_restores_what_it_found():
+    from pixel_nerf_multiscale_amd import NeRFRenderer
+    r = NeRFRenderer()
+    assert (r.forced_seed, r.ray_index_base, r.ray_index_obj_stride) == (None, 0, 0)
+    with r.keyed(11, 5, 7):
+        assert (r.forced_seed, r.ray_index_base, r.ray_index_obj_stride) == (11, 5, 7)
+    assert (r.forced_seed, r.ray_index_base, r.ray_index_obj_stride) == (None, 0, 0)
+    r.forced_seed, r.ray_index_base, r.ray_index_obj_stride = 3, 100, 400                       # prior values that are no defaults
+    with r.keyed(12):                                                                           # a seed alone leaves the ray key
+        assert (r.forced_seed, r.ray_index_base, r.ray_index_obj_stride) == (12, 100, 400)
+        with r.keyed(None, 0, 0):
+            assert (r.forced_seed, r.ray_index_base, r.ray_index_obj_stride) == (None, 0, 0)
+        assert (r.forced_seed, r.ray_index_base, r.ray_index_obj_stride) == (12, 100, 400)
+    assert (r.forced_seed, r.ray_index_base, r.ray_index_obj_stride) == (3, 100, 400)
+    with pytest.raises(KeyError):
+        with r.keyed(13, 1, 2):
+            r.forced_seed = 99                                                                  # the body may set them too
+            raise KeyError("from the body")
+    assert (r.forced_seed, r.ray_index_base, r.ray_index_obj_stride) == (3, 100, 400)
+
+
+def test_apply_sched_leaves_the_counts_of_the_stage():
+    """_apply_sched on a renderer whose state says which stage it is in (a loaded checkpoint): the counts that sched_step
+    leaves in test_renderer_surface_and_schedule."""
+    from pixel_nerf_multiscale_amd import NeRFRenderer
+    conf = dict(n_coarse=64, n_fine=32, n_fine_depth=16, sched=[[2, 4], [16, 32], [8, 16]])
+    for stage, want in ((0, (64, 32)), (1, (16, 8)), (2, (32, 16))):
+        r = NeRFRenderer.from_conf(conf)
+        r.last_sched.fill_(stage)
+        r._apply_sched()
+        assert (r.n_coarse, r.n_fine) == want
+    d = NeRFRenderer(n_coarse=48)
+    d._apply_sched()                                                                            # no schedule: nothing changes
+    assert (d.n_coarse, d.n_fine) == (48, 0)
+
+
+def test_dptr_takes_any_dtype_on_the_device_only():
+    from pixel_nerf_multiscale_amd import _native as N
+    assert N.dptr(None) is None and N.ptr(None) is None
+    for dt in (torch.float32, torch.int64, torch.uint8, torch.float16):
+        with pytest.raises(RuntimeError):
+            N.dptr(torch.zeros(3, dtype=dt))          # CPU tensors never reach the library
+    with pytest.raises(RuntimeError):
+        N.dptr(N.scratch(8, "cpu"))
+    assert N.scratch(0, "cpu").numel() == 16 and N.scratch(100, "cpu").numel() == 100 and N.scratch(1, "cpu").dtype == torch.uint8

@@ -28,7 +28,7 @@ def worker(a):
 
     import golden_util as gu
     from hip_util import model_conf
-    from pixel_nerf_multiscale_amd import NeRFRenderer, PixelNeRFNet, video
+    from pixel_nerf_multiscale_amd import NeRFRenderer, PixelNeRFNet, util, video
     from pixel_nerf_multiscale_amd.parallel import frame_seed
     W = H = a.size
     F, HW = a.frames, a.size * a.size
@@ -53,10 +53,9 @@ def worker(a):
     def render_into_record():
         with torch.no_grad():
             for i in range(F):
-                cam = ([float(x) for x in poses[i].flatten().tolist()], W, H, focal, focal, W * 0.5, H * 0.5, z_near, z_far, 0, HW)
-                rend.forced_seed = frame_seed(seed, i)
-                rend._forward_fused(net, None, False, camera=cam, packed=(record[i * HW:(i + 1) * HW].view(1, HW, 4), ("fine",)))
-        rend.forced_seed = None
+                cam = util.camera(poses[i], W, H, focal, z_near, z_far)
+                with rend.keyed(frame_seed(seed, i)):
+                    rend._forward_fused(net, None, False, camera=cam, packed=(record[i * HW:(i + 1) * HW].view(1, HW, 4), ("fine",)))
 
     def timed(fn):
         torch.cuda.synchronize()
