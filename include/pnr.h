@@ -29,7 +29,8 @@ extern "C" {
                                   * pnr_grid_points / pnr_mc_workspace_bytes / pnr_mc_count / pnr_mc_emit; the training back end, pnr_optim_chunk_elems /
                                   * pnr_optim_plan / pnr_optim_workspace_bytes / pnr_adam_step; the visualisation panel and the colour map, pnr_cmap_workspace_bytes /
                                   * pnr_cmap / pnr_vis_panel_workspace_bytes / pnr_vis_panel; the video drivers' ends, pnr_video_frames /
-                                  * pnr_view_strip / pnr_image_to_tensor */
+                                  * pnr_view_strip / pnr_image_to_tensor; the approximate evaluation's batched metrics, pnr_eval_frames /
+                                  * pnr_eval_frames_workspace_bytes */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -386,6 +387,26 @@ int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride,       /* rendered (
                        float* depth_norm,                          /* (H, W), or NULL */
                        double* metrics,                            /* 2 doubles, or NULL */
                        void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* F frames in one call: the tail of eval/eval_approx.py:136-148, which renders one target view of each of SB objects in one
+ * call and compares them UNCLAMPED.  rgb: F frames of (H*W) pixels x 3, `rgb_stride` floats per pixel (0 = 3), `frame_stride`
+ * floats from one frame to the next (0 = W * H * rgb_stride: a gap between frames is never read); gt (F, 3, H, W).  Per frame
+ * the arithmetic of pnr_eval_frame's metrics, word for word — g = fmaf(gt, 0.5, 0.5), centred fp64 window moments, one partial
+ * pair per 16 x 16 tile, a fixed-order fold without atomics — on x = clamp(rgb, 0, 1) when clamp != 0 (metrics[2 f], [2 f + 1]
+ * are then bit for bit what pnr_eval_frame writes for frame f alone) and on x = rgb as it is when clamp == 0 (a NaN stays a
+ * NaN either way and makes that frame's pair NaN).  One launch over F x tiles workgroups, one with a workgroup per frame that
+ * folds that frame's pairs: frame f's pair depends on frame f's pixels only.  Every check is made before any launch:
+ *   PNR_E_NULL       rgb, gt, metrics or workspace NULL
+ *   PNR_E_SHAPE      F < 1; min(W, H) < 7; W * H >= 2^31; F x tiles > 2^23; rgb_stride 1 or 2 (or negative); a non-zero
+ *                    frame_stride below W * H * rgb_stride
+ *   PNR_E_WORKSPACE  fewer workspace bytes than the size function asks for (16 bytes per frame and tile; 0 for a bad shape) */
+uint64_t pnr_eval_frames_workspace_bytes(int32_t F, int32_t W, int32_t H);
+int32_t pnr_eval_frames(const float* rgb, int32_t rgb_stride   /* floats per pixel, 0 = 3 */,
+                        int64_t frame_stride                   /* floats between frames, 0 = W*H*rgb_stride */,
+                        const float* gt                        /* (F, 3, H, W) planar, in [-1, 1] */,
+                        int32_t F, int32_t W, int32_t H, int32_t clamp,
+                        double* metrics                        /* (F, 2): mse, mean SSIM */,
+                        void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* ---- visualisation: the colour map of src/util/util.py:13-30 and the panel of train/train.py:423-537 (vis_step), csrc/vis.hip -- */
 /* quantize(map), the reference's image_float_to_uint8 for a float32 map:

@@ -155,6 +155,8 @@ PROTOTYPES = {
     "pnr_rgb_loss_bwd": (_i32, [_fp, _fp, _fp, _i64, _i32, _f, _f, _fp, _fp, _fp, _fp]),
     "pnr_eval_frame_workspace_bytes": (_u64, [_i32, _i32]),
     "pnr_eval_frame": (_i32, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _f, _f, _fp, _fp, _fp, _fp, _fp, _u64, _fp]),
+    "pnr_eval_frames_workspace_bytes": (_u64, [_i32, _i32, _i32]),
+    "pnr_eval_frames": (_i32, [_fp, _i32, _i64, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _u64, _fp]),
     "pnr_cmap_workspace_bytes": (_u64, [_i32, _i32]),
     "pnr_cmap": (_i32, [_fp, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _u64, _fp]),
     "pnr_vis_panel_workspace_bytes": (_u64, [_i32, _i32, _i32]),

@@ -3,6 +3,7 @@
 // normalised depth (:288-289), and the two numbers finish.txt is made of — the mean squared error behind PSNR and the mean
 // SSIM (:324-332, as evalio.ssim restates skimage: uniform 7x7 window, sample covariance, whole windows only, per channel).
 // Latency-bound: a 128 x 128 frame is 64 workgroups; the point is that nothing waits on the host.
+// And the two numbers alone for F frames in one call, clamped or not: the tail of eval/eval_approx.py:136-148 (pnr_eval_frames).
 #include "frame_common.h"
 
 namespace pnr {
@@ -28,61 +29,45 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[F
     b = red[1][0];
 }
 
-// One workgroup per 16 x 16 tile.  The tile and a 3-pixel halo of the clamped render x and of the ground truth g = 0.5 gt + 0.5
-// go to LDS (all three channels, 11.6 KB); every thread then owns one pixel: its bytes, its depth, its squared error, and — when
-// the pixel is the centre of a whole window — its SSIM term from the 49 taps around it.  The window arithmetic is fp64: mean
-// first, then CENTRED second moments (sum (x - mx)(y - my)), so a white background with variances around 1e-7 keeps them; the
-// MI355X runs fp64 FMAs at half the fp32 rate, and 2 x 49 taps x 3 channels per pixel are nothing next to the render.
-__global__ void __launch_bounds__(FRAME_THREADS) k_eval_frame(EvalArgs a) {
-    __shared__ float sx[3][EV_LDS][EV_LDS];
-    __shared__ float sg[3][EV_LDS][EV_LDS];
-    __shared__ double red[2][FRAME_THREADS];
-    const int tid = threadIdx.x, tx = tid & (FRAME_TILE - 1), ty = tid / FRAME_TILE;
-    const auto [x0, y0] = tile_origin((int)blockIdx.x, a.tiles_x);
-    const int W = a.W, H = a.H;
+// The tile body k_eval_frame and k_eval_frames share.  Load: the tile at (x0, y0) and a 3-pixel halo of the render x — clamped
+// to [0, 1] when `clamp`, as it is otherwise — and of the ground truth g = 0.5 gt + 0.5 go to LDS (all three channels, 11.6 KB).
+// gt NULL (k_eval_frame without metrics or compare strip): g = 0.
+using EvalTile = float[3][EV_LDS][EV_LDS];
+__device__ __forceinline__ void eval_tile_load(const float* rgb, int rgb_stride, const float* gt, int W, int H, int x0, int y0,
+                                               bool clamp, EvalTile& sx, EvalTile& sg, int tid) {
     const int64_t HW = (int64_t)W * H;
-
     for (int i = tid; i < EV_LDS * EV_LDS; i += FRAME_THREADS) {
         const int ly = i / EV_LDS, lx = i % EV_LDS;
         const int gy = y0 - EV_HALO + ly, gx = x0 - EV_HALO + lx;
         float v[3] = {0.0f, 0.0f, 0.0f}, g[3] = {0.0f, 0.0f, 0.0f};       // outside the image: never part of a whole window
         if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
             const int64_t pix = (int64_t)gy * W + gx;
-            const float* p = a.rgb + pix * a.rgb_stride;
+            const float* p = rgb + pix * rgb_stride;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                v[c] = clamp01(p[c]);
-                if (a.gt) g[c] = fmaf(a.gt[c * HW + pix], 0.5f, 0.5f);     // the bits of torch's images * 0.5 + 0.5
+                v[c] = clamp ? clamp01(p[c]) : p[c];
+                if (gt) g[c] = fmaf(gt[c * HW + pix], 0.5f, 0.5f);         // the bits of torch's images * 0.5 + 0.5
             }
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) { sx[c][ly][lx] = v[c]; sg[c][ly][lx] = g[c]; }
     }
     __syncthreads();
+}
 
+// Sums: every thread owns the pixel (x0 + tx, y0 + ty): its squared error and — when the pixel is the centre of a whole window
+// — its SSIM term from the 49 taps around it; then the workgroup's (squared-error sum, SSIM sum) in every thread.  The window
+// arithmetic is fp64: mean first, then CENTRED second moments (sum (x - mx)(y - my)), so a white background with variances
+// around 1e-7 keeps them; the MI355X runs fp64 FMAs at half the fp32 rate, and 2 x 49 taps x 3 channels per pixel are nothing
+// next to the render.
+__device__ __forceinline__ void eval_tile_sums(const EvalTile& sx, const EvalTile& sg, int W, int H, int x0, int y0,
+                                               double (*red)[FRAME_THREADS], int tid, double& se, double& ss) {
+    const int tx = tid & (FRAME_TILE - 1), ty = tid / FRAME_TILE;
     const int gy = y0 + ty, gx = x0 + tx;
-    const bool inside = gy < H && gx < W;
     const int cy = ty + EV_HALO, cx = tx + EV_HALO;
-    if (inside) {
-        const int64_t pix = (int64_t)gy * W + gx;
-        if (a.rgb_u8) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) a.rgb_u8[pix * 3 + c] = quant_u8(sx[c][cy][cx]);
-        }
-        if (a.compare_u8) {                                                // np.hstack((render, ground truth)): rows of 2 W pixels
-            uint8_t* row = a.compare_u8 + (int64_t)gy * W * 6;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                row[(int64_t)gx * 3 + c] = quant_u8(sx[c][cy][cx]);
-                row[((int64_t)W + gx) * 3 + c] = quant_u8(clamp01(sg[c][cy][cx]));
-            }
-        }
-        if (a.depth_norm) a.depth_norm[pix] = __fdiv_rn(__fsub_rn(a.depth[pix * a.depth_stride], a.z_near), a.z_range);
-    }
-    if (!a.part) return;                                                   // uniform over the launch
-
-    double se = 0.0, ss = 0.0;
-    if (inside) {
+    se = 0.0;
+    ss = 0.0;
+    if (gy < H && gx < W) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const double d = (double)sx[c][cy][cx] - (double)sg[c][cy][cx];
@@ -110,15 +95,75 @@ __global__ void __launch_bounds__(FRAME_THREADS) k_eval_frame(EvalArgs a) {
         }
     }
     block_sum2(se, ss, red, tid);
+}
+
+// One workgroup per 16 x 16 tile of ONE frame: the tile body on the clamped render, then every thread writes its pixel's bytes
+// and depth, and thread 0 the tile's partial pair.
+__global__ void __launch_bounds__(FRAME_THREADS) k_eval_frame(EvalArgs a) {
+    __shared__ EvalTile sx, sg;
+    __shared__ double red[2][FRAME_THREADS];
+    const int tid = threadIdx.x, tx = tid & (FRAME_TILE - 1), ty = tid / FRAME_TILE;
+    const auto [x0, y0] = tile_origin((int)blockIdx.x, a.tiles_x);
+    const int W = a.W, H = a.H;
+    eval_tile_load(a.rgb, a.rgb_stride, a.gt, W, H, x0, y0, true, sx, sg, tid);
+
+    const int gy = y0 + ty, gx = x0 + tx;
+    const int cy = ty + EV_HALO, cx = tx + EV_HALO;
+    if (gy < H && gx < W) {
+        const int64_t pix = (int64_t)gy * W + gx;
+        if (a.rgb_u8) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.rgb_u8[pix * 3 + c] = quant_u8(sx[c][cy][cx]);
+        }
+        if (a.compare_u8) {                                                // np.hstack((render, ground truth)): rows of 2 W pixels
+            uint8_t* row = a.compare_u8 + (int64_t)gy * W * 6;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                row[(int64_t)gx * 3 + c] = quant_u8(sx[c][cy][cx]);
+                row[((int64_t)W + gx) * 3 + c] = quant_u8(clamp01(sg[c][cy][cx]));
+            }
+        }
+        if (a.depth_norm) a.depth_norm[pix] = __fdiv_rn(__fsub_rn(a.depth[pix * a.depth_stride], a.z_near), a.z_range);
+    }
+    if (!a.part) return;                                                   // uniform over the launch
+
+    double se, ss;
+    eval_tile_sums(sx, sg, W, H, x0, y0, red, tid, se, ss);
     if (tid == 0) { a.part[2 * (int64_t)blockIdx.x] = se; a.part[2 * (int64_t)blockIdx.x + 1] = ss; }
 }
 
-// ONE workgroup: thread t adds the tiles t, t + 256, .. in ascending order, then block_sum2 — no atomics, the same inputs give
-// the same bits.  metrics[0] = mean squared error over 3 H W elements, metrics[1] = mean SSIM over 3 (H - 6)(W - 6) windows.
+// F frames in one launch (the approximate evaluation, eval/eval_approx.py:136-148: SB objects' target views, NOT clamped there):
+// workgroup b works on tile b % tiles of frame b / tiles with the same tile body and leaves its pair at part[b] — frame f's
+// pairs are part[f tiles .. (f + 1) tiles), what k_eval_finish's workgroup f folds.
+struct EvalFramesArgs {
+    const float* rgb; const float* gt;
+    int64_t frame_stride;                          // floats between two frames of rgb
+    int rgb_stride, W, H, tiles_x, tiles, clamp;
+    double* part;                                  // (F, tiles, 2)
+};
+
+__global__ void __launch_bounds__(FRAME_THREADS) k_eval_frames(EvalFramesArgs a) {
+    __shared__ EvalTile sx, sg;
+    __shared__ double red[2][FRAME_THREADS];
+    const int tid = threadIdx.x;
+    const int f = (int)blockIdx.x / a.tiles, tile = (int)blockIdx.x % a.tiles;
+    const auto [x0, y0] = tile_origin(tile, a.tiles_x);
+    const int W = a.W, H = a.H;
+    eval_tile_load(a.rgb + f * a.frame_stride, a.rgb_stride, a.gt + (int64_t)f * 3 * W * H, W, H, x0, y0, a.clamp != 0, sx, sg, tid);
+    double se, ss;
+    eval_tile_sums(sx, sg, W, H, x0, y0, red, tid, se, ss);
+    if (tid == 0) { a.part[2 * (int64_t)blockIdx.x] = se; a.part[2 * (int64_t)blockIdx.x + 1] = ss; }
+}
+
+// One workgroup per FRAME (one for k_eval_frame): thread t adds the frame's tiles t, t + 256, .. in ascending order, then
+// block_sum2 — no atomics, the same inputs give the same bits, and a frame's pair is made of that frame's partial pairs alone.
+// metrics[2 f] = mean squared error over 3 H W elements, metrics[2 f + 1] = mean SSIM over 3 (H - 6)(W - 6) windows.
 __global__ void __launch_bounds__(FRAME_THREADS) k_eval_finish(const double* __restrict__ part, int tiles, int W, int H,
                                                                double* __restrict__ metrics) {
     __shared__ double red[2][FRAME_THREADS];
     const int tid = threadIdx.x;
+    part += 2 * (int64_t)blockIdx.x * tiles;
+    metrics += 2 * (int64_t)blockIdx.x;
     double se = 0.0, ss = 0.0;
     for (int t = tid; t < tiles; t += FRAME_THREADS) { se += part[2 * (int64_t)t]; ss += part[2 * (int64_t)t + 1]; }
     block_sum2(se, ss, red, tid);
@@ -167,5 +212,38 @@ extern "C" int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride, const fl
                            H, metrics);
         PNR_LAUNCH_CHECK();
     }
+    return PNR_OK;
+}
+
+// F x tiles pairs; 0 for a shape pnr_eval_frames refuses
+extern "C" uint64_t pnr_eval_frames_workspace_bytes(int32_t F, int32_t W, int32_t H) {
+    if (F < 1 || !frame_pixels_ok(W, H) || W < EV_WIN || H < EV_WIN) return 0;
+    const int64_t tiles = frame_tiles(W, H);
+    if (tiles > FRAME_MAX_TILES / F) return 0;
+    return (uint64_t)F * (uint64_t)tiles * 2 * sizeof(double);
+}
+
+extern "C" int32_t pnr_eval_frames(const float* rgb, int32_t rgb_stride, int64_t frame_stride, const float* gt, int32_t F, int32_t W,
+                                   int32_t H, int32_t clamp, double* metrics, void* workspace, uint64_t workspace_bytes,
+                                   void* stream) {
+    if (!rgb || !gt || !metrics || !workspace) return PNR_E_NULL;
+    if (F < 1 || !frame_pixels_ok(W, H) || W < EV_WIN || H < EV_WIN) return PNR_E_SHAPE;
+    const int64_t tiles = frame_tiles(W, H);
+    if (tiles > FRAME_MAX_TILES / F) return PNR_E_SHAPE;                  // F x tiles workgroups in one launch
+    if (rgb_stride == 0) rgb_stride = 3;
+    if (rgb_stride < 3) return PNR_E_SHAPE;
+    const int64_t frame_floats = (int64_t)W * H * rgb_stride;
+    if (frame_stride == 0) frame_stride = frame_floats;
+    if (frame_stride < frame_floats) return PNR_E_SHAPE;
+    if (workspace_bytes < pnr_eval_frames_workspace_bytes(F, W, H)) return PNR_E_WORKSPACE;
+    EvalFramesArgs a;
+    a.rgb = rgb; a.gt = gt; a.frame_stride = frame_stride;
+    a.rgb_stride = rgb_stride; a.W = W; a.H = H; a.tiles_x = frame_tiles_x(W); a.tiles = (int)tiles; a.clamp = clamp;
+    a.part = (double*)workspace;
+    hipLaunchKernelGGL(k_eval_frames, dim3((unsigned)(F * tiles)), dim3(FRAME_THREADS), 0, (hipStream_t)stream, a);
+    PNR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)F), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)workspace,
+                       (int)tiles, W, H, metrics);
+    PNR_LAUNCH_CHECK();
     return PNR_OK;
 }

@@ -13,6 +13,8 @@ per-frame work (clamp, quantisation, PSNR / SSIM sums, normalised depth) to the 
 * checkpoints                 three mutually incompatible schemas in the reference tree
 * evaluate()                  reference eval/eval.py:186-362           the per-object loop that composes the above with
                               encode -> render -> clamp -> metrics -> finish.txt (resume), on this package's renderer
+* evaluate_approx()           reference eval/eval_approx.py:89-153     the development loop: one random target view per
+                              object, a loader batch of objects per render call, metrics on the UNclamped frames
 """
 import math
 import os
@@ -94,6 +96,11 @@ def quantize_uint8(rgb):
 def psnr(img, gt, data_range=1.0):
     err = np.mean((np.asarray(img, np.float64) - np.asarray(gt, np.float64)) ** 2)
     return 10.0 * np.log10((data_range ** 2) / err)
+
+
+def _psnr_of_mse(mse):
+    """PSNR (data_range 1) of a mean squared error read back from the device: inf for identical images, NaN for a NaN."""
+    return float("inf") if mse == 0.0 else 10.0 * math.log10(1.0 / mse) if mse > 0.0 else float("nan")
 
 
 def ssim(img, gt, data_range=1.0, win_size=7, K1=0.01, K2=0.03):
@@ -365,7 +372,7 @@ class _DeviceBackEnd(_BackEnd):
             if compare:
                 mse, s = (float(x) for x in pairs_h[i])
                 curr_ssim += s
-                curr_psnr += float("inf") if mse == 0.0 else 10.0 * math.log10(1.0 / mse) if mse > 0.0 else float("nan")
+                curr_psnr += _psnr_of_mse(mse)
         return (curr_psnr / n_gen, curr_ssim / n_gen) if compare else (0.0, 0.0)
 
 
@@ -480,3 +487,182 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
     if verbose and log.cnt:
         print("final psnr", log.mean()[0], "ssim", log.mean()[1])
     return (*log.mean(), log.cnt)
+
+
+# ------------------------------------------------------------------------------------ the approximate evaluation (eval_approx.py)
+def _approx_source(source):
+    """`source` as eval_approx.py:96 parses --source ("0 2 5", "-1"), or a sequence of view indices -> LongTensor (NS,)."""
+    views = source.split() if isinstance(source, str) else (source.tolist() if torch.is_tensor(source) else list(source))
+    return torch.tensor([int(v) for v in views], dtype=torch.long).reshape(-1)
+
+
+def draw_approx_views(SB, NV, source):
+    """The view draws of eval/eval_approx.py:111-118 for one loader batch of SB objects with NV views each, on torch's global
+    CPU generator and in the reference's order, so that one torch.random.manual_seed gives the reference's views batch after
+    batch (tests/golden/eval_approx_views.npz): source "-1" draws randint(0, NV, (SB, 1)) as the one source view of each
+    object, any other source ("0 2 5", or a sequence) is used for every object; then dest_view = randint(0, NV - NS, (SB, 1)),
+    moved past the source views by dest_view += dest_view >= src_view[:, i:i+1] for i in 0 .. NS - 1.
+    -> (src_view (SB, NS), dest_view (SB, 1)), int64 on the host.
+    ValueError, before anything is drawn, where the reference leaves the result undefined: a source list that is not strictly
+    increasing (the skips then land on source views), a source index outside [0, NV), no view left for a target (NV - NS < 1)."""
+    source = _approx_source(source)
+    SB, NV, NS = int(SB), int(NV), int(source.numel())
+    random_source = NS == 1 and int(source[0]) == -1
+    if NS < 1:
+        raise ValueError("source must name at least one view, or be -1")
+    if not random_source:
+        if NS > 1 and not bool((source[1:] > source[:-1]).all()):
+            raise ValueError(f"source views must be strictly increasing, got {source.tolist()}")
+        if int(source.min()) < 0 or int(source.max()) >= NV:
+            raise ValueError(f"source views {source.tolist()} outside [0, {NV})")
+    if NV - NS < 1:
+        raise ValueError(f"{NS} source views of {NV} leave no target view")
+    if random_source:
+        src_view = torch.randint(0, NV, (SB, 1))
+    else:
+        src_view = source.unsqueeze(0).expand(SB, -1)
+    dest_view = torch.randint(0, NV - NS, (SB, 1))
+    for i in range(NS):
+        dest_view += dest_view >= src_view[:, i:i + 1]
+    return src_view, dest_view
+
+
+def evaluate_approx(net, renderer, loader, *, source="64", seed=1234, z_near=None, z_far=None, metrics="host",
+                    render_par=None, max_batches=None, per_object=None, verbose=True):
+    """The approximate evaluation of the reference (eval/eval_approx.py:89-153, "since eval.py is too slow") on this package's
+    renderer: ONE random target view per object, a loader batch of objects per render call.  -> (mean_psnr, mean_ssim, count).
+
+    loader: an iterable of batched dicts as the reference's DataLoader yields them (:68-70), host tensors: "images"
+    (SB, NV, 3, H, W) in [-1, 1], "poses" (SB, NV, 4, 4) camera-to-world, "focal", optional "c"; "masks" is ignored.  z_near /
+    z_far from the arguments or loader.dataset's attributes (:86-87).  net / renderer as the driver sets them up: the overrides
+    of :62-64 and :76-82 (--coarse, n_coarse >= 64) stay with the caller, as in evaluate().
+
+    torch.random.manual_seed(seed) once before the loop (:89).  Per batch (:101-152): focal = data["focal"][0] serves the
+    whole batch (:105); the views from draw_approx_views (:111-118); the rays of the SB target cameras (:120-123) built on
+    the device into one (SB, H*W, 8) tensor (util.gen_rays_device, the bits of pnr_gen_rays); net.encode on the (SB, NS, ..)
+    selection of source images and poses (:125-132) — only the selection and the SB ground-truth views are uploaded
+    (util.upload, pinned and asynchronous), never all NV views; ONE render call for all SB objects (:134) through render_par,
+    or a _RenderWrapper(net, renderer, simple_output=True) when none is given; SSIM and PSNR per object on the UNCLAMPED frames
+    against images * 0.5 + 0.5 (:136-150); the running "curr psnr .. ssim .." line (:152) when verbose, and the final line (:153).
+
+    metrics="host" is the reference's tail: one D2H copy of the batch's fp32 frames, evalio.ssim / evalio.psnr per object.
+    metrics="device": one util.eval_frames(.., clamp=False) call per batch (pnr_eval_frames) on the frames where the render
+    left them; the (SB, 2) [mse, ssim] pairs stay on the device and PSNR is 10 log10(1 / mse) on the host in fp64, inf for
+    mse == 0 and NaN for a NaN, as in evaluate(metrics="device").  The host reads one batch's pairs per batch when verbose (the
+    running line needs them) and everything in a single read after the last batch otherwise.
+    per_object: a list that receives (batch, index_in_batch, src_views, dest_view, psnr, ssim) per object.
+    max_batches: stop after that many batches.
+
+    Deliberate differences: data["c"][0] is used as the principal point of the batch when the loader gives one (the
+    reference ignores "c", :120-132, and so renders every dataset about the image centre; without the key this is the
+    reference's behaviour).  The render does not consume torch's generator — util.seed_from_torch would change every
+    later view draw relative to the reference: batch b renders under renderer.keyed(frame_seed(seed, b)), with object
+    stride 0, so the objects of a batch follow each other in the ray key and share no jitter.  SSIM is this module's
+    restatement (skimage is not importable here: parity unpinned); the view draws are pinned by fixture.  min(H, W) < 7 (no
+    whole SSIM window) is a ValueError before anything is rendered.  Under an initialised process group of more than one
+    rank the function raises NotImplementedError: evaluate() is the sharded driver."""
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("evaluate_approx runs in one process; evaluate() is the driver that shards over ranks")
+    source = _approx_source(source)
+    dset = getattr(loader, "dataset", None)
+    z_near = getattr(dset, "z_near", None) if z_near is None else z_near
+    z_far = getattr(dset, "z_far", None) if z_far is None else z_far
+    torch.random.manual_seed(seed)
+    total_psnr = total_ssim = 0.0
+    cnt = 0
+    dev = was_training = None
+    views, pairs = [], []                # per batch: (src_view, dest_view); device back end: the (SB, 2) device pairs
+
+    def account(b, numbers):
+        """numbers: (psnr, ssim) per object of batch b, in order."""
+        nonlocal total_psnr, total_ssim, cnt
+        for sb, (p, s) in enumerate(numbers):
+            total_ssim += s
+            total_psnr += p
+            if per_object is not None:
+                per_object.append((b, sb, views[b][0][sb].tolist(), int(views[b][1][sb, 0]), p, s))
+        cnt += len(numbers)
+
+    def read_pairs(dev_pairs):
+        """One read of device pairs (n, 2) -> [(psnr, ssim)] * n."""
+        host = torch.empty(dev_pairs.shape, dtype=torch.float64, pin_memory=True)
+        host.copy_(dev_pairs, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        done.synchronize()
+        return [(_psnr_of_mse(float(m)), float(s)) for m, s in host.tolist()]
+
+    try:
+        with torch.no_grad():
+            for b, data in enumerate(loader):
+                if max_batches is not None and b >= max_batches:
+                    break
+                images = data["images"]                                        # (SB, NV, 3, H, W)
+                poses = data["poses"]                                          # (SB, NV, 4, 4)
+                SB, NV, _, H, W = images.shape
+                if min(H, W) < 7:
+                    raise ValueError(f"{H} x {W} frames hold no whole 7 x 7 SSIM window")
+                if dev is None:                                                # the first batch: before it nothing touches net
+                    dev, was_training = net.poses.device, net.training
+                    net.eval()
+                    z_near, z_far = float(z_near), float(z_far)
+                    if render_par is None:
+                        from .render.nerf import _RenderWrapper
+                        render_par = _RenderWrapper(net, renderer, simple_output=True).eval()
+                focal = torch.as_tensor(data["focal"][0]).float()              # :105
+                focal = focal.reshape(()) if focal.numel() == 1 else focal.reshape(2)
+                c = torch.as_tensor(data["c"][0]).float() if data.get("c") is not None else None
+                src_view, dest_view = draw_approx_views(SB, NV, source)        # :111-118
+                views.append((src_view, dest_view))
+
+                dest_poses = util.batched_index_select_nd(poses, dest_view).reshape(SB, 4, 4).float()
+                all_rays = torch.empty(SB, H * W, 8, device=dev, dtype=torch.float32)
+                for sb in range(SB):
+                    util.gen_rays_device(dest_poses[sb], W, H, focal, z_near, z_far, c=c, out=all_rays[sb])
+
+                pri_images = util.batched_index_select_nd(images, src_view)    # (SB, NS, 3, H, W)
+                pri_poses = util.batched_index_select_nd(poses, src_view)      # (SB, NS, 4, 4)
+                net.encode(util.upload(pri_images.float().contiguous(), dev), util.upload(pri_poses.float().contiguous(), dev),
+                           util.upload(focal[None] if focal.dim() else focal, dev),
+                           c=None if c is None else util.upload(c.reshape(1, -1), dev))
+
+                with renderer.keyed(frame_seed(seed, b)):
+                    rgb_fine, _depth = render_par(all_rays)
+                _depth = None
+                images_gt = util.batched_index_select_nd(images, dest_view).reshape(SB, 3, H, W).float()
+                if metrics == "device":
+                    gt_dev = util.upload(images_gt.contiguous(), dev)
+                    pairs.append(util.eval_frames(rgb_fine.reshape(SB, H * W, 3), gt_dev, clamp=False))
+                    if verbose:
+                        account(b, read_pairs(pairs[-1]))
+                else:
+                    rgb_dev = rgb_fine.reshape(SB, H, W, 3)
+                    rgb_h = torch.empty(rgb_dev.shape, dtype=torch.float32, pin_memory=True)
+                    rgb_h.copy_(rgb_dev, non_blocking=True)
+                    done = torch.cuda.Event()
+                    done.record(torch.cuda.current_stream(dev))
+                    done.synchronize()
+                    rgb_np = rgb_h.numpy()
+                    rgb_gt_all = (images_gt * 0.5 + 0.5).permute(0, 2, 3, 1).contiguous().numpy()
+                    numbers = []
+                    for sb in range(SB):
+                        s = ssim(rgb_np[sb], rgb_gt_all[sb], data_range=1)
+                        numbers.append((float(psnr(rgb_np[sb], rgb_gt_all[sb], data_range=1)), s))
+                    account(b, numbers)
+                if verbose:
+                    print("curr psnr", total_psnr / cnt, "ssim", total_ssim / cnt)
+            if metrics == "device" and not verbose and pairs:
+                numbers, at = read_pairs(torch.cat(pairs, 0)), 0               # the single read of the run
+                for b, p in enumerate(pairs):
+                    account(b, numbers[at:at + p.shape[0]])
+                    at += p.shape[0]
+    finally:
+        if was_training is not None:
+            net.train(was_training)
+    if not cnt:
+        return 0.0, 0.0, 0
+    if verbose:
+        print("final psnr", total_psnr / cnt, "ssim", total_ssim / cnt)
+    return total_psnr / cnt, total_ssim / cnt, cnt

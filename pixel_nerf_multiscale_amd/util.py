@@ -207,13 +207,19 @@ def seed_from_torch():
     return (hi << 31) | lo
 
 
-def gen_rays_device(pose, width, height, focal, z_near, z_far, c=None, device="cuda"):
+def gen_rays_device(pose, width, height, focal, z_near, z_far, c=None, device="cuda", out=None):
     """gen_rays for ONE camera, computed on the GPU by libpnr_hip (pnr_gen_rays): pose (4,4) c2w on the host ->
-    rays (H*W, 8) on `device`, never materialised on the host."""
+    rays (H*W, 8) on `device`, never materialised on the host.  out: a contiguous float32 (H*W, 8) device tensor
+    to write into — one row of an (SB, H*W, 8) batch of cameras — which is then returned; `device` is out's."""
     from . import _native as N
     cam = camera(pose, width, height, focal, z_near, z_far, c=c)
-    dev = torch.device(device)
-    out = torch.empty(cam.n, 8, device=dev, dtype=torch.float32)
+    if out is None:
+        dev = torch.device(device)
+        out = torch.empty(cam.n, 8, device=dev, dtype=torch.float32)
+    else:
+        if tuple(out.shape) != (cam.n, 8) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 ({cam.n}, 8), got {out.dtype} {tuple(out.shape)}")
+        dev = N.same_device(out)
     N.check(N.lib.pnr_gen_rays(*cam.c_args(), N.ptr(out), N.current_stream(dev)), "pnr_gen_rays")
     return out
 
@@ -361,6 +367,38 @@ def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True,
                                  N.dptr(rgb_u8), N.dptr(compare_u8), N.dptr(depth_norm), N.dptr(metrics), N.dptr(ws), nbytes,
                                  N.current_stream(dev)), "pnr_eval_frame")
     return rgb_u8, compare_u8, depth_norm, metrics
+
+
+def eval_frames(rgb, gt, *, clamp=False, metrics_out=None):
+    """The metrics of eval_frame for F frames in ONE call, on the GPU by libpnr_hip (pnr_eval_frames): what the approximate
+    evaluation does with the SB target views of a batch (eval/eval_approx.py:136-148).  rgb (F, H, W, 3) or (F, H*W, 3) float32
+    as the render left it — dense, or a regular view into a packed per-ray record such as the (N, 4) record, with any gap between
+    the frames; gt (F, 3, H, W) float32 in [-1, 1].  clamp=False compares the render as it is, as eval_approx.py does;
+    clamp=True clamps it to [0, 1] first, and row f is then bit for bit eval_frame's pair of frame f.
+    -> (F, 2) float64 on the device, rows [mean squared error, mean SSIM]; metrics_out: a contiguous (F, 2) float64 device
+    tensor to write into.  Nothing here waits for the device; PSNR = 10 log10(1 / mse) is the caller's, on the host."""
+    from . import _native as N
+    if gt.dim() != 4 or gt.shape[1] != 3 or gt.dtype != torch.float32:
+        raise ValueError(f"gt must be float32 (F, 3, H, W), got {gt.dtype} {tuple(gt.shape)}")
+    F, _, H, W = (int(s) for s in gt.shape)
+    if F < 1 or rgb.dim() not in (3, 4) or rgb.shape[0] != F:
+        raise ValueError(f"rgb must be ({F}, {H}, {W}, 3) or ({F}, {H * W}, 3) with F >= 1, got {tuple(rgb.shape)}")
+    dev = N.same_device(rgb, gt, metrics_out)
+    rs = _record_stride(rgb[0], (H, W) if rgb.dim() == 4 else (H * W,), 3, "a frame of rgb")
+    fs = 0
+    if F > 1:
+        fs = int(rgb.stride(0))
+        if fs < H * W * rs:
+            raise ValueError(f"the frames of rgb must follow each other at >= {H * W * rs} floats, got strides {rgb.stride()}")
+    gt = gt.contiguous()
+    metrics = torch.empty(F, 2, dtype=torch.float64, device=dev) if metrics_out is None else metrics_out
+    if tuple(metrics.shape) != (F, 2) or metrics.dtype != torch.float64 or not metrics.is_contiguous():
+        raise ValueError(f"metrics_out must be a contiguous float64 ({F}, 2), got {metrics.dtype} {tuple(metrics.shape)}")
+    nbytes = int(N.lib.pnr_eval_frames_workspace_bytes(F, W, H))
+    ws = N.scratch(nbytes, dev)
+    N.check(N.lib.pnr_eval_frames(rgb.data_ptr(), rs, fs, gt.data_ptr(), F, W, H, int(bool(clamp)), metrics.data_ptr(),
+                                  ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_eval_frames")
+    return metrics
 
 
 def _upsample_sizes(shapes):
