@@ -183,7 +183,7 @@ def resnetfc(sd, zx, d_latent, NS, P, n_blocks=5, combine_layer=3, combine_type=
 def point_forward(sd, cam, latents, xyz, viewdirs, NS, use_code_viewdirs=False,
                   n_blocks=5, combine_layer=3, combine_type="average", return_stages=False, rnd=None):
     """xyz, viewdirs (SB,P,3) world space -> (SB,P,4) [sigmoid rgb, relu sigma].
-    cam = (w2c (SB*NS,3,4), focal (1|SB*NS,2), c (1|SB*NS,2)) from encode_cameras.  rnd: resnetfc's rounding hook."""
+    cam = (w2c (SB*NS,3,4), focal (1|SB|SB*NS,2), c (1|SB|SB*NS,2)) from encode_cameras.  rnd: resnetfc's rounding hook."""
     w2c, focal, c = cam
     SB, P, _ = xyz.shape
     rep = lambda t: t.unsqueeze(1).expand(-1, NS, *t.shape[1:]).reshape(-1, *t.shape[1:])
@@ -198,8 +198,11 @@ def point_forward(sd, cam, latents, xyz, viewdirs, NS, use_code_viewdirs=False,
     else:
         zf = torch.cat((positional_encoding(zf, **hook), vd), dim=1)
     uv = -x_cam[:, :, :2] / x_cam[:, :, 2:]
-    uv = uv * (rep(focal.unsqueeze(1)) if focal.shape[0] > 1 else focal.unsqueeze(1))
-    uv = uv + (rep(c.unsqueeze(1)) if c.shape[0] > 1 else c.unsqueeze(1))
+    # one row serves every view, SB rows are repeated per view (backup2:216-221); SB*NS rows are per view already (pnr.h's
+    # n_focal / n_c = SB*NS, which the reference's encode() cannot express)
+    per_view = lambda t: t.unsqueeze(1) if t.shape[0] in (1, w2c.shape[0]) else rep(t.unsqueeze(1))
+    uv = uv * per_view(focal)
+    uv = uv + per_view(c)
     lat = index_latent(uv, latents)                                  # (SB*NS, L, P)
     L = lat.shape[1]
     lat = lat.transpose(1, 2).reshape(-1, L)

@@ -109,13 +109,19 @@ def interior_spec(lat, image=None, focal=None, **kw):
     return spec
 
 
-def interior_case(lat, NS=1, SB=1, P=TILE * 24 + 17, seed=500, image=None, focal=None, uv_image=False, **kw):
+def interior_case(lat, NS=1, SB=1, P=TILE * 24 + 17, seed=500, image=None, focal=None, uv_image=False, focal_xy=None, c_xy=None,
+                  **kw):
     """An interior_spec, source poses as golden_util.make_inputs places them, and P points per object along target rays at
     random depths — rays drawn WITH replacement (make_inputs is limited to N <= W H).  The target rays never pass behind a
     source camera, so every BEHIND_EVERY-th point (from index 41 on) is put on its ray's direction from source camera 0's
     centre instead, on the side behind that camera, at the same depth.
+    focal_xy / c_xy: the source cameras' own intrinsics (golden_util.intrinsics), SB or SB*NS rows.  The target rays keep the
+    scalar focal and the image centre.
     Returns dict(spec, poses, maps, xyz (SB,P,3), dirs (SB,P,3), uv_scale)."""
     spec = interior_spec(lat, image, focal, NS=NS, SB=SB, N=P, seed=seed, **kw)
+    for key, val in (("focal_xy", focal_xy), ("c_xy", c_xy)):
+        if val is not None:
+            spec[key] = [[float(a), float(b)] for a, b in val]
     W, H = spec["image"]
     rng = np.random.default_rng(seed * 1000 + 7)
     poses = np.zeros((SB, NS, 4, 4), np.float32)
@@ -137,11 +143,11 @@ def interior_case(lat, NS=1, SB=1, P=TILE * 24 + 17, seed=500, image=None, focal
                 uv_scale=uv_scales(spec) if uv_image else None)
 
 
-def rays_case(lat, n_rays, K, seed=520):
+def rays_case(lat, n_rays, K, seed=520, NS=1, focal_xy=None, c_xy=None):
     """Rays-mode input (pnr_point_mlp with rays and z): n_rays rays drawn with replacement, K random depths per ray.  The
     points are o + z d of the FP32 inputs, formed in float64 (what the kernel is asked to evaluate) and handed to truth and
     emulation as they are."""
-    case = interior_case(lat, P=n_rays, seed=seed)
+    case = interior_case(lat, NS=NS, P=n_rays, seed=seed, focal_xy=focal_xy, c_xy=c_xy)
     spec = case["spec"]
     W, H = spec["image"]
     rng = np.random.default_rng(seed * 1000 + 8)
@@ -167,14 +173,14 @@ def covered_level(spec, uv_scale=None):
 def texel_coords(spec, poses, xyz, level, uv_scale=None):
     """float64 texel coordinates on `level`: (ix, iy, z_cam), each (SB, NS, P).  The fork's lookup normalises by the latent
     size and unnormalises again: texel coordinate = (scaled) pixel coordinate."""
-    W, H = spec["image"]
+    f, c = gu.view_intrinsics(spec)                                        # (SB, NS, 2) each: the case's own, per view
     c2w = np.asarray(poses, np.float64)
     R = np.swapaxes(c2w[..., :3, :3], -1, -2)                              # (SB, NS, 3, 3) world -> camera
     t = -np.einsum("bvij,bvj->bvi", R, c2w[..., :3, 3])
     xc = np.einsum("bvij,bpj->bvpi", R, np.asarray(xyz, np.float64)) + t[:, :, None, :]
     with np.errstate(divide="ignore", invalid="ignore"):
-        u = -xc[..., 0] / xc[..., 2] * spec["focal"] + W * 0.5
-        v = -xc[..., 1] / xc[..., 2] * -spec["focal"] + H * 0.5
+        u = -xc[..., 0] / xc[..., 2] * f[:, :, None, 0] + c[:, :, None, 0]
+        v = -xc[..., 1] / xc[..., 2] * -f[:, :, None, 1] + c[:, :, None, 1]
     sx, sy = uv_scale[level] if uv_scale else (1.0, 1.0)
     return u * sx, v * sy, xc[..., 2]
 
@@ -368,3 +374,68 @@ INTERIOR_CASES = {
 
 def make_case(name):
     return interior_case(**INTERIOR_CASES[name]["make"])
+
+
+# ----------------------------------------------------------------------------- per-view intrinsics (tests/test_gpu_intrinsics.py)
+F8 = 131.25 / 128.0 * 8                      # interior_spec's scalar focal on an 8 x 8 map
+INTR_F_ROWS = gu.INTR_F_ROWS + [[1.13, 0.93], [0.95, 1.18]]          # fx != fy, every row another pair
+INTR_C_ROWS = gu.INTR_C_ROWS + [[+0.4, +0.5], [-0.35, -0.6]]         # off the centre (4, 4), every row another offset
+
+
+def intr_rows(n, first=0):
+    """focal_xy / c_xy of n rows (from row `first` of the tables) on the 8 x 8 interior geometry."""
+    return gu.scaled_intrinsics(F8, (8, 8), INTR_F_ROWS[first:first + n], INTR_C_ROWS[first:first + n])
+
+
+_L8 = [(256, 8, 8)]
+# fused kernel: _c's fields as in INTERIOR_CASES.  One object of one view is the scalar-cache load_cam branch (n_objs == 1); three
+# views carry one row per VIEW; three objects of two views carry one row per OBJECT, which the host repeats per view, with P off a
+# tile multiple (per-object projected streams; on the general stream a tile straddles two objects and view_of picks per lane)
+INTR_FUSED_CASES = {
+    "sb1_ns1_proj": _c("proj", lat=_L8, seed=561, **intr_rows(1)),
+    "sb1_ns1_general": _c("general", proj=False, lat=_L8, seed=561, **intr_rows(1)),
+    "sb1_ns3_per_view_mean": _c("proj", lat=_L8, NS=3, seed=562, **intr_rows(3)),
+    "sb1_ns3_per_view_max": _c("proj", lat=_L8, NS=3, seed=563, combine_type="max", **intr_rows(3)),
+    "sb3_ns2_per_object_proj": _c("proj", lat=_L8, SB=3, NS=2, P=1000, seed=564, **intr_rows(3)),
+    "sb3_ns2_per_object_general": _c("general", proj=False, lat=_L8, SB=3, NS=2, P=1000, seed=564, **intr_rows(3)),
+}
+# training backward at explicit points (k_features_bwd, k_latent_grad_lds): two objects of two views, one row per object
+INTR_TRAIN = dict(lat=_L8, SB=2, NS=2, P=700, seed=581, d_hidden=64, **intr_rows(2))
+INTR_RAYS = dict(lat=_L8, n_rays=83, K=37, seed=565, NS=2, **intr_rows(2))       # rays mode: one object, a row per view
+
+
+def intr_case(name):
+    return rays_case(**INTR_RAYS) if name == "rays_sb1_ns2" else interior_case(**INTR_FUSED_CASES[name]["make"])
+
+
+def _rows_of(spec):
+    """(focal rows (n, 2), c rows (m, 2)) of a spec as float arrays, the defaults written out as one row."""
+    W, H = spec["image"]
+    focal, c = gu.intrinsics(spec)
+    f = np.full((1, 2), float(focal)) if np.ndim(focal) == 0 else np.asarray(focal, np.float64)
+    return f, (np.array([[W * 0.5, H * 0.5]]) if c is None else np.asarray(c, np.float64))
+
+
+def intrinsics_mutants(spec):
+    """{name: spec with deliberately wrong source intrinsics}: the mistakes a kernel or the host layer can make with (fx, fy),
+    (cx, cy) and the row a view reads.  A mutant that leaves this spec's intrinsics as they are (one row cannot be given to
+    the wrong object; a scalar focal has no axes to swap) is left out: it is no mistake on that case."""
+    f, c = _rows_of(spec)
+    W, H = spec["image"]
+    centre = np.array([[W * 0.5, H * 0.5]])
+    m = {
+        "fy := fx": (f[:, [0, 0]], c), "fx <-> fy": (f[:, ::-1], c),
+        "c := centre": (f, np.broadcast_to(centre, c.shape)), "cx <-> cy": (f, c[:, ::-1]),
+        "row 0 for every row": (np.broadcast_to(f[:1], f.shape), np.broadcast_to(c[:1], c.shape)),
+        "rows rolled by one": (np.roll(f, 1, axis=0), np.roll(c, 1, axis=0)),
+        "only focal broadcast": (np.broadcast_to(f[:1], f.shape), c), "only c broadcast": (f, np.broadcast_to(c[:1], c.shape)),
+    }
+    out = {}
+    for name, (mf, mc) in m.items():
+        if not (np.array_equal(mf, f) and np.array_equal(mc, c)):
+            out[name] = dict(spec, **({} if np.array_equal(mf, f) else dict(focal_xy=np.asarray(mf).tolist())),
+                             **({} if np.array_equal(mc, c) else dict(c_xy=np.asarray(mc).tolist())))
+    return out
+
+
+MUTANT_FACTOR = 5.0          # a mutant must move the fp64 truth's rgb by 5 x what class_compare accepts for bf16 (2 x emulation rms)

@@ -61,6 +61,59 @@ CASES = {
                           radius=2.0, edge=True),
 }
 
+# Cases with per-object source intrinsics (fx != fy, off-centre c) on INTERIOR geometry: the image is as large as the map, so
+# the texel a point reads depends on f and c.  Kept apart from CASES: the 16-bit floors of test_gpu_parity.py were measured on
+# border-clamped geometry and do not apply here.  focal_xy / c_xy: SB (or SB*NS) rows of (fx, fy) / (cx, cy), see intrinsics().
+INTR_F_ROWS = [[1.00, 1.22], [0.86, 1.07]]              # per object, times the spec's scalar focal
+INTR_C_ROWS = [[+0.6, -0.45], [-0.8, +0.35]]            # per object, added to the image centre
+
+
+def scaled_intrinsics(focal, image, f_rows=INTR_F_ROWS, c_rows=INTR_C_ROWS):
+    """dict(focal_xy, c_xy) for a spec: rows of factors on the scalar focal and of offsets from the image centre, as plain
+    lists (a spec goes into a fixture as JSON)."""
+    W, H = image
+    return dict(focal_xy=[[float(focal * a), float(focal * b)] for a, b in f_rows],
+                c_xy=[[float(W * 0.5 + a), float(H * 0.5 + b)] for a, b in c_rows])
+
+
+INTRINSICS_CASES = {
+    "tiny_sb2_ns2_intr": _case(seed=17, SB=2, NS=2, N=12, image=(7, 5), focal=45.0 * 7 / 40,
+                               **scaled_intrinsics(45.0 * 7 / 40, (7, 5))),
+    # seed 37: sigma > 0 on 0.60 (coarse) / 0.47 (fine) of the oracle's points — many seeds leave one pass all but empty
+    "full_sb2_ns2_intr": _case(seed=37, d_hidden=512, lat=[(256, 8, 8)], image=(8, 8), focal=131.25 * 8 / 128, SB=2, NS=2,
+                               N=16, Kc=16, Kf=8, Kfd=4, **scaled_intrinsics(131.25 * 8 / 128, (8, 8))),
+}
+
+
+def intrinsics(spec):
+    """(focal, c) of a spec's SOURCE cameras, in the form a caller hands them to encode() / set_cameras / encode_cameras: the
+    scalar spec["focal"] and None (the image centre) unless the spec carries focal_xy / c_xy — SB or SB*NS rows of (fx, fy) /
+    (cx, cy), returned as fp32 arrays (rows, 2) with fy positive (encode negates it).  Target rays keep the scalar focal:
+    they come from a target camera."""
+    fxy, cxy = spec.get("focal_xy"), spec.get("c_xy")
+    rows = (spec["SB"], spec["SB"] * spec["NS"])
+    focal = spec["focal"] if fxy is None else np.asarray(fxy, np.float32).reshape(-1, 2)
+    c = None if cxy is None else np.asarray(cxy, np.float32).reshape(-1, 2)
+    assert (fxy is None or focal.shape[0] in rows) and (cxy is None or c.shape[0] in rows), (rows, fxy, cxy)
+    return focal, c
+
+
+def view_intrinsics(spec):
+    """intrinsics(spec) written out per source view in float64: (f (SB, NS, 2) = (fx, fy) with fy positive, c (SB, NS, 2)).
+    One row serves every view, SB rows serve the NS views of their object, SB*NS rows are object-major."""
+    W, H = spec["image"]
+    SB, NS = spec["SB"], spec["NS"]
+    focal, c = intrinsics(spec)
+    f = np.asarray(focal, np.float32).astype(np.float64)                   # the fp32 value every consumer is handed
+    f = np.full((1, 2), float(f)) if f.ndim == 0 else f
+    c = np.array([[W * 0.5, H * 0.5]]) if c is None else np.asarray(c, np.float64)
+
+    def per_view(t):
+        if t.shape[0] == SB * NS:
+            return t.reshape(SB, NS, 2)
+        return np.broadcast_to(t.reshape(-1, 1, 2), (SB, NS, 2))
+    return per_view(f), per_view(c)
+
 
 # ----------------------------------------------------------------------------- cameras / rays
 def pose_spherical(theta_deg, phi_deg, radius):

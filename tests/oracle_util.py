@@ -10,7 +10,7 @@ from oracle import pixelnerf_oracle as orc
 def oracle_setup(fx):
     spec = fx["spec"]
     W, H = spec["image"]
-    cam = orc.encode_cameras(torch.from_numpy(fx["poses"]), spec["focal"], None, W, H)
+    cam = orc.encode_cameras(torch.from_numpy(fx["poses"]), *gu.intrinsics(spec), W, H)
     lat = [torch.from_numpy(x) for x in gu.make_latents(spec)]
     sd_c = {k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, "coarse").items()}
     sd_f = {k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, "fine").items()} if spec["fine_mlp"] else None

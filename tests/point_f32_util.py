@@ -250,6 +250,17 @@ CHUNKED = {                     # d_hidden 64: the chunk logic does not depend o
 RAYS_K, RAYS_SEED, LATTICE_SEED = 37, 620, 620
 RAYS = {"rays_83": 83, "rays_131": 131}          # 3071 points (NCHW) and 4847 (channels-last)
 POINT_CASES = {**INSIDE, **SWITCH, **CHUNKED}
+# per-view intrinsics (tests/test_gpu_intrinsics.py): two objects of two views, one point set each, called with its first
+# P_INTR_BELOW points per object (4094 points: NCHW reads) and with all P_INTR_ABOVE (4130: the channels-last copies) — both
+# with view > 0.  One row per object (the host repeats it per view), SB*NS distinct rows, and n_focal = 1 with n_c = SB*NS.
+P_INTR_BELOW, P_INTR_ABOVE = CL_POINTS // 2 - 1, CL_POINTS // 2 + 17
+_intr = dict(lat=[(256, 8, 8)], SB=2, NS=2, P=P_INTR_ABOVE)
+INTR = {
+    "intr_per_object": _make(seed=571, **_intr, **fu.intr_rows(2)),
+    "intr_per_view": _make(seed=572, **_intr, **fu.intr_rows(4)),
+    "intr_scalar_focal_per_view_c": _make(seed=573, **_intr, c_xy=fu.intr_rows(4)["c_xy"]),
+}
+_MAKE = {**POINT_CASES, **INTR}
 _cases, _ensembles = {}, {}
 
 
@@ -261,12 +272,12 @@ def make_case(name):
         elif name in RAYS:
             _cases[name] = fu.rays_case([(256, 8, 8)], RAYS[name], RAYS_K, seed=RAYS_SEED)
         else:
-            _cases[name] = fu.interior_case(**POINT_CASES[name]["make"])
+            _cases[name] = fu.interior_case(**_MAKE[name]["make"])
     return _cases[name]
 
 
 def coarse_of(name):
-    return POINT_CASES[name]["coarse"] if name in POINT_CASES else True
+    return _MAKE[name]["coarse"] if name in _MAKE else True
 
 
 def ensemble(name):

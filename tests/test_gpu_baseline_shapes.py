@@ -125,7 +125,7 @@ def test_cfg1_srn_64x64_k32_fp32_path_matches_the_oracle():
     g = torch.Generator().manual_seed(1)
     noise = dict(noise_c=torch.rand(4096, 32, generator=g))
     W, H = spec["image"]
-    cam = orc.encode_cameras(torch.from_numpy(poses), spec["focal"], None, W, H)
+    cam = orc.encode_cameras(torch.from_numpy(poses), *gu.intrinsics(spec), W, H)
     sd_c = {k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, "coarse").items()}
     with torch.no_grad():
         ref = orc.render(sd_c, None, cam, [torch.from_numpy(x) for x in gu.make_latents(spec)], rays, 1, 32, 0, 0,

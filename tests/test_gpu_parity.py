@@ -475,7 +475,7 @@ def test_encoder_half_channels_last_latents_are_consumed_without_repack():
     handed to libpnr_hip by pointer (no pnr_pack_latents), and the render matches the fp32-trunk + repack route.
     (The trunk itself is unpinned against torchvision, which is not installed here: parity unpinned for N2.)"""
     import ctypes as C
-    from hip_util import model_conf, build_renderer
+    from hip_util import model_conf, build_renderer, camera_tensors
     import golden_util as gu
     from pixel_nerf_multiscale_amd import PixelNeRFNet, util
     spec = dict(gu.CASES["full_ns3"]); spec.update(NS=2, Kf=0, Kfd=0, Kc=32)
@@ -492,13 +492,13 @@ def test_encoder_half_channels_last_latents_are_consumed_without_repack():
     rend = build_renderer(spec)
     rend.forced_seed = 3
     with torch.no_grad():
-        net.encode(images, poses, torch.tensor(spec["focal"]))
+        net.encode(images, poses, camera_tensors(spec)[0])
     lat32 = net.encoder.latent.clone()
     assert lat32.shape == (2, 256, H // 16, W // 16)
     ref = rend(net, rays).coarse.rgb.cpu()                         # fp32 trunk -> pnr_pack_latents -> fp16 kernel
     net.encoder.half_dtype = torch.float16
     with torch.no_grad():
-        net.encode(images, poses, torch.tensor(spec["focal"]))
+        net.encode(images, poses, camera_tensors(spec)[0])
     m16 = net.encoder.level_maps16(torch.float16)
     assert m16 is not None and m16[0].dtype == torch.float16 and m16[0].is_contiguous(memory_format=torch.channels_last)
     rel = float((m16[0].float() - lat32).abs().max() / lat32.abs().max())
@@ -930,7 +930,7 @@ def test_fused_kernel_shape_space(n_blocks, combine_layer, NS, lat, proj, prec):
     noise = dict(noise_c=torch.rand(n, spec["Kc"], generator=g), u=torch.rand(n, n_imp, generator=g),
                  r=torch.rand(n, n_imp, generator=g), g=torch.randn(n, spec["Kfd"], generator=g))
     W, H = spec["image"]
-    cam = orc.encode_cameras(torch.from_numpy(poses), spec["focal"], None, W, H)
+    cam = orc.encode_cameras(torch.from_numpy(poses), *gu.intrinsics(spec), W, H)
     sd = {w: {k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, w).items()} for w in ("coarse", "fine")}
     with torch.no_grad():
         ref = orc.render(sd["coarse"], sd["fine"], cam, [torch.from_numpy(x) for x in gu.make_latents(spec)],

@@ -419,3 +419,52 @@ def test_calc_losses_batches(monkeypatch):
     same = inds[:1].expand(SB, -1).contiguous().cuda()
     _, gt2 = real_batch(data["images"].cuda(), data["poses"].cuda(), data["focal"], data["c"], same, Z_NEAR, Z_FAR)
     assert torch.equal(gt2[1].cpu(), rgb_all[1][inds[0]]) and not torch.equal(gt2[0], gt2[1])
+
+
+@pytest.mark.parametrize("nviews", [[2], [1]])
+def test_calc_losses_forward_matches_the_oracle(nviews):
+    """The route above compares calc_losses with the HIP path driven by hand.  Here the batch calc_losses drew — its rays, its
+    source poses and its per-object focal (SB, 2) and c (SB, 2), as it handed them to net.encode — goes through orc.render
+    with the same explicit noise (rend.fixed_noise): out.coarse.rgb within 1e-4, the bound test_gradients_match_reference
+    holds the taped forward to."""
+    import train_fp64_util as tu
+    from oracle import pixelnerf_oracle as orc
+    from oracle_util import maxdiff
+    from pixel_nerf_multiscale_amd import train
+    from pixel_nerf_multiscale_amd.model.loss import RenderLoss
+    net, rend, data, kept = _front_end_setup()
+    spec = gu.CASES["tiny_ns2_codeview"]
+    SB, NV, _, H, W = data["images"].shape
+    noise = tu.make_noise(dict(spec, SB=SB, N=RAY_BATCH), 31)
+    rend.fixed_noise = {k: v.cuda() for k, v in noise.items()}
+    render_par = rend.bind_parallel(net, None)
+    seen = {}
+    real_encode = net.encode
+
+    def spy_encode(images, poses, focal, z_bounds=None, c=None):
+        seen.update(poses=poses.detach().cpu(), focal=focal.detach().cpu(), c=c.detach().cpu())
+        return real_encode(images, poses, focal, z_bounds, c=c)
+
+    def spy_render(rays, want_weights=True):
+        out = render_par(rays, want_weights=want_weights)
+        seen.update(rays=rays.detach().cpu(), out=out)
+        return out
+
+    net.encode = spy_encode
+    torch.manual_seed(13); np.random.seed(13)
+    train.calc_losses(net, spy_render, data, ray_batch_size=RAY_BATCH, nviews=nviews, z_near=Z_NEAR, z_far=Z_FAR,
+                      loss=RenderLoss(LAM_C, LAM_F))
+    NS = nviews[0]
+    assert tuple(seen["poses"].shape) == (SB, NS, 4, 4) and tuple(seen["focal"].shape) == tuple(seen["c"].shape) == (SB, 2)
+    assert torch.equal(seen["focal"], data["focal"][:, None].expand(SB, 2)) and torch.equal(seen["c"], data["c"])
+    assert not torch.equal(seen["focal"][0], seen["focal"][1]) and not torch.equal(seen["c"][0], seen["c"][1])
+    cam = orc.encode_cameras(seen["poses"], seen["focal"], seen["c"], W, H)
+    sd = lambda mlp: {k: v.detach().cpu() for k, v in mlp.state_dict().items()}
+    res = orc.render(sd(net.mlp_coarse), sd(net.mlp_fine), cam, [kept[-1].detach().cpu()], seen["rays"], NS, spec["Kc"], spec["Kf"],
+                     spec["Kfd"], spec["depth_std"], spec["white_bkgd"], spec["lindisp"], noise,
+                     use_code_viewdirs=spec["use_code_viewdirs"], n_blocks=spec["n_blocks"], combine_layer=spec["combine_layer"],
+                     combine_type=spec["combine_type"])
+    got = seen["out"]["coarse"]["rgb"].detach().cpu()
+    d = maxdiff(got, res["coarse"]["rgb"])
+    print(f"nviews={nviews}: max |coarse rgb - oracle| = {d:.3e}")
+    assert tuple(got.shape) == (SB, RAY_BATCH, 3) and d <= 1e-4

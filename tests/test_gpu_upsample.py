@@ -186,12 +186,12 @@ def test_upstream_mode_renders_through_the_unchanged_kernels():
     under the scaled camera is upstream's lookup (uv_scale = "image") under the original one (tests/test_gpu_uv_scale.py);
     the x and y ratios are equal here.  fp32 path: the 1e-4 of test_gpu_parity.  fp16 kernel against the fp32 path: FLOOR_DB on
     the coarse pass and FINE_E2E_FLOOR_DB end to end on the fine pass, as everywhere in test_gpu_parity."""
-    from hip_util import build_renderer
+    from hip_util import build_renderer, camera_tensors
     from oracle import pixelnerf_oracle as orc
     spec = _spec()
     rays, poses, images, noise = _inputs(spec, 64)
     W, H = spec["image"]
-    focal = torch.tensor(spec["focal"])
+    focal = camera_tensors(spec)[0]
     outs, nets = {}, {}
     for p in ("fp32", "fp16"):
         net = _upstream_net(spec, p)
@@ -212,7 +212,7 @@ def test_upstream_mode_renders_through_the_unchanged_kernels():
     # here and may have taken another convolution algorithm (fp32 sums of up to 2304 terms in another order)
     assert maxdiff(net.encoder.latent.cpu(), lat.float()) <= 1e-5 * float(lat.max())
     s = 16.0 / 32.0
-    cam = orc.encode_cameras(poses, spec["focal"], None, W, H)
+    cam = orc.encode_cameras(poses, *gu.intrinsics(spec), W, H)
     sd = {w: {k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, w).items()} for w in ("coarse", "fine")}
     with torch.no_grad():
         ref = orc.render(sd["coarse"], sd["fine"], (cam[0], cam[1] * s, cam[2] * s), [lat.float()], rays, spec["NS"],
@@ -252,10 +252,10 @@ def test_upstream_mode_trains_through_the_unchanged_kernels():
     of each level, so that nothing the convolutions below add is in it, and the repeated runs start from the level tensors the
     first run's trunk produced: the trunk's convolutions and batch norms are MIOpen's, forward as well as backward, and are not
     claimed reproducible — from the levels onwards (map, render, loss, render backward, the map's adjoint) everything is."""
-    from hip_util import build_renderer
+    from hip_util import build_renderer, camera_tensors
     spec = _spec()
     rays, poses, images, noise = _inputs(spec, 32)
-    focal = torch.tensor(spec["focal"])
+    focal = camera_tensors(spec)[0]
     target = torch.rand(1, 32, 3, generator=torch.Generator().manual_seed(8))
     net = _upstream_net(spec, "fp32").train()
     twin = copy.deepcopy(net)

@@ -52,7 +52,7 @@ def test_render_with_image_scaling_equals_the_fork_lookup_under_a_scaled_camera(
     C_, Hl, Wl = spec["lat"][0]
     sx, sy = Wl / W, Hl / H
     assert sx == sy
-    cam = orc.encode_cameras(torch.from_numpy(fx["poses"]), spec["focal"], None, W, H)
+    cam = orc.encode_cameras(torch.from_numpy(fx["poses"]), *gu.intrinsics(spec), W, H)
     cam_s = (cam[0], cam[1] * sx, cam[2] * sx)
     noise = noise_from_fixture(fx)
     sd_c = {k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, "coarse").items()}
@@ -103,7 +103,7 @@ def test_image_scaling_carries_into_the_gradients():
     G = torch.randn(out.shape, generator=g).cuda()
     (out * G).sum().backward()
     # oracle: same points, fork lookup, camera scaled per axis (uv_x * sx, uv_y * sy)
-    cam = orc.encode_cameras(torch.from_numpy(fx["poses"]), spec["focal"], None, W, H)
+    cam = orc.encode_cameras(torch.from_numpy(fx["poses"]), *gu.intrinsics(spec), W, H)
     s2 = torch.tensor([sx, sy])
     cam_s = (cam[0], cam[1] * s2, cam[2] * s2)
     zc = z.detach().cpu().double().requires_grad_(True)

@@ -9,10 +9,11 @@ from oracle import pixelnerf_oracle as orc
 from oracle_util import maxdiff, noise_from_fixture, oracle_render, oracle_setup
 
 ALL = sorted(gu.CASES)
+INTR = sorted(gu.INTRINSICS_CASES)      # per-object (fx, fy) and c on interior geometry: the oracle's per-object branch
 TOL = 2e-5   # fp32; the two sides differ only in summation order inside addmm / gather
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + INTR)
 def test_render_matches_reference(name):
     fx = gu.load_fixture(name)
     res = oracle_render(fx)
@@ -26,7 +27,7 @@ def test_render_matches_reference(name):
         assert maxdiff(res[lvl]["depth"], fx[f"{lvl}_depth"]) < TOL * max(span, 1.0) * 4, lvl
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + INTR)
 def test_point_outputs_match_reference(name):
     fx = gu.load_fixture(name)
     spec, cam, lat, sd_c, sd_f = oracle_setup(fx)
@@ -51,13 +52,15 @@ def test_point_outputs_match_reference(name):
         assert np.allclose(out.numpy(), fx["pts_out_fine"], rtol=1e-5, atol=TOL)
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + INTR)
 def test_encode_cameras(name):
     fx = gu.load_fixture(name)
     spec = fx["spec"]
     W, H = spec["image"]
-    w2c, focal, c = orc.encode_cameras(torch.from_numpy(fx["poses"]), spec["focal"], None, W, H)
+    w2c, focal, c = orc.encode_cameras(torch.from_numpy(fx["poses"]), *gu.intrinsics(spec), W, H)
     assert maxdiff(w2c, fx["enc_w2c"]) < 1e-6
+    assert tuple(focal.shape) == fx["enc_focal"].shape and tuple(c.shape) == fx["enc_c"].shape
+    assert focal.shape[0] == (spec["SB"] if name in INTR else 1)
     assert maxdiff(focal, fx["enc_focal"]) == 0
     assert maxdiff(c, fx["enc_c"]) == 0
     assert list(fx["enc_image_shape"]) == [W, H]

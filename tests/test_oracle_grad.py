@@ -71,7 +71,7 @@ def compare_grads(got, gfx, rtol, what, truth=None):
         assert abs(np.linalg.norm(g) - norm) <= rtol * norm + 1e-7, f"{what} {k}: norm {np.linalg.norm(g)} vs {norm}"
 
 
-@pytest.mark.parametrize("name", gu.GRAD_CASES)
+@pytest.mark.parametrize("name", gu.GRAD_CASES + sorted(gu.INTRINSICS_CASES))
 def test_oracle_autograd_matches_reference_gradients(name):
     fx = gu.load_fixture(name)
     gfx = gu.load_grad_fixture(name)

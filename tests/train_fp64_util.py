@@ -39,7 +39,7 @@ def fp64_leaves(spec, maps, sds=None, dtype=F64):
 
 def fp64_camera(spec, poses, dtype=F64):
     W, H = spec["image"]
-    return tuple(t.to(dtype) for t in orc.encode_cameras(torch.as_tensor(np.asarray(poses)), spec["focal"], None, W, H))
+    return tuple(t.to(dtype) for t in orc.encode_cameras(torch.as_tensor(np.asarray(poses)), *gu.intrinsics(spec), W, H))
 
 
 def fp64_forward(spec, rays, poses, maps, noise, sds=None, dtype=F64):

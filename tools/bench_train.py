@@ -136,7 +136,7 @@ def front_end(a):
         mse = torch.nn.MSELoss()
 
         def plain_cameras():                    # the other variants' encode() leaves their own source cameras behind
-            net.set_cameras(torch.from_numpy(poses_np).reshape(-1, 4, 4), torch.tensor(spec["focal"]), None, W, H)
+            net.set_cameras(torch.from_numpy(poses_np).reshape(-1, 4, 4), *hu.camera_tensors(spec), W, H)
 
         def step_plain():                       # the step this tool times without --front-end
             opt.zero_grad(set_to_none=True)

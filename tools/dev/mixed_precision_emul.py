@@ -92,7 +92,7 @@ def main():
                     Kf=0, Kfd=0, lindisp=w["lindisp"], white_bkgd=w["white"], use_code_viewdirs=False, z_near=w["z"][0],
                     z_far=w["z"][1], radius=w["radius"])
         poses = np.stack([gu.pose_spherical(30.0 * v, -20.0, w["radius"]) for v in range(w["NS"])])[None]
-        cam = orc.encode_cameras(torch.from_numpy(poses), spec["focal"], None, W_img, H_img)
+        cam = orc.encode_cameras(torch.from_numpy(poses), *gu.intrinsics(spec), W_img, H_img)
         lat = [torch.from_numpy(x) for x in gu.make_latents(spec)]
         sd = {k: torch.from_numpy(v) for k, v in gu.make_mlp_state(spec, "coarse").items()}
         tgt = gu.pose_spherical(75.0, -25.0, w["radius"])

@@ -13,7 +13,7 @@ tests/golden/.  The big tensors (MLP weights, latent maps) are regenerated from 
 golden_util, so they are not stored.
 
     python tools/gen_golden.py            # all cases
-    python tools/gen_golden.py tiny_ns1   # some cases
+    python tools/gen_golden.py tiny_ns1   # some cases (names of golden_util.CASES and INTRINSICS_CASES)
 """
 import importlib.machinery
 import importlib.util
@@ -151,7 +151,9 @@ def build_case(spec, NeRFRenderer, PixelNeRFNet):
     W, H = spec["image"]
     SB, NS = spec["SB"], spec["NS"]
     images = torch.zeros(SB, NS, 3, H, W)
-    net.encode(images, torch.from_numpy(poses_np), torch.tensor(spec["focal"], dtype=torch.float32))
+    focal, c = gu.intrinsics(spec)      # a scalar and None, or per-object (SB, 2) rows
+    net.encode(images, torch.from_numpy(poses_np), torch.as_tensor(focal, dtype=torch.float32),
+               c=None if c is None else torch.from_numpy(c))
 
     renderer = NeRFRenderer(
         n_coarse=spec["Kc"], n_fine=spec["Kf"], n_fine_depth=spec["Kfd"],
@@ -235,9 +237,10 @@ def run_case(name, spec, NeRFRenderer, PixelNeRFNet):
 
 def main():
     NeRFRenderer, PixelNeRFNet = load_reference()
-    names = sys.argv[1:] or list(gu.CASES)
+    cases = {**gu.CASES, **gu.INTRINSICS_CASES}
+    names = sys.argv[1:] or list(cases)
     for n in names:
-        run_case(n, gu.CASES[n], NeRFRenderer, PixelNeRFNet)
+        run_case(n, cases[n], NeRFRenderer, PixelNeRFNet)
 
 
 if __name__ == "__main__":

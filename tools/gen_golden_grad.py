@@ -91,7 +91,7 @@ def run(name, NeRFRenderer, PixelNeRFNet):
 
 def main():
     NeRFRenderer, PixelNeRFNet = gg.load_reference()
-    for n in sys.argv[1:] or gu.GRAD_CASES:
+    for n in sys.argv[1:] or gu.GRAD_CASES + list(gu.INTRINSICS_CASES):
         run(n, NeRFRenderer, PixelNeRFNet)
 
 
