@@ -30,7 +30,8 @@ extern "C" {
                                   * pnr_optim_plan / pnr_optim_workspace_bytes / pnr_adam_step; the visualisation panel and the colour map, pnr_cmap_workspace_bytes /
                                   * pnr_cmap / pnr_vis_panel_workspace_bytes / pnr_vis_panel; the video drivers' ends, pnr_video_frames /
                                   * pnr_view_strip / pnr_image_to_tensor; the approximate evaluation's batched metrics, pnr_eval_frames /
-                                  * pnr_eval_frames_workspace_bytes */
+                                  * pnr_eval_frames_workspace_bytes; the metrics of saved 8-bit images, pnr_eval_frames_u8 /
+                                  * pnr_eval_frames_u8_workspace_bytes */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -407,6 +408,29 @@ int32_t pnr_eval_frames(const float* rgb, int32_t rgb_stride   /* floats per pix
                         int32_t F, int32_t W, int32_t H, int32_t clamp,
                         double* metrics                        /* (F, 2): mse, mean SSIM */,
                         void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* F pairs of saved 8-bit images in one call: the arithmetic of eval/calc_metrics.py:218-234, which reads the PNGs eval.py
+ * wrote and the dataset's images back and recomputes PSNR and SSIM on them.  pred (F, H, W, pred_channels) and gt
+ * (F, H, W, gt_channels), uint8, dense and interleaved as a PNG decoder returns them, 3 or 4 channels each: frame f starts at
+ * byte f * H * W * channels, NO alignment is assumed (a 7 x 7 RGB frame is 147 bytes), and a fourth channel is never part of
+ * any result (the reference's [..., :3]).  x = float(p) / 255.0f, ONE correctly rounded fp32 division — the bits of
+ * imageio.imread(..).astype(np.float32) / 255.0, :226-227 — and g the same of the ground truth; on (x, g) the arithmetic of
+ * pnr_eval_frames, word for word: centred fp64 window moments, whole 7 x 7 windows only, divisor 48, C1 = 1e-4, C2 = 9e-4, one
+ * partial pair per 16 x 16 tile, the same fixed-order fold without atomics.  (The exact integer window sums 8-bit inputs
+ * would allow are deliberately not used: the reference's inputs are the rounded quotients, and the two entry points share one
+ * arithmetic.)  metrics[2 f] = mean squared error, metrics[2 f + 1] = mean SSIM of pair f, which depend on pair f's bytes only.
+ * pred_planar / gt_planar, when not NULL: x * 2.0f - 1.0f (two fp32 operations) as (F, 3, H, W), the LPIPS inputs of :232-233.
+ * One launch over F x tiles workgroups, then the fold with a workgroup per frame.  Every check is made before any launch:
+ *   PNR_E_NULL       pred, gt, metrics or workspace NULL
+ *   PNR_E_SHAPE      F < 1; min(W, H) < 7; a channel count other than 3 or 4; W * H >= 2^31; F x tiles > 2^23
+ *   PNR_E_WORKSPACE  fewer workspace bytes than the size function asks for (that of pnr_eval_frames; 0 for a bad shape) */
+uint64_t pnr_eval_frames_u8_workspace_bytes(int32_t F, int32_t W, int32_t H);
+int32_t pnr_eval_frames_u8(const uint8_t* pred, int32_t pred_channels   /* (F, H, W, pred_channels), 3 or 4 */,
+                           const uint8_t* gt, int32_t gt_channels       /* (F, H, W, gt_channels), 3 or 4 */,
+                           int32_t F, int32_t W, int32_t H,
+                           float* pred_planar, float* gt_planar         /* (F, 3, H, W) each, or NULL */,
+                           double* metrics                              /* (F, 2): mse, mean SSIM */,
+                           void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* ---- visualisation: the colour map of src/util/util.py:13-30 and the panel of train/train.py:423-537 (vis_step), csrc/vis.hip -- */
 /* quantize(map), the reference's image_float_to_uint8 for a float32 map:

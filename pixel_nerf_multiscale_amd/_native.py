@@ -157,6 +157,8 @@ PROTOTYPES = {
     "pnr_eval_frame": (_i32, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _f, _f, _fp, _fp, _fp, _fp, _fp, _u64, _fp]),
     "pnr_eval_frames_workspace_bytes": (_u64, [_i32, _i32, _i32]),
     "pnr_eval_frames": (_i32, [_fp, _i32, _i64, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _u64, _fp]),
+    "pnr_eval_frames_u8_workspace_bytes": (_u64, [_i32, _i32, _i32]),
+    "pnr_eval_frames_u8": (_i32, [_fp, _i32, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _u64, _fp]),
     "pnr_cmap_workspace_bytes": (_u64, [_i32, _i32]),
     "pnr_cmap": (_i32, [_fp, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _u64, _fp]),
     "pnr_vis_panel_workspace_bytes": (_u64, [_i32, _i32, _i32]),

@@ -3,7 +3,8 @@
 // normalised depth (:288-289), and the two numbers finish.txt is made of — the mean squared error behind PSNR and the mean
 // SSIM (:324-332, as evalio.ssim restates skimage: uniform 7x7 window, sample covariance, whole windows only, per channel).
 // Latency-bound: a 128 x 128 frame is 64 workgroups; the point is that nothing waits on the host.
-// And the two numbers alone for F frames in one call, clamped or not: the tail of eval/eval_approx.py:136-148 (pnr_eval_frames).
+// And the two numbers alone for F frames in one call, clamped or not: the tail of eval/eval_approx.py:136-148 (pnr_eval_frames),
+// and for F pairs of 8-bit interleaved frames as a PNG decoder returns them: eval/calc_metrics.py:218-234 (pnr_eval_frames_u8).
 #include "frame_common.h"
 
 namespace pnr {
@@ -155,6 +156,62 @@ __global__ void __launch_bounds__(FRAME_THREADS) k_eval_frames(EvalFramesArgs a)
     if (tid == 0) { a.part[2 * (int64_t)blockIdx.x] = se; a.part[2 * (int64_t)blockIdx.x + 1] = ss; }
 }
 
+// F pairs of 8-bit interleaved frames in one launch (eval/calc_metrics.py:218-234: the saved PNGs against the dataset's images).
+// Another load in front of the same sums: x = p / 255.0f, one correctly rounded fp32 division — the bits of
+// imread(..).astype(np.float32) / 255.0 — for the render and for the ground truth; a fourth channel is stepped over ([..., :3]).
+// Byte loads: a frame may start at any address.  The thread that owns a pixel also writes x * 2 - 1 of both images to the
+// planar (F, 3, H, W) outputs, the LPIPS inputs of :232-233, when they are asked for.
+struct EvalFramesU8Args {
+    const uint8_t* pred; const uint8_t* gt;
+    int pred_ch, gt_ch, W, H, tiles_x, tiles;
+    float* pred_planar; float* gt_planar;          // (F, 3, H, W) each, or NULL
+    double* part;                                  // (F, tiles, 2)
+};
+
+__device__ __forceinline__ void eval_tile_load_u8(const uint8_t* pred, int pred_ch, const uint8_t* gt, int gt_ch, int W, int H,
+                                                  int x0, int y0, EvalTile& sx, EvalTile& sg, int tid) {
+    for (int i = tid; i < EV_LDS * EV_LDS; i += FRAME_THREADS) {
+        const int ly = i / EV_LDS, lx = i % EV_LDS;
+        const int gy = y0 - EV_HALO + ly, gx = x0 - EV_HALO + lx;
+        float v[3] = {0.0f, 0.0f, 0.0f}, g[3] = {0.0f, 0.0f, 0.0f};       // outside the image: never part of a whole window
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            const int64_t pix = (int64_t)gy * W + gx;
+            const uint8_t* p = pred + pix * pred_ch;
+            const uint8_t* q = gt + pix * gt_ch;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { v[c] = __fdiv_rn((float)p[c], 255.0f); g[c] = __fdiv_rn((float)q[c], 255.0f); }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { sx[c][ly][lx] = v[c]; sg[c][ly][lx] = g[c]; }
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(FRAME_THREADS) k_eval_frames_u8(EvalFramesU8Args a) {
+    __shared__ EvalTile sx, sg;
+    __shared__ double red[2][FRAME_THREADS];
+    const int tid = threadIdx.x, tx = tid & (FRAME_TILE - 1), ty = tid / FRAME_TILE;
+    const int f = (int)blockIdx.x / a.tiles, tile = (int)blockIdx.x % a.tiles;
+    const auto [x0, y0] = tile_origin(tile, a.tiles_x);
+    const int W = a.W, H = a.H;
+    const int64_t HW = (int64_t)W * H;
+    eval_tile_load_u8(a.pred + f * HW * a.pred_ch, a.pred_ch, a.gt + f * HW * a.gt_ch, a.gt_ch, W, H, x0, y0, sx, sg, tid);
+
+    const int gy = y0 + ty, gx = x0 + tx;
+    const int cy = ty + EV_HALO, cx = tx + EV_HALO;
+    if (gy < H && gx < W) {
+        const int64_t at = (int64_t)f * 3 * HW + (int64_t)gy * W + gx;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {                                      // x * 2.0 - 1.0: two fp32 operations, the product exact
+            if (a.pred_planar) a.pred_planar[at + c * HW] = __fsub_rn(__fmul_rn(sx[c][cy][cx], 2.0f), 1.0f);
+            if (a.gt_planar) a.gt_planar[at + c * HW] = __fsub_rn(__fmul_rn(sg[c][cy][cx], 2.0f), 1.0f);
+        }
+    }
+    double se, ss;
+    eval_tile_sums(sx, sg, W, H, x0, y0, red, tid, se, ss);
+    if (tid == 0) { a.part[2 * (int64_t)blockIdx.x] = se; a.part[2 * (int64_t)blockIdx.x + 1] = ss; }
+}
+
 // One workgroup per FRAME (one for k_eval_frame): thread t adds the frame's tiles t, t + 256, .. in ascending order, then
 // block_sum2 — no atomics, the same inputs give the same bits, and a frame's pair is made of that frame's partial pairs alone.
 // metrics[2 f] = mean squared error over 3 H W elements, metrics[2 f + 1] = mean SSIM over 3 (H - 6)(W - 6) windows.
@@ -241,6 +298,33 @@ extern "C" int32_t pnr_eval_frames(const float* rgb, int32_t rgb_stride, int64_t
     a.rgb_stride = rgb_stride; a.W = W; a.H = H; a.tiles_x = frame_tiles_x(W); a.tiles = (int)tiles; a.clamp = clamp;
     a.part = (double*)workspace;
     hipLaunchKernelGGL(k_eval_frames, dim3((unsigned)(F * tiles)), dim3(FRAME_THREADS), 0, (hipStream_t)stream, a);
+    PNR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)F), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)workspace,
+                       (int)tiles, W, H, metrics);
+    PNR_LAUNCH_CHECK();
+    return PNR_OK;
+}
+
+// the pairs of pnr_eval_frames: the same F x tiles partial pairs
+extern "C" uint64_t pnr_eval_frames_u8_workspace_bytes(int32_t F, int32_t W, int32_t H) {
+    return pnr_eval_frames_workspace_bytes(F, W, H);
+}
+
+extern "C" int32_t pnr_eval_frames_u8(const uint8_t* pred, int32_t pred_channels, const uint8_t* gt, int32_t gt_channels, int32_t F,
+                                      int32_t W, int32_t H, float* pred_planar, float* gt_planar, double* metrics, void* workspace,
+                                      uint64_t workspace_bytes, void* stream) {
+    if (!pred || !gt || !metrics || !workspace) return PNR_E_NULL;
+    if (F < 1 || !frame_pixels_ok(W, H) || W < EV_WIN || H < EV_WIN) return PNR_E_SHAPE;
+    if ((pred_channels != 3 && pred_channels != 4) || (gt_channels != 3 && gt_channels != 4)) return PNR_E_SHAPE;
+    const int64_t tiles = frame_tiles(W, H);
+    if (tiles > FRAME_MAX_TILES / F) return PNR_E_SHAPE;                  // F x tiles workgroups in one launch
+    if (workspace_bytes < pnr_eval_frames_u8_workspace_bytes(F, W, H)) return PNR_E_WORKSPACE;
+    EvalFramesU8Args a;
+    a.pred = pred; a.gt = gt; a.pred_ch = pred_channels; a.gt_ch = gt_channels;
+    a.W = W; a.H = H; a.tiles_x = frame_tiles_x(W); a.tiles = (int)tiles;
+    a.pred_planar = pred_planar; a.gt_planar = gt_planar;
+    a.part = (double*)workspace;
+    hipLaunchKernelGGL(k_eval_frames_u8, dim3((unsigned)(F * tiles)), dim3(FRAME_THREADS), 0, (hipStream_t)stream, a);
     PNR_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)F), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)workspace,
                        (int)tiles, W, H, metrics);

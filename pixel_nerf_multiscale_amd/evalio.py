@@ -15,7 +15,10 @@ per-frame work (clamp, quantisation, PSNR / SSIM sums, normalised depth) to the 
                               encode -> render -> clamp -> metrics -> finish.txt (resume), on this package's renderer
 * evaluate_approx()           reference eval/eval_approx.py:89-153     the development loop: one random target view per
                               object, a loader batch of objects per render call, metrics on the UNclamped frames
+* calc_metrics()              reference eval/calc_metrics.py:119-340   PSNR / SSIM (and an LPIPS hook) of the SAVED PNGs against
+                              the dataset's image files: metrics.txt per object (map), all_metrics.txt (reduce)
 """
+import json
 import math
 import os
 import warnings
@@ -419,7 +422,9 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
     pinned host buffers, asynchronously; the host waits ONCE per object, before it writes that object's files and its
     finish.txt line.  PSNR is 10 log10(1 / mse) on the host in fp64.  Under a process group every rank computes the metrics
     (the return value is the same everywhere) and rank 0 alone copies bytes out and writes.  A ground truth whose size differs
-    from the render's (scale != 1 with comparison) is a ValueError: there is no resampling on the device."""
+    from the render's (scale != 1 with comparison) is a ValueError: there is no resampling on the device.
+
+    finish.txt holds the metrics of the unquantised frames; calc_metrics() recomputes them on the PNGs written here."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
     dev = net.poses.device
@@ -666,3 +671,382 @@ def evaluate_approx(net, renderer, loader, *, source="64", seed=1234, z_near=Non
     if verbose:
         print("final psnr", total_psnr / cnt, "ssim", total_ssim / cnt)
     return total_psnr / cnt, total_ssim / cnt, cnt
+
+
+# ------------------------------------------------------------------------------------ metrics of the saved PNGs (calc_metrics.py)
+DTU_BAD_VIEWS = (3, 4, 5, 6, 7, 16, 17, 18, 19, 20, 21, 36, 37, 38, 39)        # calc_metrics.py:143-145
+METRIC_NAMES = ("psnr", "ssim", "lpips")                                      # calc_metrics.py:275, the order of every line
+
+
+def _image_layout(dataset_format, list_name):
+    """-> (name of the object list file or "", name of an object's image folder or ""), calc_metrics.py:101-112."""
+    if dataset_format == "dvr":
+        return list_name + ".lst", "image"
+    if dataset_format == "srn":
+        return "", "rgb"
+    if dataset_format == "nerf":
+        warnings.warn("test split not implemented for NeRF synthetic data format")
+        return "", ""
+    raise NotImplementedError("Not supported data format " + str(dataset_format))
+
+
+def _view_ids(x):
+    """"0 1 2", a sequence or a tensor of view indices, or None -> list of int."""
+    if x is None:
+        return []
+    if isinstance(x, str):
+        return [int(v) for v in x.split()]
+    return [int(v) for v in (x.tolist() if torch.is_tensor(x) else x)]
+
+
+def _metric_objects(datadir, output, list_file, multicat, verbose):
+    """Object discovery of calc_metrics.py:159-183 -> [(dataset folder, render folder)] of the objects whose render folder
+    exists, categories in sorted order and the objects sorted inside each."""
+    cats = sorted(os.listdir(datadir)) if multicat else ["."]
+    all_objs, total = [], 0
+    if verbose:
+        print("CATEGORICAL SUMMARY")
+    for cat in cats:
+        cat_root = os.path.join(datadir, cat)
+        if not os.path.isdir(cat_root):
+            continue
+        objs = sorted(os.listdir(cat_root))
+        if list_file:
+            with open(os.path.join(cat_root, list_file)) as f:
+                split = {x.strip() for x in f.readlines()}
+            objs = [x for x in objs if x in split]
+        pairs = [(os.path.join(cat_root, x), os.path.join(output, cat + "_" + x if multicat else x)) for x in objs]
+        pairs = [p for p in pairs if os.path.isdir(p[0])]
+        avail = [p for p in pairs if os.path.exists(p[1])]
+        if verbose:
+            print(cat, "TOTAL", len(pairs), "AVAILABLE", len(avail))
+        total += len(pairs)
+        all_objs.extend(avail)
+    if verbose:
+        print(">>> USING", len(all_objs), "OF", total, "OBJECTS")
+    return all_objs
+
+
+def _counted_views(im_root, rend_path, exclude, eval_views):
+    """The (ground-truth file, render file) pairs calc_metrics.py:205, :218-225 counts, in its order."""
+    pairs = []
+    for im_name in sorted(os.listdir(im_root)):
+        stem, ext = os.path.splitext(im_name)
+        if ext != ".jpg" and ext != ".png":
+            continue
+        view = int(stem)
+        rend = os.path.join(rend_path, "{:06}.png".format(view))
+        if os.path.exists(rend) and view not in exclude and (eval_views is None or view in eval_views):
+            pairs.append((os.path.join(im_root, im_name), rend))
+    return pairs
+
+
+def _read_u8(path, modes):
+    """(H, W, 3 | 4) uint8 of an 8-bit image file whose PIL mode is one of `modes`."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode not in modes:
+            raise ValueError(f"{path}: image mode {im.mode!r}, expected 8-bit {' or '.join(modes)}")
+        return np.asarray(im, dtype=np.uint8)
+
+
+def _lpips_mean(lpips, preds, gts, batch):
+    """calc_metrics.py:238-246: the callable on batches of `batch` pairs, the mean of everything it returned."""
+    vals = [torch.as_tensor(lpips(p, g)).reshape(-1).double() for p, g in zip(torch.split(preds, batch, 0), torch.split(gts, batch, 0))]
+    return torch.cat(vals).mean().item()
+
+
+class _PngMetrics:
+    """One object's pairs -> (psnr_sum, ssim_sum, lpips mean or None); name: the object, for the messages."""
+
+    def _pair(self, name, gt_path, rend_path, shape):
+        gt, pred = _read_u8(gt_path, ("RGB", "RGBA")), _read_u8(rend_path, ("RGB",))
+        if gt.shape[:2] != pred.shape[:2]:
+            raise ValueError(f"{name}: {rend_path} is {pred.shape[1]} x {pred.shape[0]}, {gt_path} is {gt.shape[1]} x {gt.shape[0]}")
+        if shape is not None and pred.shape[:2] != shape:
+            raise ValueError(f"{name}: images of two sizes, {shape[1]} x {shape[0]} and {pred.shape[1]} x {pred.shape[0]}")
+        return gt, pred
+
+
+class _PngHost(_PngMetrics):
+    """metrics="host", the reference's recipe (:226-233): fp32 / 255 arrays, psnr and ssim one pair at a time."""
+
+    def __init__(self, lpips, lpips_batch_size, device):
+        self.lpips, self.batch, self.dev = lpips, lpips_batch_size, device
+
+    def __call__(self, name, pairs):
+        psnr_sum = ssim_sum = 0.0
+        shape, gts, preds = None, [], []
+        for gt_path, rend_path in pairs:
+            gt, pred = self._pair(name, gt_path, rend_path, shape)
+            shape = pred.shape[:2]
+            gt = gt.astype(np.float32)[..., :3] / 255.0
+            pred = pred.astype(np.float32) / 255.0
+            psnr_sum += float(psnr(pred, gt, data_range=1))
+            ssim_sum += ssim(pred, gt, data_range=1)
+            if self.lpips is not None:
+                gts.append(torch.from_numpy(np.ascontiguousarray(gt)).permute(2, 0, 1) * 2.0 - 1.0)
+                preds.append(torch.from_numpy(pred).permute(2, 0, 1) * 2.0 - 1.0)
+        if self.lpips is None:
+            return psnr_sum, ssim_sum, None
+        gts, preds = torch.stack(gts), torch.stack(preds)
+        if self.dev is not None:
+            gts, preds = gts.to(self.dev), preds.to(self.dev)
+        return psnr_sum, ssim_sum, _lpips_mean(self.lpips, preds, gts, self.batch)
+
+
+class _PngDevice(_PngMetrics):
+    """metrics="device": the object's pairs are decoded into two pinned byte buffers, uploaded once per chunk of frames_per_call
+    frames, one util.eval_frames_u8 call per chunk writes its rows of the object's (n, 2) buffer, and the host reads that
+    buffer once.  A frame's row depends on that frame's bytes alone, so the chunk size does not change a bit."""
+
+    def __init__(self, lpips, lpips_batch_size, device, frames_per_call):
+        self.lpips, self.batch, self.dev, self.chunk, self.pin = lpips, lpips_batch_size, device, int(frames_per_call), {}
+        if self.chunk < 1:
+            raise ValueError(f"frames_per_call must be >= 1, got {frames_per_call}")
+
+    def _pinned(self, key, shape, dtype):
+        t = self.pin.get(key)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self.pin[key] = torch.empty(shape, dtype=dtype, pin_memory=True)
+        return t
+
+    def __call__(self, name, pairs):
+        n, shape, pred_h, gt_h, gt_np = len(pairs), None, None, None, []
+        for i, (gt_path, rend_path) in enumerate(pairs):
+            gt, pred = self._pair(name, gt_path, rend_path, shape)
+            if shape is None:
+                shape = pred.shape[:2]
+                if min(shape) < 7:
+                    raise ValueError(f"{name}: {shape[1]} x {shape[0]} images hold no whole 7 x 7 SSIM window")
+                pred_h = self._pinned("pred", (n, *shape, 3), torch.uint8)
+            pred_h[i].numpy()[...] = pred
+            gt_np.append(gt)
+        gc = 4 if all(g.shape[2] == 4 for g in gt_np) else 3              # RGBA travels as it is; a mix is cut to RGB here
+        gt_h = self._pinned("gt%d" % gc, (n, *shape, gc), torch.uint8)
+        for i, g in enumerate(gt_np):
+            gt_h[i].numpy()[...] = g[..., :gc]
+        rows = torch.empty(n, 2, dtype=torch.float64, device=self.dev)
+        planar = []
+        for a in range(0, n, self.chunk):
+            b = min(n, a + self.chunk)
+            out = util.eval_frames_u8(pred_h[a:b].to(self.dev, non_blocking=True), gt_h[a:b].to(self.dev, non_blocking=True),
+                                      want_planar=self.lpips is not None, metrics_out=rows[a:b])
+            if self.lpips is not None:
+                planar.append(out[1:])
+        rows_h = self._pinned("rows", (n, 2), torch.float64)
+        rows_h.copy_(rows, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(self.dev))
+        done.synchronize()                                                  # the one wait of this object
+        psnr_sum = ssim_sum = 0.0
+        for mse, s in rows_h.tolist():
+            psnr_sum += _psnr_of_mse(mse)
+            ssim_sum += s
+        if self.lpips is None:
+            return psnr_sum, ssim_sum, None
+        preds, gts = torch.cat([p[0] for p in planar]), torch.cat([p[1] for p in planar])
+        return psnr_sum, ssim_sum, _lpips_mean(self.lpips, preds, gts, self.batch)
+
+
+def metrics_map(datadir, output, *, dataset_format="dvr", list_name="softras_test", multicat=False, viewlist="",
+                eval_view_list=None, primary="", exclude_dtu_bad=False, overwrite=False, lpips=None, lpips_batch_size=32,
+                metrics="host", device=None, frames_per_call=256, verbose=True, rank=0, world=1):
+    """The map step of the reference's eval/calc_metrics.py (run_map, :119-254): "<output>/<obj>/metrics.txt" for every object
+    of the dataset folder `datadir` that has a render folder under `output` (evaluate(write_images=True) writes those).
+    The keyword arguments are the script's flags.  -> the list of metrics.txt paths this call wrote.
+
+    Objects (:159-183): the folders of datadir — of every category folder with multicat, the render folder is then
+    "<cat>_<obj>" — kept when the "<list_name>.lst" file of a "dvr" dataset names them and when their render folder exists;
+    the images of an object lie in "image" (dvr), "rgb" (srn) or the object folder itself (nerf) (:101-112).  An object whose
+    metrics.txt exists is skipped unless overwrite (:203-204).  Views (:205, :218-225): ground-truth files ending in .png or
+    .jpg, matched to "<view:06>.png" in the render folder, minus the excluded views, restricted to eval_view_list (a file or
+    indices).  PSNR and SSIM of every pair on the 8-bit values / 255 in fp32, against the first three channels of the ground
+    truth (:226-231); the per-object means go to metrics.txt as "psnr {}\nssim {}" (:247-251).
+
+    metrics="host": evalio.psnr / evalio.ssim, one pair at a time.  metrics="device": util.eval_frames_u8
+    (pnr_eval_frames_u8), frames_per_call pairs per call on `device` (None = the current HIP device); the host waits once per
+    object and PSNR is 10 log10(1 / mse) on the host in fp64.
+    lpips: a callable (pred, gt) -> n values for two (n, 3, H, W) float32 tensors in [-1, 1], called per batch of
+    lpips_batch_size pairs (:238-246) — on the kernel's planar outputs with the device back end, on host tensors moved to
+    `device` with the host back end; its mean is written as a third line "lpips {}".  None: no such line (the reference always
+    writes one; its lpips package and weights are not part of this project).
+    rank, world: this call takes the objects i of the list with i % world == rank.
+
+    Images are read with PIL: 8-bit RGB, or RGBA for the ground truth; the render must be RGB.  ValueError for any other
+    mode (naming the file), for a pair or an object of two sizes, for an object without a counted view (the reference
+    divides by zero there) and for an object the viewlist does not list.
+
+    Deliberate difference: with viewlist (a file or a dict as read_source_view_lut returns it) the excluded views are the
+    union of the table's views for "<cat>/<obj>" (:212-213), `primary` and the DTU list; the reference itself raises there
+    (:216 calls .extend on a tensor).  This step follows the reference by reading only: it cannot run here (it needs lpips and
+    a CUDA device), so it is unpinned, and SSIM is this module's restatement of skimage as everywhere else."""
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
+    list_file, img_dir = _image_layout(dataset_format, list_name)
+    lut = None
+    if isinstance(viewlist, str):
+        if viewlist:
+            if verbose:
+                print("Excluding views from list", viewlist)
+            lut = read_source_view_lut(viewlist)
+    elif viewlist is not None:
+        lut = viewlist
+    base_exclude = set(_view_ids(primary)) | (set(DTU_BAD_VIEWS) if exclude_dtu_bad else set())
+    eval_views = None
+    if eval_view_list is not None:
+        eval_views = set(_view_ids(read_eval_view_list(eval_view_list) if isinstance(eval_view_list, str) else eval_view_list))
+        if verbose:
+            print("Only using views", sorted(eval_views))
+    if metrics == "device":
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        back = _PngDevice(lpips, lpips_batch_size, dev, frames_per_call)
+    else:
+        back = _PngHost(lpips, lpips_batch_size, device)
+    written = []
+    with torch.no_grad():
+        for i, (path, rend_path) in enumerate(_metric_objects(datadir, output, list_file, multicat, verbose and rank == 0)):
+            out_path = os.path.join(rend_path, "metrics.txt")
+            if i % world != rank or (os.path.exists(out_path) and not overwrite):
+                continue
+            name = os.path.basename(rend_path)
+            exclude = set(base_exclude)
+            if lut is not None:
+                key = name.replace("_", "/")                                # :212
+                if key not in lut:
+                    raise ValueError(f"{name}: the viewlist has no line for {key!r}")
+                exclude |= set(_view_ids(lut[key]))
+            pairs = _counted_views(os.path.join(path, img_dir) if img_dir else path, rend_path, exclude, eval_views)
+            if not pairs:
+                raise ValueError(f"{name}: no view to compare in {rend_path}")
+            psnr_sum, ssim_sum, lp = back(name, pairs)
+            txt = "psnr {}\nssim {}".format(psnr_sum / len(pairs), ssim_sum / len(pairs))
+            if lp is not None:
+                txt += "\nlpips {}".format(lp)
+            with open(out_path, "w") as f:
+                f.write(txt)
+            written.append(out_path)
+    return written
+
+
+def metrics_reduce(datadir, output, *, multicat=False, metadata="metadata.yaml", dtu_sort=False, verbose=True):
+    """The reduce step of the reference's eval/calc_metrics.py (run_reduce, :257-340), pinned byte for byte by
+    tests/golden/calc_metrics_reduce.npz: the metrics.txt of every folder of `output` whose name does not start with "_", in
+    sorted order — by the scan number of "scan<N>" with dtu_sort (:264-271) —, running sums per metric and, with multicat, per
+    category (the part of the folder name before the first "_"), divided by the counts; "<output>/all_metrics.txt" holds, with
+    multicat, one line "{:12s} psnr: {:.6f} .. n_inst: {}" per category that has objects — its name from the first entry of
+    datadir/<metadata>["<cat>"]["name"], a file read as JSON as the reference does — then "---" and the "total" line, and
+    the line of totals alone otherwise.  -> the dict of means (name -> mean, and "<cat>.<name>" with multicat); its .text is what
+    was written.
+
+    The metric names are those found in the files, in the reference's order psnr, ssim, lpips (the reference always has all
+    three; metrics_map writes no lpips line without an lpips callable).  ValueError for files that disagree about the names,
+    for a name outside those three, for a category the metadata does not list, and for no object at all."""
+    if multicat:
+        with open(os.path.join(datadir, metadata)) as f:
+            meta = json.load(f)
+        cats = sorted(meta.keys())
+        cat_description = {cat: meta[cat]["name"].split(",")[0] for cat in cats}
+    objs = [x for x in os.listdir(output) if x[0] != "_" and os.path.isdir(os.path.join(output, x))]
+    objs = sorted(objs, key=lambda x: int(x[4:])) if dtu_sort else sorted(objs)
+    if not objs:
+        raise ValueError(f"{output}: no object folder to reduce")
+    if verbose:
+        print(">>> PROCESSING", len(objs), "OBJECTS")
+    names, sums, cat_sz = None, {}, {cat: 0 for cat in cats} if multicat else {}
+    for obj in objs:
+        with open(os.path.join(output, obj, "metrics.txt")) as f:
+            rows = [line.split() for line in f.readlines()]
+        found = [r[0] for r in rows]
+        if names is None:
+            if any(n not in METRIC_NAMES for n in found) or len(set(found)) != len(found) or not found:
+                raise ValueError(f"{obj}/metrics.txt: metric names {found}, expected some of {list(METRIC_NAMES)}")
+            names = [n for n in METRIC_NAMES if n in found]
+            for n in names:
+                sums[n] = 0.0
+                for cat in cat_sz:
+                    sums[cat + "." + n] = 0.0
+        if sorted(found) != sorted(names):
+            raise ValueError(f"{obj}/metrics.txt has the metrics {found}, the objects before it {names}")
+        if multicat:
+            cat = obj.split("_")[0]
+            if cat not in cat_sz:
+                raise ValueError(f"{obj}: category {cat!r} is not in {metadata}")
+            cat_sz[cat] += 1
+            for metric, val in rows:
+                sums[cat + "." + metric] += float(val)
+        for metric, val in rows:
+            sums[metric] += float(val)
+    for n in names:
+        for cat in cat_sz:
+            if cat_sz[cat] > 0:
+                sums[cat + "." + n] /= cat_sz[cat]
+        sums[n] /= len(objs)
+    lines = []
+    if multicat:
+        for cat in cats:
+            if cat_sz[cat] > 0:
+                txt = "{:12s}".format(cat_description[cat])
+                for n in names:
+                    txt += " {}: {:.6f}".format(n, sums[cat + "." + n])
+                lines.append(txt + " n_inst: {}".format(cat_sz[cat]))
+        total = "---\n{:12s}".format("total")
+    else:
+        total = ""
+    for n in names:
+        total += " {}: {:.6f}".format(n, sums[n])
+    lines.append(total)
+    text = "\n".join(lines)
+    out_path = os.path.join(output, "all_metrics.txt")
+    with open(out_path, "w") as f:
+        f.write(text)
+    if verbose:
+        print("WROTE", out_path)
+        print(text)
+    return MetricTotals(sums, text)
+
+
+class MetricTotals(dict):
+    """What metrics_reduce returns: the means by name; .text: the contents of all_metrics.txt."""
+
+    def __init__(self, values, text):
+        super().__init__(values)
+        self.text = text
+
+
+def calc_metrics(datadir, output, *, dataset_format="dvr", list_name="softras_test", multicat=False, viewlist="",
+                 eval_view_list=None, primary="", exclude_dtu_bad=False, overwrite=False, reduce_only=False,
+                 metadata="metadata.yaml", dtu_sort=False, lpips=None, lpips_batch_size=32, metrics="host", device=None,
+                 frames_per_call=256, verbose=True):
+    """The reference's eval/calc_metrics.py, the step after eval.py: metrics_map (unless reduce_only), then metrics_reduce; the
+    keyword arguments are the script's flags (see the two functions) plus this package's metrics / device / frames_per_call /
+    verbose.  -> the MetricTotals of metrics_reduce.
+
+    evaluate() already puts PSNR / SSIM into finish.txt, but of the unquantised frames: the published tables, and the
+    per-category table of the NMR experiment, are the metrics of the PNGs, which this recomputes from the files alone.
+
+    Under an initialised process group object i of the list belongs to rank i % world; every object has its own metrics.txt,
+    so there is nothing to merge: a barrier, rank 0 reduces, and one broadcast gives every rank rank 0's totals."""
+    sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    rank, world = (dist.get_rank(), dist.get_world_size()) if sharded else (0, 1)
+    if not reduce_only:
+        if verbose and rank == 0:
+            print(">>> Compute")
+        metrics_map(datadir, output, dataset_format=dataset_format, list_name=list_name, multicat=multicat, viewlist=viewlist,
+                    eval_view_list=eval_view_list, primary=primary, exclude_dtu_bad=exclude_dtu_bad, overwrite=overwrite,
+                    lpips=lpips, lpips_batch_size=lpips_batch_size, metrics=metrics, device=device,
+                    frames_per_call=frames_per_call, verbose=verbose, rank=rank, world=world)
+    elif metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
+    if sharded:
+        dist.barrier()                  # every rank's metrics.txt files are written
+    totals = None
+    if rank == 0:
+        if verbose:
+            print(">>> Reduce")
+        totals = metrics_reduce(datadir, output, multicat=multicat, metadata=metadata, dtu_sort=dtu_sort, verbose=verbose)
+    if sharded:
+        box = [None if totals is None else (dict(totals), totals.text)]
+        dist.broadcast_object_list(box, src=0)
+        totals = MetricTotals(*box[0])
+    return totals

@@ -401,6 +401,36 @@ def eval_frames(rgb, gt, *, clamp=False, metrics_out=None):
     return metrics
 
 
+def eval_frames_u8(pred_u8, gt_u8, *, want_planar=False, metrics_out=None):
+    """The metrics of eval_frames for F pairs of saved 8-bit images, on the GPU by libpnr_hip (pnr_eval_frames_u8): what
+    eval/calc_metrics.py:218-234 does with the PNGs eval.py wrote.  pred_u8, gt_u8: uint8 device tensors (F, H, W, 3 | 4),
+    interleaved as a PNG decoder returns them (a non-dense view is made dense); a fourth channel is never read into a result.
+    x = p / 255 in fp32 (the bits of imread(..).astype(np.float32) / 255.0), then the arithmetic of eval_frames.
+    -> (F, 2) float64 on the device, rows [mean squared error, mean SSIM]; with want_planar -> (metrics, pred_planar,
+    gt_planar), the two (F, 3, H, W) float32 tensors x * 2 - 1, the LPIPS inputs of :232-233.  metrics_out: a contiguous
+    (F, 2) float64 device tensor to write into.  Nothing here waits for the device; PSNR is the caller's, on the host."""
+    from . import _native as N
+    for name, t in (("pred_u8", pred_u8), ("gt_u8", gt_u8)):
+        if t.dim() != 4 or t.dtype != torch.uint8 or t.shape[3] not in (3, 4):
+            raise ValueError(f"{name} must be uint8 (F, H, W, 3 or 4), got {t.dtype} {tuple(t.shape)}")
+    F, H, W, pc = (int(s) for s in pred_u8.shape)
+    if F < 1 or tuple(gt_u8.shape[:3]) != (F, H, W):
+        raise ValueError(f"gt_u8 must be ({F}, {H}, {W}, 3 or 4) with F >= 1, got {tuple(gt_u8.shape)}")
+    dev = N.same_device(pred_u8, gt_u8, metrics_out)
+    pred_u8, gt_u8 = pred_u8.contiguous(), gt_u8.contiguous()
+    metrics = torch.empty(F, 2, dtype=torch.float64, device=dev) if metrics_out is None else metrics_out
+    if tuple(metrics.shape) != (F, 2) or metrics.dtype != torch.float64 or not metrics.is_contiguous():
+        raise ValueError(f"metrics_out must be a contiguous float64 ({F}, 2), got {metrics.dtype} {tuple(metrics.shape)}")
+    pred_planar = torch.empty(F, 3, H, W, dtype=torch.float32, device=dev) if want_planar else None
+    gt_planar = torch.empty(F, 3, H, W, dtype=torch.float32, device=dev) if want_planar else None
+    nbytes = int(N.lib.pnr_eval_frames_u8_workspace_bytes(F, W, H))
+    ws = N.scratch(nbytes, dev)
+    N.check(N.lib.pnr_eval_frames_u8(pred_u8.data_ptr(), pc, gt_u8.data_ptr(), int(gt_u8.shape[3]), F, W, H, N.dptr(pred_planar),
+                                     N.dptr(gt_planar), metrics.data_ptr(), ws.data_ptr(), nbytes, N.current_stream(dev)),
+            "pnr_eval_frames_u8")
+    return (metrics, pred_planar, gt_planar) if want_planar else metrics
+
+
 def _upsample_sizes(shapes):
     arr = lambda k: (C.c_int32 * len(shapes))(*[int(s[k]) for s in shapes])
     return arr(1), arr(2), arr(3)
