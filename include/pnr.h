@@ -31,7 +31,8 @@ extern "C" {
                                   * pnr_cmap / pnr_vis_panel_workspace_bytes / pnr_vis_panel; the video drivers' ends, pnr_video_frames /
                                   * pnr_view_strip / pnr_image_to_tensor; the approximate evaluation's batched metrics, pnr_eval_frames /
                                   * pnr_eval_frames_workspace_bytes; the metrics of saved 8-bit images, pnr_eval_frames_u8 /
-                                  * pnr_eval_frames_u8_workspace_bytes */
+                                  * pnr_eval_frames_u8_workspace_bytes; the camera gradients, pnr_point_mlp_bwd_cam /
+                                  * pnr_train_bwd_cam_workspace_bytes */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -277,6 +278,42 @@ int32_t pnr_point_mlp_bwd(const pnr_params* params, const pnr_mlp* mlp, const pn
                           const float* out, const float* d_out, void* tape, uint64_t tape_bytes,
                           const pnr_mlp_grads* grads, float* const* d_latent, float* d_xyz, float* d_z,
                           void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* pnr_point_mlp_bwd plus the camera gradients the reference's autograd gives (xyz = o + z d, the view directions, and
+ * self.poses / self.focal / self.c, models.py.backup2:108-150,166-221).  Three more outputs, each may be NULL:
+ *   d_dirs   (n_points, 3)  explicit mode only: gradient at viewdirs
+ *   d_rays   (n_rays, 8)    rays mode only: columns 0:3 d(origin), 3:6 d(direction); columns 6:8 (near, far) are written
+ *                           as exact zeros (the reference's are not: a documented deviation)
+ *   d_cam    (n_objs*n_views, 16), 16-byte aligned: per stored view [dR 9, row-major | dt 3 | dfx dfy dcx dcy], the gradient
+ *            at views->w2c and at the (fx, fy, cx, cy) that view reads (fy in its stored, negated form).  A caller whose
+ *            focal / c hold fewer rows than views sums the records of the views that share a row.
+ * Every output is written (=), not accumulated.  With all three NULL the call is pnr_point_mlp_bwd: same launches, same
+ * workspace.  A mode / output mismatch (d_rays with explicit points, d_dirs with rays) returns PNR_E_SHAPE before any launch.
+ * workspace: pnr_train_bwd_cam_workspace_bytes(mlp, views, n_points, want_point = d_dirs or d_rays wanted, want_cam);
+ * with both flags 0 it equals pnr_train_bwd_workspace_bytes.
+ *
+ * Arithmetic, for point g and view v (R, t the stored w2c rows, p and d the world point and direction, xr = R p,
+ * xc = xr + t, dr = R d; du, dv the gradient at the pixel coordinate with the level's uv scale applied):
+ *   ddr   = gradient at dr: the identity and sine entries of the 6-wide code (use_code_viewdirs), else the three raw columns
+ *   dt    = (du (-fx/zc), dv (-fy/zc), du xc fx/zc^2 + dv yc fy/zc^2)       the projection's share only: the positional code
+ *                                                                          reads xr without t
+ *   dxr   = dt + gradient of the positional code at xr
+ *   dR[i][j] = dxr[i] p[j] + ddr[i] d[j];  dfx = du (-xc/zc), dfy = dv (-yc/zc), dcx = du, dcy = dv
+ *   d_dir = sum_v R^T ddr,  dp = sum_v R^T dxr;  per ray d_o = sum_k dp_k, d_d = sum_k (z_k dp_k + d_dir_k)
+ * Summation order (no floating-point atomics; every output is bit-reproducible): the (point, view) records are fp32; the
+ * points of an (object, view) are cut into chunks of 1024; inside a chunk sub-sum s = 0..15 adds records s, s+16, .. in that
+ * order in fp64 and the 16 sub-sums are added in order s = 0..15; the chunk sums are folded in chunk order in fp64 and
+ * rounded once to fp32.  The per-ray sums run over k = 0..K-1 in fp64 and are rounded once. */
+uint64_t pnr_train_bwd_cam_workspace_bytes(const pnr_mlp* mlp, const pnr_views* views, int64_t n_points,
+                                           int32_t want_point, int32_t want_cam);
+int32_t pnr_point_mlp_bwd_cam(const pnr_params* params, const pnr_mlp* mlp, const pnr_views* views,
+                              const float* rays, const float* z, int32_t K,
+                              const float* xyz, const float* viewdirs,
+                              int64_t n_points, int64_t points_per_obj,
+                              const float* out, const float* d_out, void* tape, uint64_t tape_bytes,
+                              const pnr_mlp_grads* grads, float* const* d_latent, float* d_xyz, float* d_z,
+                              float* d_dirs, float* d_rays, float* d_cam,
+                              void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* Backward of pnr_composite (render/nerf.py:178-182,223-249).  d_weights / d_rgb / d_depth may be NULL (zero);
  * writes d_rgbsigma (N,K,4) and, when non-NULL, d_z (N,K) (deltas and depth depend on z). */

@@ -147,6 +147,10 @@ PROTOTYPES = {
     "pnr_point_mlp_bwd": (_i32, [C.POINTER(pnr_params), C.POINTER(pnr_mlp), C.POINTER(pnr_views), _fp, _fp, _i32, _fp, _fp,
                                  _i64, _i64, _fp, _fp, _fp, _u64, C.POINTER(pnr_mlp_grads), C.POINTER(C.c_void_p), _fp, _fp,
                                  _fp, _u64, _fp]),
+    "pnr_train_bwd_cam_workspace_bytes": (_u64, [C.POINTER(pnr_mlp), C.POINTER(pnr_views), _i64, _i32, _i32]),
+    "pnr_point_mlp_bwd_cam": (_i32, [C.POINTER(pnr_params), C.POINTER(pnr_mlp), C.POINTER(pnr_views), _fp, _fp, _i32, _fp, _fp,
+                                     _i64, _i64, _fp, _fp, _fp, _u64, C.POINTER(pnr_mlp_grads), C.POINTER(C.c_void_p), _fp, _fp,
+                                     _fp, _fp, _fp, _fp, _u64, _fp]),
     "pnr_composite_bwd": (_i32, [_fp, _fp, _fp, _i64, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
     "pnr_sample_fine_bwd": (_i32, [_fp, _fp, _i64, _i32, _i32, _i32, _f, _fp, _u64, _i64, _fp, _fp, _fp, _fp]),
     "pnr_gen_rays": (_i32, [C.POINTER(C.c_float), _i32, _i32, _f, _f, _f, _f, _f, _f, _i64, _i64, _fp, _fp]),

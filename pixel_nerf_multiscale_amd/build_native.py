@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpnr_hip.so")
-SOURCES = ["pnr_api.hip", "stage_kernels.hip", "point_f32.hip", "point_mfma.hip", "train_f32.hip", "loss.hip", "eval.hip",
+SOURCES = ["pnr_api.hip", "stage_kernels.hip", "point_f32.hip", "point_mfma.hip", "train_f32.hip", "cam_grad.hip", "loss.hip", "eval.hip",
            "mesh.hip", "optim.hip", "upsample.hip", "vis.hip", "video.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

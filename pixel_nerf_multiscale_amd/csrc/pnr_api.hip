@@ -1,4 +1,5 @@
 // C-ABI entry points: argument validation, workspace carving, stage sequencing on the caller's stream.
+#include "cam_grad.h"
 #include "pnr_common.h"
 
 namespace pnr {
@@ -34,7 +35,7 @@ int32_t point_train_fwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_vie
 int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, PointSrc src, int64_t P,
                   int64_t pts_per_obj, const float* out, const float* d_out, void* tape, uint64_t tape_bytes,
                   const pnr_mlp_grads* gr, float* const* d_latent, float* d_xyz, float* d_z, void* workspace,
-                  uint64_t ws_bytes, hipStream_t s);
+                  uint64_t ws_bytes, hipStream_t s, const CamGradOut* cam = nullptr);
 }  // namespace pnr
 
 using namespace pnr;
@@ -229,6 +230,42 @@ extern "C" int32_t pnr_point_mlp_bwd(const pnr_params* params, const pnr_mlp* ml
     if (n_points == 0) return PNR_OK;
     return point_bwd(params, mlp, views, src, n_points, points_per_obj, out, d_out, tape, tape_bytes, grads, d_latent,
                      d_xyz, d_z, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// The camera outputs' scratch follows the backward's own workspace, on the next 256-byte boundary.
+extern "C" uint64_t pnr_train_bwd_cam_workspace_bytes(const pnr_mlp* mlp, const pnr_views* views, int64_t n_points,
+                                                      int32_t want_point, int32_t want_cam) {
+    if (!mlp || !views || n_points < 0) return 0;
+    const uint64_t base = train_bwd_workspace_bytes(mlp, views, n_points);
+    const uint64_t extra = cam_grad_workspace_bytes(views, n_points, want_point != 0, want_cam != 0);
+    return extra ? round_up_256(base) + extra : base;
+}
+
+extern "C" int32_t pnr_point_mlp_bwd_cam(const pnr_params* params, const pnr_mlp* mlp, const pnr_views* views,
+                                         const float* rays, const float* z, int32_t K, const float* xyz,
+                                         const float* viewdirs, int64_t n_points, int64_t points_per_obj,
+                                         const float* out, const float* d_out, void* tape, uint64_t tape_bytes,
+                                         const pnr_mlp_grads* grads, float* const* d_latent, float* d_xyz, float* d_z,
+                                         float* d_dirs, float* d_rays, float* d_cam, void* workspace,
+                                         uint64_t workspace_bytes, void* stream) {
+    PointSrc src;
+    int32_t rc = point_args(params, mlp, views, rays, z, K, xyz, viewdirs, n_points, points_per_obj, &src);
+    if (rc) return rc;
+    if (!out || !d_out || !grads || ((!tape || !workspace) && n_points > 0)) return PNR_E_NULL;
+    if ((((uintptr_t)out | (uintptr_t)d_out) & 15) != 0) return PNR_E_ALIGN;
+    if (d_cam && ((uintptr_t)d_cam & 15) != 0) return PNR_E_ALIGN;
+    if (rays ? d_xyz != nullptr : d_z != nullptr) return PNR_E_SHAPE;   // d_z goes with rays, d_xyz with explicit points
+    if (rays ? d_dirs != nullptr : d_rays != nullptr) return PNR_E_SHAPE;   // d_rays goes with rays, d_dirs with explicit points
+    if (n_points == 0) return PNR_OK;
+    const bool want_point = d_dirs || d_rays;
+    if (!want_point && !d_cam)
+        return point_bwd(params, mlp, views, src, n_points, points_per_obj, out, d_out, tape, tape_bytes, grads, d_latent,
+                         d_xyz, d_z, workspace, workspace_bytes, (hipStream_t)stream);
+    if (workspace_bytes < pnr_train_bwd_cam_workspace_bytes(mlp, views, n_points, want_point, d_cam != nullptr)) return PNR_E_WORKSPACE;
+    const uint64_t base = round_up_256(train_bwd_workspace_bytes(mlp, views, n_points));
+    const CamGradOut cam{d_dirs, d_rays, d_cam, (uint8_t*)workspace + base, workspace_bytes - base};
+    return point_bwd(params, mlp, views, src, n_points, points_per_obj, out, d_out, tape, tape_bytes, grads, d_latent,
+                     d_xyz, d_z, workspace, base, (hipStream_t)stream, &cam);
 }
 
 struct RenderWs { uint64_t zc, zf, rgbs, w, rgb, depth, rays, point, total; };

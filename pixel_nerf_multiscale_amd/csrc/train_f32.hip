@@ -11,6 +11,7 @@
 // out = lin_out(relu(x)); rgb = sigmoid, sigma = relu.
 #include <type_traits>
 
+#include "cam_grad.h"
 #include "f32_kernels.h"
 
 namespace pnr {
@@ -2401,7 +2402,7 @@ int32_t point_train_fwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_vie
 int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, PointSrc src, int64_t P,
                   int64_t pts_per_obj, const float* out, const float* d_out, void* tape, uint64_t tape_bytes,
                   const pnr_mlp_grads* gr, float* const* d_latent, float* d_xyz, float* d_z, void* workspace,
-                  uint64_t ws_bytes, hipStream_t s) {
+                  uint64_t ws_bytes, hipStream_t s, const CamGradOut* cam /* camera gradients (cam_grad.hip), or null */) {
     if (tape_bytes < train_tape_bytes_p(prm, mlp, vw, P)) return PNR_E_WORKSPACE;
     if (ws_bytes < train_bwd_workspace_bytes(mlp, vw, P)) return PNR_E_WORKSPACE;
     const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden, E = feature_stride(mlp);
@@ -2421,10 +2422,11 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
     float* lat_part = (float*)wp;          wp += round_up_256(latent_part_bytes(vw, P));
     uint8_t* lat_q = wp;                   // [scale words (256 B)][fixed-point maps], latent_q_bytes
     const bool want_p = d_xyz || d_z;
+    const bool want_code = want_p || cam;      // the gradient at the code columns of dzx
     bool want_lat = false;
     LatGrad lg{};
     for (int l = 0; l < vw->n_levels; ++l) { lg.p[l] = d_latent ? d_latent[l] : nullptr; want_lat |= lg.p[l] != nullptr; }
-    const bool want_dz = L > 0 && (want_lat || want_p);
+    const bool want_dz = L > 0 && (want_lat || want_code);
 
     hipLaunchKernelGGL(k_out_act_bwd, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const float4*)out,
                        (const float4*)d_out, P, (float4*)do4);
@@ -2481,8 +2483,8 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
     }
     const Mat gx = f32_only(g), code = f32_mat(t.zx + L, E);
     PNR_TRY((grad_w<false>(gx, code, gr->lin_in_w, Din, gr->lin_in_b, MV, H, Din, half, dws, s)));
-    if ((want_p || want_lat) && L > 0 && !dz_started) PNR_HIP_CHECK(hipMemsetAsync(dzx, 0, (size_t)MV * E * 4, s));
-    if (want_p)
+    if ((want_code || want_lat) && L > 0 && !dz_started) PNR_HIP_CHECK(hipMemsetAsync(dzx, 0, (size_t)MV * E * 4, s));
+    if (want_code)
         PNR_TRY((gemm<false, true>(gx, plain_weight(mlp->lin_in_w, Din), nullptr, NO_MAT, NO_MAT, f32_mat(dzx + L, E), MV, Din, H,
                                    half, s)));
     // small single-level map: latent gradient on per-block partial maps + an ordered reduction (bit-reproducible)
@@ -2533,6 +2535,7 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
                            prm->use_code_viewdirs, prm->num_freqs, prm->freq_factor, dzx, E, lg, d_xyz, d_z);
         PNR_LAUNCH_CHECK();
     }
+    if (cam) PNR_TRY(cam_grad_launch(prm, vw, src, P, pts_per_obj, L, dzx, E, *cam, s));
     if (fixed_point) {
         for (int l = 0; l < vw->n_levels; ++l) {
             if (!lg.q[l]) continue;

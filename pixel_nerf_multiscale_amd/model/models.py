@@ -281,8 +281,8 @@ class PixelNeRFNet(torch.nn.Module):
 
     def wants_grad(self, *inputs):
         """True when the call must go through the differentiable (fp32, taped) path: the module is in training
-        mode (or `differentiable` is forced True), autograd is on, and a parameter, a latent map or one of `inputs`
-        requires grad.  Everything else — eval(), torch.no_grad() — takes the fused inference kernels."""
+        mode (or `differentiable` is forced True), autograd is on, and a parameter, a latent map, a stored source
+        camera (poses / focal / c) or one of `inputs` requires grad.  Everything else — eval(), torch.no_grad() — takes the fused inference kernels."""
         if self.differentiable is not None:
             if not self.differentiable:
                 return False
@@ -291,6 +291,8 @@ class PixelNeRFNet(torch.nn.Module):
         if not torch.is_grad_enabled():
             return False
         if any(t is not None and t.requires_grad for t in inputs):
+            return True
+        if self.poses.requires_grad or self.focal.requires_grad or self.c.requires_grad:    # source cameras under autograd
             return True
         if any(p.requires_grad for p in self.mlp_coarse.parameters()):
             return True

@@ -44,8 +44,9 @@ def _train_params(net):
 
 class PointMLP(torch.autograd.Function):
     """out (n_points, 4) = PixelNeRFNet.forward at points named by rays+z (a, b = rays (N,8), z (N,K)) or
-    explicitly (a, b = xyz (SB*P,3), viewdirs (SB*P,3)).  Differentiable in b=z / a=xyz, the MLP parameters
-    and the latent maps."""
+    explicitly (a, b = xyz (SB*P,3), viewdirs (SB*P,3)).  Differentiable in a and b, the stored cameras (poses, focal, c:
+    pnr_point_mlp_bwd_cam, called only when one of them or the rays / view directions asks), the MLP parameters and the
+    latent maps.  Columns 6:8 of d(rays) are exact zeros."""
 
     @staticmethod
     def forward(ctx, hdr, a, b, poses, focal, c, *tensors):
@@ -102,18 +103,48 @@ class PointMLP(torch.autograd.Function):
             d_pos = torch.empty_like(a)
         g = _grads_struct_from(hdr, g_par)
         dl = (C.c_void_p * N.PNR_MAX_LEVELS)(*[N.dptr(t) for t in g_map])
-        ws = N.scratch(N.lib.pnr_train_bwd_workspace_bytes(C.byref(m), C.byref(v), n_points), dev)
         d_out = N.f32c(d_out)
         K = b.shape[1] if rays_mode else 0
         args = (N.ptr(a), N.ptr(b), K, None, None) if rays_mode else (None, None, 0, N.ptr(a), N.ptr(b))
-        N.check(N.lib.pnr_point_mlp_bwd(C.byref(hdr["prm"]), C.byref(m), C.byref(v), *args, n_points,
-                                        n_points // v.n_objs, N.ptr(out), N.ptr(d_out), tape.data_ptr(), tape.numel(),
-                                        C.byref(g), dl,
-                                        None if rays_mode else N.ptr(d_pos), N.ptr(d_pos) if rays_mode else None,
-                                        ws.data_ptr(), ws.numel(), N.current_stream(dev)), "pnr_point_mlp_bwd")
-        g_a = d_pos if not rays_mode else None
-        g_b = d_pos if rays_mode else None
-        return (None, g_a, g_b, None, None, None, *g_par, *g_map)
+        head = (C.byref(hdr["prm"]), C.byref(m), C.byref(v), *args, n_points, n_points // v.n_objs, N.ptr(out), N.ptr(d_out),
+                tape.data_ptr(), tape.numel(), C.byref(g), dl,
+                None if rays_mode else N.ptr(d_pos), N.ptr(d_pos) if rays_mode else None)
+        # the camera outputs: the other member of (a, b) — the rays, or the view directions — and the stored cameras
+        want_other = need[1] if rays_mode else need[2]
+        want_cam = need[3] or need[4] or need[5]
+        if not (want_other or want_cam):
+            ws = N.scratch(N.lib.pnr_train_bwd_workspace_bytes(C.byref(m), C.byref(v), n_points), dev)
+            N.check(N.lib.pnr_point_mlp_bwd(*head, ws.data_ptr(), ws.numel(), N.current_stream(dev)), "pnr_point_mlp_bwd")
+            return (None, d_pos if not rays_mode else None, d_pos if rays_mode else None, None, None, None, *g_par, *g_map)
+        d_other = torch.empty_like(a if rays_mode else b) if want_other else None
+        d_cam = torch.empty(v.n_objs * v.n_views, 16, device=dev) if want_cam else None
+        ws = N.scratch(N.lib.pnr_train_bwd_cam_workspace_bytes(C.byref(m), C.byref(v), n_points, int(bool(want_other)),
+                                                               int(bool(want_cam))), dev)
+        N.check(N.lib.pnr_point_mlp_bwd_cam(*head, None if rays_mode else N.ptr(d_other), N.ptr(d_other) if rays_mode else None,
+                                            N.ptr(d_cam), ws.data_ptr(), ws.numel(), N.current_stream(dev)),
+                "pnr_point_mlp_bwd_cam")
+        g_a, g_b = (d_other, d_pos) if rays_mode else (d_pos, d_other)
+        g_poses = g_focal = g_c = None
+        if want_cam:
+            nv = d_cam.shape[0]
+            if need[3]:
+                g_poses = torch.cat((d_cam[:, :9].reshape(nv, 3, 3), d_cam[:, 9:12].reshape(nv, 3, 1)), dim=2).reshape(poses.shape)
+            g_focal = _rows_as_stored(d_cam[:, 12:14], focal, v.n_objs) if need[4] else None
+            g_c = _rows_as_stored(d_cam[:, 14:16], c, v.n_objs) if need[5] else None
+        return (None, g_a, g_b, g_poses, g_focal, g_c, *g_par, *g_map)
+
+
+def _rows_as_stored(d_view, stored, n_objs):
+    """Per-view intrinsics gradients (n_views_total, 2) summed into the rows the caller stored: one row for all views, one
+    per object (views_from repeats those per view) or one per view.  torch sums on the device, in a fixed order."""
+    nv, rows = d_view.shape[0], stored.shape[0]
+    if rows == nv:
+        return d_view.reshape(stored.shape)
+    if rows == 1:
+        return d_view.sum(0, keepdim=True).reshape(stored.shape)
+    if rows == n_objs:
+        return d_view.reshape(n_objs, nv // n_objs, 2).sum(1).reshape(stored.shape)
+    raise ValueError(f"{rows} intrinsics rows for {nv} views of {n_objs} objects")
 
 
 class Composite(torch.autograd.Function):

@@ -7,7 +7,11 @@ rays, 64 coarse + 32 fine samples, 1-3 source views).  Prints one JSON line per 
 and goes through train.calc_losses; timed in the same run, in alternating rounds: the step above (rays and targets made
 outside the loop), the calc_losses step, and a step whose front end is the reference's recipe in torch (gen_rays over
 every view + indexing, torch criteria, three .item()); and the two front ends alone.
-    python tools/bench_train.py --precision bf16 --front-end"""
+    python tools/bench_train.py --precision bf16 --front-end
+--cam-grad: the same step with camera gradients off (the step above: today's backward call) and on (the rays, the c2w source
+poses handed to set_cameras, focal and c require grad: pnr_point_mlp_bwd_cam), in alternating rounds of one run; medians and
+the spread of the rounds.
+    python tools/bench_train.py --precision bf16 --cam-grad"""
 import argparse
 import json
 import os
@@ -33,10 +37,13 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"])
     ap.add_argument("--front-end", action="store_true")
     ap.add_argument("--nv", type=int, default=50, help="--front-end: views per object in the batch")
-    ap.add_argument("--rounds", type=int, default=5, help="--front-end: alternating rounds of --steps steps; medians reported")
+    ap.add_argument("--rounds", type=int, default=5, help="--front-end / --cam-grad: alternating rounds of --steps steps; medians reported")
+    ap.add_argument("--cam-grad", action="store_true")
     a = ap.parse_args()
     if a.front_end:
         return front_end(a)
+    if a.cam_grad:
+        return cam_grad(a)
     for ns in a.views:
         spec = gu._case(seed=5, d_hidden=512, lat=[(256, 8, 8)], image=(128, 128), focal=131.25, NS=ns, SB=a.sb,
                         N=a.rays, Kc=64, Kf=32, Kfd=16)
@@ -71,6 +78,61 @@ def main():
         print(json.dumps({"what": "train_step", "sb": a.sb, "rays_per_obj": a.rays, "views": ns, "samples": "64+32",
                           "ms_per_step": round(ms, 2), "rays_per_s": round(n_rays / ms * 1e3),
                           "tflops_fwd_bwd": round(3 * flop_fwd / ms / 1e9, 1), "dtype": {"fp32": "f32", "bf16": "bf16 products, f32 accumulate", "bf16x3": "bf16x3 split products (fp32-class), f32 accumulate"}[a.precision]}))
+
+
+def cam_grad(a):
+    import statistics
+    W = H = 128
+    for ns in a.views:
+        spec = gu._case(seed=5, d_hidden=512, lat=[(256, 8, 8)], image=(W, H), focal=131.25, NS=ns, SB=a.sb,
+                        N=a.rays, Kc=64, Kf=32, Kfd=16)
+        rays_np, poses_np = gu.make_inputs(spec)
+        net = hu.build_net(spec, poses_np).train()
+        net.train_precision = a.precision
+        maps = [torch.from_numpy(x).cuda().requires_grad_(True) for x in gu.make_latents(spec)]
+        net.encoder.set_latents(maps)
+        rend = hu.build_renderer(spec)
+        rays = torch.from_numpy(rays_np).cuda()
+        tgt = torch.rand(a.sb, a.rays, 3, device="cuda")
+        opt = torch.optim.Adam([p for p in net.parameters() if p.requires_grad], lr=1e-4)
+        c2w = torch.from_numpy(poses_np).reshape(-1, 4, 4).cuda()
+        leaves = [t.requires_grad_(True) for t in (rays.clone(), c2w.clone(), torch.full((a.sb, 2), 131.25, device="cuda"),
+                                                   torch.full((a.sb, 2), 64.0, device="cuda"))]
+
+        def step(on):
+            opt.zero_grad(set_to_none=True)
+            if on:
+                for t in leaves:
+                    t.grad = None
+                net.set_cameras(*leaves[1:], W, H)          # the graph from the c2w / focal / c leaves, rebuilt every step
+            out = rend(net, leaves[0] if on else rays, want_weights=True)
+            loss = ((out.coarse.rgb - tgt) ** 2).mean() + ((out.fine.rgb - tgt) ** 2).mean()
+            loss.backward()
+            opt.step()
+
+        def cameras_off():
+            net.set_cameras(c2w, *hu.camera_tensors(spec), W, H)
+
+        ms = {"off": [], "on": []}
+        for r in range(-1, a.rounds):                       # round -1: warm-up
+            for k in ms:
+                if k == "off":
+                    cameras_off()
+                for _ in range(a.warmup if r < 0 else 0):
+                    step(k == "on")
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    step(k == "on")
+                torch.cuda.synchronize()
+                if r >= 0:
+                    ms[k].append((time.perf_counter() - t0) / a.steps * 1e3)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        print(json.dumps({"what": "train_step_cam_grad", "sb": a.sb, "rays_per_obj": a.rays, "views": ns, "precision": a.precision,
+                          "steps": a.steps, "rounds": a.rounds, "ms_off": round(med["off"], 3), "ms_on": round(med["on"], 3),
+                          "spread_ms_off": round(max(ms["off"]) - min(ms["off"]), 3),
+                          "spread_ms_on": round(max(ms["on"]) - min(ms["on"]), 3),
+                          "on_over_off": round(med["on"] / med["off"], 4)}))
 
 
 def _torch_front_end(data, dev, ray_batch_size, nviews, z_near, z_far):
