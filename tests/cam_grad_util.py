@@ -3,7 +3,9 @@
 Truth is torch autograd through the oracle in float64 with the cameras, the view directions or the rays as leaves.  The
 restatement (formula) forms the same gradients the way include/pnr.h states the kernels do — from the gradient at the
 assembled rows d(zx), the lookup's slope and the closed forms of dR, dt, dfx .. — and takes a `mutant`: one planted mistake,
-handed to the comparison rules as "kernel output" by tests/test_cam_grad_cpu.py.  Nothing here touches a GPU."""
+handed to the comparison rules as "kernel output" by tests/test_cam_grad_cpu.py.  The three-stage sum of the per-view
+outputs is restated apart from it (records, fold) with mistakes planted in its index arithmetic, for the cases with more than
+one chunk of 1024 points per (object, view).  Nothing here touches a GPU."""
 import numpy as np
 import torch
 
@@ -33,6 +35,16 @@ POINT_CASES = {
 P_SMALL = 3
 # rays mode: 37 rays (not a multiple of the four points a block holds once K is odd); K 24 = a sorted 16 + 8 set with repeated z
 RAY_CASES = {K: dict(lat=_L8, n_rays=37, K=K, seed=720 + K, NS=2, **fu.intr_rows(2)) for K in (1, 5, 24)}
+# more than one chunk of CAMG_CHUNK points per (object, view) (k_cam_partial / k_cam_fold): three objects of two views, so that
+# the object offset and the view stride are no power of two; a chunk one short of full, a full one, a one-point tail, and 17
+# points behind three full chunks.  TAIL_OBJ: the object whose last chunk alone carries the tail-only cotangent.
+CHUNK = 1024
+MULTI_P = (1023, 1024, 1025, 3 * CHUNK + 17)
+TAIL_OBJ = {1023: 1, 1024: 1, 1025: 2, 3 * CHUNK + 17: 2}
+# rays mode, two objects of two views, a row per object: (rays per object, K).  43 x 24 = 1032 points: ray 42 holds points
+# 1008 .. 1031, across the chunk boundary; 211 x 5 = 1055: an odd K and a 31-point tail.  The tail-only cotangent is object 1's.
+MULTI_RAYS = ((43, 24), (211, 5))
+RAY_TAIL_OBJ = 1
 _cache = {}
 
 
@@ -40,6 +52,30 @@ def point_case(name):
     if ("p", name) not in _cache:
         _cache["p", name] = fu.interior_case(**POINT_CASES[name])
     return _cache["p", name]
+
+
+def multi_case(P):
+    """SB 3, NS 2, P points per object, a focal and a c row per object."""
+    if ("m", P) not in _cache:
+        _cache["m", P] = fu.interior_case(lat=_L8, SB=3, NS=2, P=P, d_hidden=64, seed=770, **fu.intr_rows(3))
+    return _cache["m", P]
+
+
+def multi_ray_case(n_rays, K, SB=2, seed=780):
+    """fused_fp64_util.rays_case for SB objects: n_rays rays per object towards the object's own target camera (interior_case's),
+    K sorted depths each; rays (SB n_rays, 8), z (SB n_rays, K), object-major as render_train hands them over."""
+    if ("mr", n_rays, K, SB) not in _cache:
+        case = fu.interior_case(lat=_L8, SB=SB, NS=2, P=n_rays, d_hidden=64, seed=seed + K, **fu.intr_rows(SB))
+        spec = case["spec"]
+        W, H = spec["image"]
+        rng = np.random.default_rng((seed + K) * 1000 + 8)
+        rays = [gu.pinhole_rays(gu.pose_spherical(75.0 + 5.0 * sb, -25.0, spec["radius"]), W, H, spec["focal"], spec["z_near"],
+                                spec["z_far"], rng.integers(0, W * H, size=n_rays)) for sb in range(SB)]
+        z = np.sort(rng.uniform(spec["z_near"], spec["z_far"], size=(SB * n_rays, K)).astype(np.float32), axis=1)
+        case.update(rays=np.concatenate(rays).astype(np.float32), z=z)
+        case.pop("xyz"), case.pop("dirs")
+        _cache["mr", n_rays, K, SB] = case
+    return _cache["mr", n_rays, K, SB]
 
 
 def ray_case(K):
@@ -56,11 +92,30 @@ def ray_case(K):
     return _cache["r", K]
 
 
+MULTI_IDS = [("points", P) for P in MULTI_P] + [("rays", nk) for nk in MULTI_RAYS]
+
+
+def multi_truth(kind, key, cot_name):
+    """(case, cotangent, float64 truth, fp32 restatement) of a multi-chunk case under its "full" or "tail" cotangent, computed
+    once per process."""
+    if ("mt", kind, key, cot_name) not in _cache:
+        rays_mode = kind == "rays"
+        case = multi_ray_case(*key) if rays_mode else multi_case(key)
+        if cot_name == "tail":
+            cot = tail_cotangent(case, RAY_TAIL_OBJ if rays_mode else TAIL_OBJ[key], rays_mode)
+        else:
+            cot = cotangent(case, n_points=key[0] * key[1] if rays_mode else None, rays_mode=rays_mode)
+        _cache["mt", kind, key, cot_name] = (case, cot, point_truth(case, cot, rays_mode=rays_mode)[1],
+                                             point_truth(case, cot, dtype=torch.float32, rays_mode=rays_mode)[1])
+    return _cache["mt", kind, key, cot_name]
+
+
 def ray_points(case):
-    """(xyz (1, n K, 3), dirs) of a ray case in float64 from its fp32 rays and depths."""
+    """(xyz (SB, n K, 3), dirs) of a ray case in float64 from its fp32 rays and depths."""
+    SB = case["spec"]["SB"]
     r, z = case["rays"].astype(np.float64), case["z"].astype(np.float64)
     xyz = r[:, None, :3] + z[..., None] * r[:, None, 3:6]
-    return xyz.reshape(1, -1, 3), np.ascontiguousarray(np.broadcast_to(r[:, None, 3:6], xyz.shape)).reshape(1, -1, 3)
+    return xyz.reshape(SB, -1, 3), np.ascontiguousarray(np.broadcast_to(r[:, None, 3:6], xyz.shape)).reshape(SB, -1, 3)
 
 
 RELU_MARGIN = 2.0 ** -20       # 16 ulp of fp32, relative to the layer's largest input
@@ -111,6 +166,17 @@ def cotangent(case, n_points=None, seed=9, rays_mode=False):
     return cot
 
 
+def tail_cotangent(case, obj, rays_mode=False):
+    """cotangent() with everything zeroed but the points of the last chunk of CHUNK points of object `obj`: the only records
+    that are not exact zeros are that one chunk's, so a sum that leaves them out, or takes them into another object's or
+    view's row, has nothing else to hide the difference in."""
+    cot = cotangent(case, n_points=case["z"].size // case["spec"]["SB"] if rays_mode else None, rays_mode=rays_mode)
+    first = (cot.shape[1] - 1) // CHUNK * CHUNK
+    out = np.zeros_like(cot)
+    out[obj, first:] = cot[obj, first:]
+    return out
+
+
 def class_counts(case, xyz=None):
     """(interior fraction, clamped pairs, pairs behind a camera) of a case's (view, point) pairs, from the float64 geometry."""
     cls = fu.tap_class(case["spec"], case["poses"], case["xyz"] if xyz is None else xyz, None, case.get("uv_scale"))
@@ -143,8 +209,8 @@ def point_truth(case, cot, dtype=F64, rays_mode=False, sd=None):
     if rays_mode:
         rays = _leaf(case["rays"], dtype)
         z = torch.from_numpy(case["z"]).to(dtype)
-        xyz = (rays[:, None, :3] + z.unsqueeze(2) * rays[:, None, 3:6]).reshape(1, -1, 3)
-        dirs = rays[:, None, 3:6].expand(-1, z.shape[1], -1).reshape(1, -1, 3)
+        xyz = (rays[:, None, :3] + z.unsqueeze(2) * rays[:, None, 3:6]).reshape(spec["SB"], -1, 3)
+        dirs = rays[:, None, 3:6].expand(-1, z.shape[1], -1).reshape(spec["SB"], -1, 3)
         leaves = dict(rays=rays)
     else:
         xyz, dirs = _leaf(case["xyz"], dtype), _leaf(case["dirs"], dtype)
@@ -200,6 +266,30 @@ def _fold_rows(per_view, rows, SB, NS, as_per_view=False):
 
 def formula(case, cot, rays_mode=False, mutant=None):
     """include/pnr.h's arithmetic in float64 from the oracle's d(zx): dict(poses, focal, c, xyz, dirs | rays)."""
+    return _formula(case, cot, rays_mode, mutant)[0]
+
+
+def records(case, cot, rays_mode=False):
+    """k_cam_grad's records in float64, in the workspace's layout: (NS * SB * P, 16), row v * (SB P) + obj * P + point holds
+    [dR 9 | dt 3 | dfx dfy dcx dcy] of view v of the point's object — what fold() sums."""
+    spec = case["spec"]
+    rec = _formula(case, cot, rays_mode, None)[1]                       # (SB NS, P, 16), stored-view major
+    return rec.reshape(spec["SB"], spec["NS"], -1, 16).permute(1, 0, 2, 3).reshape(-1, 16).numpy()
+
+
+def cam_from_sums(case, sums):
+    """dict(poses, focal, c) from the (SB NS, 16) per-view sums: the stored w2c's layout and the intrinsics rows the case
+    stores (render/autograd.py's _rows_as_stored)."""
+    spec = case["spec"]
+    SB, NS = spec["SB"], spec["NS"]
+    focal, c = (t for t in tu.fp64_camera(spec, case["poses"], F64)[1:])
+    rec = np.asarray(sums, np.float64)
+    return dict(poses=np.concatenate((rec[:, :9].reshape(-1, 3, 3), rec[:, 9:12].reshape(-1, 3, 1)), axis=2),
+                focal=_fold_rows(rec[:, 12:14], focal.shape[0], SB, NS), c=_fold_rows(rec[:, 14:16], c.shape[0], SB, NS))
+
+
+def _formula(case, cot, rays_mode, mutant):
+    """(formula's dict, the per-(view, point) records (SB NS, P, 16) as a tensor)."""
     spec = case["spec"]
     SB, NS = spec["SB"], spec["NS"]
     nv = SB * NS
@@ -270,7 +360,8 @@ def formula(case, cot, rays_mode=False, mutant=None):
         dR = dR.transpose(-1, -2)
     dt_out = dxr if mutant == "dt := dxr" else dt
     intr = torch.stack((du * (-xc[..., 0] / zc), dv * (-xc[..., 1] / zc) * (-1.0 if mutant == "dfy sign" else 1.0), du, dv), dim=-1)
-    rec = torch.cat((dR.reshape(nv, P, 9), dt_out, intr), dim=-1).sum(1)          # (nv, 16)
+    rec_pv = torch.cat((dR.reshape(nv, P, 9), dt_out, intr), dim=-1)              # (nv, P, 16)
+    rec = rec_pv.sum(1)                                                           # (nv, 16)
     if mutant == "record of the next view":
         rec = torch.roll(rec, -1, dims=0)
     rec = rec.numpy()
@@ -289,7 +380,76 @@ def formula(case, cot, rays_mode=False, mutant=None):
         g["rays"] = torch.cat((dp.sum(1), d_d, torch.zeros(n, 2, dtype=F64)), dim=-1).numpy()
     else:
         g["xyz"], g["dirs"] = dp.numpy(), ddir.numpy()
-    return g
+    return g, rec_pv
+
+
+# ----------------------------------------------------------------------------- k_cam_partial and k_cam_fold, restated
+FOLD_MUTANTS = ("tail chunk dropped", "tail chunk read at a full chunk's length", "no object offset", "view stride pts_per_obj",
+                "chunk count and length from P", "partials indexed chunk * views + view", "fold stops one chunk early",
+                "second chunk in place of the first")
+
+
+def fold_mutant_acts(mutant, SB, NS, pts_per_obj, chunk=CHUNK):
+    """Whether the planted mistake changes a sum at these sizes."""
+    n_chunks = -(-pts_per_obj // chunk)
+    return {"tail chunk dropped": pts_per_obj % chunk != 0, "tail chunk read at a full chunk's length": pts_per_obj % chunk != 0,
+            "no object offset": SB > 1, "view stride pts_per_obj": SB > 1 and NS > 1, "chunk count and length from P": SB > 1,
+            "partials indexed chunk * views + view": n_chunks > 1 and SB * NS > 1, "fold stops one chunk early": True,
+            "second chunk in place of the first": n_chunks > 1}[mutant]
+
+
+# the cotangent under which a planted mistake must sit at MUTANT_FACTOR or more on EVERY case it acts on (the other one is
+# printed).  "full" only: under the tail-only cotangent of the LAST object the records a mistaken index reaches instead are
+# exact zeros (the next view's first objects, or nothing at all behind the last view), and at four chunks the first and the
+# second chunk are both zero.  "tail" only: a tail of 1 or 17 points is a share of the full sum that shrinks with P.
+FOLD_MUTANT_COTANGENT = {"tail chunk dropped": "tail", "tail chunk read at a full chunk's length": "full", "no object offset": "tail",
+                         "view stride pts_per_obj": "tail", "chunk count and length from P": "tail",
+                         "partials indexed chunk * views + view": "tail", "fold stops one chunk early": "tail",
+                         "second chunk in place of the first": "full"}
+
+
+def fold(records, SB, NS, pts_per_obj, chunk=CHUNK, mutant=None):
+    """k_cam_partial and k_cam_fold in float64 on records() -> the (SB NS, 16) per-view sums: per (object, view) and chunk, 16
+    sub-sums of the records s, s + 16, .. in that order, added in order s = 0 .. 15; the chunk sums folded in chunk order.
+    mutant: one mistake planted in the index arithmetic.  A read past the end of the records or of the partials gives zeros
+    here (on the device: whatever the workspace holds behind them).
+    "chunk count and length from P": in the kernel as it stands a block past an object's last chunk finds nothing left and
+    adds nothing, so a chunk count from P alone could never show; the planted form takes the length left from P as well and
+    runs on into the records that follow."""
+    rec = np.asarray(records, np.float64).reshape(-1, 16)
+    P = SB * pts_per_obj
+    assert rec.shape[0] == NS * P, (rec.shape, SB, NS, pts_per_obj)
+    views = SB * NS
+    per_obj = P if mutant == "chunk count and length from P" else pts_per_obj
+    n_chunks = -(-per_obj // chunk)
+    stride = pts_per_obj if mutant == "view stride pts_per_obj" else P
+    part = np.zeros((views * n_chunks + n_chunks + 1, 16))
+    for view in range(views):
+        obj, v = divmod(view, NS)
+        for ch in range(n_chunks):
+            first = ch * chunk
+            n = min(per_obj - first, chunk)
+            if mutant == "tail chunk dropped" and n < chunk:
+                continue
+            if mutant == "tail chunk read at a full chunk's length":
+                n = chunk
+            r0 = v * stride + (0 if mutant == "no object offset" else obj * pts_per_obj) + first
+            blk = np.zeros((-(-n // 16) * 16, 16))
+            got = rec[r0:r0 + n]
+            blk[:got.shape[0]] = got
+            blk = blk.reshape(-1, 16, 16)                                # [j, sub, comp]: record j * 16 + sub
+            sub = np.zeros((16, 16))
+            for j in range(blk.shape[0]):
+                sub += blk[j]
+            total = sub[0].copy()
+            for k in range(1, 16):
+                total += sub[k]
+            part[ch * views + view if mutant == "partials indexed chunk * views + view" else view * n_chunks + ch] = total
+    sums = np.zeros((views, 16))
+    for view in range(views):
+        for k in range(n_chunks - (1 if mutant == "fold stops one chunk early" else 0)):
+            sums[view] += part[view * n_chunks + (1 if mutant == "second chunk in place of the first" and k == 0 else k)]
+    return sums
 
 
 # ----------------------------------------------------------------------------- the rules
@@ -317,6 +477,48 @@ def compare(got, truth, ref32, what, check=True):
         tu.full_compare(_sel(got, POINT_KEYS), _sel(truth, POINT_KEYS), RTOL, what)
         tu.l2_compare(_sel(got, VIEW_KEYS), _sel(truth, VIEW_KEYS), RTOL, what, ref32=None if ref32 is None else _sel(ref32, VIEW_KEYS))
     return ratios
+
+
+def view_pieces(g):
+    """{label: array}: d(poses) split into the stored views (12 numbers each), d(focal) and d(c) into their stored rows."""
+    out = {}
+    for k in VIEW_KEYS:
+        if k in g:
+            a = np.asarray(g[k], dtype=np.float64)
+            a = a.reshape(-1, 12) if k == "poses" else a.reshape(-1, 2)
+            out.update({f"{k}[{i}]": a[i] for i in range(a.shape[0])})
+    return out
+
+
+def compare_per_view(got, truth, ref32, what, check=True):
+    """l2_compare(RTOL, ref32) on every stored view of d(poses) and every stored row of d(focal), d(c) on its own: a whole
+    tensor's l2 lets a view, or a short tail chunk of one, hide behind the others.  A piece whose truth is exactly zero (the
+    tail-only cotangent) must be exactly zero.  Prints and returns the worst piece: dict(piece, figure, ref, ratio) with
+    figure / ref the kernel's and the fp32 restatement's relative l2 and ratio = figure / bound (inf: not zero where the truth
+    is).  check=False asserts and prints nothing (the planted mistakes)."""
+    gp, tp, rp = view_pieces(got), view_pieces(truth), view_pieces(ref32)
+    assert gp.keys() == tp.keys() == rp.keys() and len(tp) > 0, (what, list(gp), list(tp))
+    worst, bad = dict(piece=None, figure=0.0, ref=0.0, ratio=-1.0), []
+    for k, t in tp.items():
+        if not t.any():
+            fig, ref = float(np.linalg.norm(gp[k])), float(np.linalg.norm(rp[k]))
+            ratio = 0.0 if not np.asarray(gp[k]).any() else np.inf              # a NaN is not zero either
+            if ratio:
+                bad.append(f"{k}: norm {fig:.3e} where the truth is exactly zero")
+        else:
+            fig, ref = tu.rel_l2({k: gp[k]}, {k: t})[k], tu.rel_l2({k: rp[k]}, {k: t})[k]
+            ratio = fig / max(RTOL, tu.L2_REF32_FACTOR * ref) if np.isfinite(fig) else np.inf
+            if check:
+                try:
+                    tu.l2_compare({k: gp[k]}, {k: t}, RTOL, what, ref32={k: rp[k]})
+                except AssertionError as e:
+                    bad.append(str(e))
+        if not ratio <= worst["ratio"]:
+            worst = dict(piece=k, figure=fig, ref=ref, ratio=ratio)
+    if check:
+        print(f"{what}: worst per view {worst['piece']} {worst['figure']:.1e} / {worst['ref']:.1e}")
+    assert not (check and bad), f"{what}, per view: " + "; ".join(bad)
+    return worst
 
 
 def table_line(what, got, truth, ref32):

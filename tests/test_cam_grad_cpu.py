@@ -1,6 +1,7 @@
 """Camera gradients without a GPU: the new exports and their refusals, the workspace size, the oracle against the reference's
 own camera gradients, the conditions the GPU cases (tests/test_gpu_cam_grad.py) rest on, and what the comparison rules reject —
-the kernels' arithmetic restated in float64 (cam_grad_util.formula) with one mistake planted, handed over as "kernel output"."""
+the kernels' arithmetic restated in float64 (cam_grad_util.formula) with one mistake planted, handed over as "kernel output";
+the same for the three-stage sum past one chunk of 1024 points (cam_grad_util.fold) under the per-view rule."""
 import ctypes as C
 
 import numpy as np
@@ -181,3 +182,137 @@ def test_restated_arithmetic_passes_and_every_planted_mistake_is_rejected(kind, 
         assert worst >= cg.MUTANT_FACTOR, (kind, key, mutant, r)
     print(f"\n{kind} {key}: " + "; ".join(lines))
     assert len(lines) >= 5
+
+
+# ----------------------------------------------------------------------------- more than one chunk of 1024 points
+@pytest.mark.parametrize("P", cg.MULTI_P)
+def test_multi_chunk_cases_meet_their_conditions(P):
+    case = cg.multi_case(P)
+    spec = case["spec"]
+    assert (spec["SB"], spec["NS"]) == (3, 2) and case["xyz"].shape == (3, P, 3)
+    assert np.shape(gu.intrinsics(spec)[0]) == (3, 2) and np.shape(gu.intrinsics(spec)[1]) == (3, 2)        # a row per object
+    frac, clamped, behind = cg.class_counts(case)
+    keep = cg.relu_keep(case)
+    first = (P - 1) // cg.CHUNK * cg.CHUNK
+    tail = keep[:, first:]
+    print(f"\nP {P}: interior {frac:.2f}, clamped pairs {clamped}, behind {behind}, masked {(~keep).mean():.4f}, "
+          f"tail points kept {tail.sum(1).tolist()} of {P - first}")
+    assert frac >= cg.MIN_INTERIOR and clamped > 0 and behind > 0
+    assert (~keep).mean() <= cg.MAX_MASKED
+    assert {1023: (1, 1023), 1024: (1, 1024), 1025: (2, 1), 3089: (4, 17)}[P] == (-(-P // cg.CHUNK), P - first)
+    if P > cg.CHUNK:
+        assert tail.all()                                     # every tail point of every object carries a cotangent
+    cot = cg.tail_cotangent(case, cg.TAIL_OBJ[P])
+    nz = np.abs(cot).sum(-1) > 0
+    assert nz[cg.TAIL_OBJ[P], first:].sum() == tail[cg.TAIL_OBJ[P]].sum() and nz.sum() == nz[cg.TAIL_OBJ[P], first:].sum()
+
+
+@pytest.mark.parametrize("n,K", cg.MULTI_RAYS)
+def test_multi_ray_cases_meet_their_conditions(n, K):
+    case = cg.multi_ray_case(n, K)
+    spec = case["spec"]
+    P = n * K
+    assert (spec["SB"], spec["NS"]) == (2, 2) and case["rays"].shape == (2 * n, 8) and case["z"].shape == (2 * n, K)
+    assert case["rays"].dtype == np.float32 and (np.diff(case["z"], axis=1) >= 0).all()
+    assert P > cg.CHUNK and {(43, 24): 1032, (211, 5): 1055}[n, K] == P
+    if (n, K) == (43, 24):
+        assert 42 * K < cg.CHUNK < 43 * K                     # ray 42 holds points 1008 .. 1031: across the chunk boundary
+    xyz, _ = cg.ray_points(case)
+    frac, clamped, _ = cg.class_counts(case, xyz)
+    keep = cg.relu_keep(case, True)
+    assert xyz.shape == (2, P, 3) and frac >= cg.MIN_INTERIOR and clamped > 0 and (~keep).mean() <= cg.MAX_MASKED
+    assert keep[cg.RAY_TAIL_OBJ, cg.CHUNK:].all()
+    cot = cg.tail_cotangent(case, cg.RAY_TAIL_OBJ, True)
+    nz = np.abs(cot).sum(-1) > 0
+    assert nz[cg.RAY_TAIL_OBJ, cg.CHUNK:].all() and nz.sum() == P - cg.CHUNK
+
+
+def test_sb1_ray_cases_are_unchanged_by_the_object_count():
+    """ray_points / point_truth take the object count from the spec now: one object gives the shapes they always gave."""
+    case = cg.ray_case(5)
+    xyz, dirs = cg.ray_points(case)
+    assert xyz.shape == dirs.shape == (1, 37 * 5, 3)
+
+
+@pytest.mark.parametrize("kind,key", cg.MULTI_IDS, ids=[f"{k}-{v}" if k == "points" else f"rays-{v[0]}x{v[1]}" for k, v in cg.MULTI_IDS])
+def test_fold_matches_autograd_and_every_planted_index_mistake_is_rejected(kind, key):
+    """cam_grad_util.fold — k_cam_partial and k_cam_fold restated — on the restated records equals autograd to 1e-12; each
+    mistake planted in its index arithmetic sits at MUTANT_FACTOR or more above compare_per_view's bound under the cotangent
+    FOLD_MUTANT_COTANGENT names for it, on every case it acts on.  Under the other cotangent the figure is printed: 0 x where
+    the mistake cannot show there (see FOLD_MUTANT_COTANGENT)."""
+    rays_mode = kind == "rays"
+    lines, seen = [], {}
+    for cname in ("full", "tail"):
+        case, cot, truth, ref32 = cg.multi_truth(kind, key, cname)
+        spec = case["spec"]
+        SB, NS = spec["SB"], spec["NS"]
+        ppo = cot.shape[1]
+        rec = cg.records(case, cot, rays_mode)
+        assert rec.shape == (NS * SB * ppo, 16)
+        good = cg.cam_from_sums(case, cg.fold(rec, SB, NS, ppo))
+        for k in cg.VIEW_KEYS:
+            assert good[k].shape == truth[k].shape
+            assert np.abs(good[k] - truth[k]).max() <= 1e-12 * np.abs(truth[k]).max(), (cname, k)
+        assert cg.compare_per_view(good, truth, ref32, f"{kind} {key} {cname}, restated fold")["ratio"] <= 1e-6
+        if cname == "tail":                                   # the other objects' rows: exact zeros in the truth itself
+            obj = cg.RAY_TAIL_OBJ if rays_mode else cg.TAIL_OBJ[key]
+            others = [o for o in range(SB) if o != obj]
+            assert not truth["poses"].reshape(SB, -1)[others].any() and not truth["focal"][others].any()
+            assert all(np.linalg.norm(truth["poses"].reshape(SB, NS, 12)[obj, v]) > 10 for v in range(NS))
+        for mutant in cg.FOLD_MUTANTS:
+            if not cg.fold_mutant_acts(mutant, SB, NS, ppo):
+                continue
+            got = cg.cam_from_sums(case, cg.fold(rec, SB, NS, ppo, mutant=mutant))
+            r = cg.compare_per_view(got, truth, ref32, f"{cname}, {mutant}", check=False)["ratio"]
+            seen.setdefault(mutant, {})[cname] = r
+            if cg.FOLD_MUTANT_COTANGENT[mutant] == cname:
+                assert r >= cg.MUTANT_FACTOR, (kind, key, cname, mutant, r)
+    for mutant, r in seen.items():
+        lines.append(f"{mutant}: full {r['full']:.0f} x, tail {r['tail']:.0f} x")
+    print(f"\n{kind} {key}: " + "; ".join(lines))
+    assert len(seen) >= (4 if key in (1023, 1024) else 8)
+
+
+def test_every_planted_index_mistake_acts_on_some_case():
+    sizes = [(3, 2, P) for P in cg.MULTI_P] + [(2, 2, n * K) for n, K in cg.MULTI_RAYS]
+    for mutant in cg.FOLD_MUTANTS:
+        assert sum(cg.fold_mutant_acts(mutant, *s) for s in sizes) >= 4, mutant
+        assert cg.FOLD_MUTANT_COTANGENT[mutant] in ("full", "tail")
+
+
+def test_per_view_rule_rejects_what_the_whole_tensor_rule_lets_through():
+    """One view of six 1e-3 off is 4e-4 of the whole tensor: cg.compare passes it, compare_per_view names the view; a piece
+    that is not zero where the truth is fails whatever its size."""
+    rng = np.random.default_rng(5)
+    truth = dict(poses=rng.standard_normal((6, 3, 4)), focal=rng.standard_normal((3, 2)), c=rng.standard_normal((3, 2)))
+    got = {k: v.copy() for k, v in truth.items()}
+    got["poses"][4] *= 1.0 + 1e-3
+    assert tu.rel_l2(got, truth)["poses"] < cg.RTOL
+    cg.compare(got, truth, truth, "one view 1e-3 off")
+    with pytest.raises(AssertionError, match=r"poses\[4\]"):
+        cg.compare_per_view(got, truth, truth, "one view 1e-3 off")
+    worst = cg.compare_per_view(got, truth, truth, "one view 1e-3 off", check=False)
+    assert worst["piece"] == "poses[4]" and abs(worst["ratio"] - 2.0) < 1e-6
+    truth["focal"][1] = 0.0
+    got = {k: v.copy() for k, v in truth.items()}
+    assert cg.compare_per_view(got, truth, truth, "zero row")["ratio"] == 0.0
+    got["focal"][1, 0] = 1e-30
+    with pytest.raises(AssertionError, match="exactly zero"):
+        cg.compare_per_view(got, truth, truth, "zero row")
+
+
+def test_camera_workspace_terms():
+    """DESIGN §4.14's terms on top of the backward's own workspace, each rounded up to 256 bytes behind 256 bytes of alignment
+    slack: 24 B per point, 64 B per (point, view), 128 B per (object, view, chunk of 1024 points) — the only term that
+    grows with the chunk count."""
+    from pixel_nerf_multiscale_amd import _native as N
+    r256 = lambda x: (x + 255) // 256 * 256
+    for SB, NS in ((1, 1), (2, 2), (3, 2)):
+        prm, m, v, _ = _structs(SB, NS)
+        for ppo in (3, 1023, 1024, 1025, 1032, 3089, 8193):
+            n = SB * ppo
+            base = N.lib.pnr_train_bwd_workspace_bytes(C.byref(m), C.byref(v), n)
+            pt, rec, part = r256(24 * n), r256(64 * NS * n), r256(128 * SB * NS * (-(-ppo // cg.CHUNK)))
+            for a, b in ((1, 0), (0, 1), (1, 1)):
+                got = N.lib.pnr_train_bwd_cam_workspace_bytes(C.byref(m), C.byref(v), n, a, b)
+                assert got == r256(base) + 256 + a * pt + b * (rec + part), (SB, NS, ppo, a, b, got, base)

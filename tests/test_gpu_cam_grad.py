@@ -1,6 +1,6 @@
 """Camera gradients on the device (csrc/cam_grad.hip through render/autograd.py) against float64 autograd through the oracle:
-the view directions, the rays, and the stored source poses / focal / c.  Cases, truth, the restated arithmetic and the rules
-are tests/cam_grad_util.py's; tests/test_cam_grad_cpu.py shows what the rules reject.  Every comparison prints
+the view directions, the rays, and the stored source poses / focal / c; from section 8 on with more than one chunk of 1024
+points per (object, view).  Cases, truth, the restated arithmetic and the rules are tests/cam_grad_util.py's; tests/test_cam_grad_cpu.py shows what the rules reject.  Every comparison prints
 kernel figure / fp32-restatement figure (pytest -s): DESIGN §4.14's table."""
 import ctypes as C
 
@@ -88,6 +88,7 @@ def test_point_camera_gradients_match_fp64(name):
     assert all(got[k].shape == truth[k].shape for k in got), {k: (got[k].shape, truth[k].shape) for k in got}
     print("\n" + cg.table_line(name, got, truth, ref32))
     cg.compare(got, truth, ref32, name)
+    cg.compare_per_view(got, truth, ref32, name)
 
 
 def test_three_points_less_than_one_block():
@@ -113,6 +114,7 @@ def test_ray_gradients_match_fp64(K):
     truth, ref32 = _truths(("r", K), case, cot, rays_mode=True)
     print("\n" + cg.table_line(f"rays K {K}", got, truth, ref32))
     cg.compare(got, truth, ref32, f"rays K {K}")
+    cg.compare_per_view(got, truth, ref32, f"rays K {K}")
     today = _run_rays(case, cot, want=())
     assert today["rays"] is None and today["poses"] is None
     assert torch.equal(g["z"], today["z"])
@@ -179,18 +181,25 @@ def test_only_poses_requiring_grad():
 # ----------------------------------------------------------------------------- 5. the bf16 product modes
 def test_bf16x3_and_bf16_camera_gradients():
     """bf16x3 against the fp32 path within 1e-2 in l2, the bound test_gpu_train.test_bf16x3_gradients holds that mode's
-    gradients to; plain bf16: finite, figure printed."""
-    case = cg.point_case("sb2_per_view_coded")
-    cot = cg.cotangent(case)
+    gradients to; plain bf16 under test_gpu_train.test_bf16_product_mode_gradients' rule for that mode, per tensor: relative
+    l2 <= 0.15 and cosine >= 0.99 against the fp32 path (the camera gradients read the dzx rows the latent gradients read).
+    "P 3089": SB 3, four chunks per (object, view)."""
     keys = ("xyz", "dirs", "poses", "focal", "c")
-    g32 = _run_points(case, cot)
-    for prec in ("bf16x3", "bf16"):
-        g = _run_points(case, cot, precision=prec)
-        rel = {k: float((g[k].double() - g32[k].double()).norm() / g32[k].double().norm()) for k in keys}
-        print(f"\n{prec} vs fp32, relative l2: " + ", ".join(f"{k} {v:.1e}" for k, v in rel.items()))
-        assert all(bool(torch.isfinite(g[k]).all()) for k in keys)
-        if prec == "bf16x3":
-            assert all(v <= 1e-2 for v in rel.values()), rel
+    for name, case in (("sb2_per_view_coded", cg.point_case("sb2_per_view_coded")), ("P 3089", cg.multi_case(3089))):
+        cot = cg.cotangent(case)
+        g32 = _run_points(case, cot)
+        for prec in ("bf16x3", "bf16"):
+            g = _run_points(case, cot, precision=prec)
+            a, b = {k: g[k].double().flatten() for k in keys}, {k: g32[k].double().flatten() for k in keys}
+            rel = {k: float((a[k] - b[k]).norm() / b[k].norm()) for k in keys}
+            cos = {k: float((a[k] @ b[k]) / (a[k].norm() * b[k].norm())) for k in keys}
+            print(f"\n{name}, {prec} vs fp32, relative l2: " + ", ".join(f"{k} {v:.1e}" for k, v in rel.items())
+                  + "; 1 - cosine: " + ", ".join(f"{k} {1 - v:.1e}" for k, v in cos.items()))
+            assert all(bool(torch.isfinite(g[k]).all()) for k in keys)
+            if prec == "bf16x3":
+                assert all(v <= 1e-2 for v in rel.values()), (name, rel)
+            else:
+                assert all(rel[k] <= 0.15 and cos[k] >= 0.99 for k in keys), (name, rel, cos)
 
 
 # ----------------------------------------------------------------------------- 3. a whole step through render_train
@@ -327,3 +336,126 @@ def test_refine_pose_ten_steps():
     assert bool(torch.isfinite(l1).all()) and float(l1[-1]) < float(l1[0])
     assert torch.equal(l1, l2) and torch.equal(p1, p2)
     assert all(p.grad is None for p in net.parameters())
+
+
+# ----------------------------------------------------------------------------- 8. more than one chunk of 1024 points per (object, view)
+CAM_KEYS = ("poses", "focal", "c")
+
+
+def _multi_run(kind, key, cot, **kw):
+    return _run_rays(cg.multi_ray_case(*key), cot, **kw) if kind == "rays" else _run_points(cg.multi_case(key), cot, **kw)
+
+
+@pytest.mark.parametrize("cot_name", ["full", "tail"])
+@pytest.mark.parametrize("P", cg.MULTI_P)
+def test_multi_chunk_point_camera_gradients_match_fp64(P, cot_name):
+    """SB 3, NS 2, P per object one short of a chunk, a chunk, a chunk and one point, three chunks and 17: d(xyz), d(viewdirs)
+    on every entry, the per-view sums per stored view and row (compare_per_view) as well as per tensor.  "tail": the cotangent
+    lives on the last chunk of one object alone, and the other objects' rows are exact zeros."""
+    case, cot, truth, ref32 = cg.multi_truth("points", P, cot_name)
+    frac, clamped, behind = cg.class_counts(case)
+    keep = cg.relu_keep(case)
+    assert frac >= cg.MIN_INTERIOR and clamped > 0 and behind > 0, (frac, clamped, behind)
+    assert (~keep).mean() <= cg.MAX_MASKED and (P <= cg.CHUNK or keep[:, P // cg.CHUNK * cg.CHUNK:].all())
+    got = _np(_run_points(case, cot), ("xyz", "dirs") + CAM_KEYS)
+    assert all(got[k].shape == truth[k].shape for k in got), {k: (got[k].shape, truth[k].shape) for k in got}
+    what = f"P {P} {cot_name}"
+    print("\n" + cg.table_line(what, got, truth, ref32))
+    if cot_name == "tail":
+        obj = cg.TAIL_OBJ[P]
+        others = [o for o in range(3) if o != obj]
+        assert np.linalg.norm(truth["poses"].reshape(3, -1)[obj]) > 10
+        for k in CAM_KEYS:                                     # a row per object (focal, c); two views of 12 (poses)
+            assert np.array_equal(got[k].reshape(3, -1)[others], np.zeros_like(got[k].reshape(3, -1)[others])), k
+    cg.compare(got, truth, ref32, what)
+    cg.compare_per_view(got, truth, ref32, what)
+
+
+@pytest.mark.parametrize("cot_name", ["full", "tail"])
+@pytest.mark.parametrize("n,K", cg.MULTI_RAYS)
+def test_multi_chunk_ray_gradients_match_fp64(n, K, cot_name):
+    """Rays mode with two objects of two views and more than 1024 points per object (a ray across the chunk boundary; an odd K
+    with a 31-point tail).  "tail": the cotangent lives on object 1's points from 1024 on; every other ray's row is exact zeros."""
+    case, cot, truth, ref32 = cg.multi_truth("rays", (n, K), cot_name)
+    g = _run_rays(case, cot)
+    got = _np(g, ("rays",) + CAM_KEYS)
+    assert got["rays"].shape == (2 * n, 8) and np.array_equal(got["rays"][:, 6:], np.zeros((2 * n, 2), np.float32))
+    what = f"rays {n} x {K} {cot_name}"
+    print("\n" + cg.table_line(what, got, truth, ref32))
+    if cot_name == "tail":
+        touched = (np.abs(cot).sum(-1) > 0).reshape(2 * n, K).any(1)
+        assert not touched[:n].any() and 0 < touched[n:].sum() == n - cg.CHUNK // K
+        assert np.array_equal(got["rays"][~touched, :6], np.zeros((int((~touched).sum()), 6), np.float32))
+        for k in CAM_KEYS:
+            assert np.array_equal(got[k].reshape(2, -1)[0], np.zeros_like(got[k].reshape(2, -1)[0])), k
+    else:
+        today = _run_rays(case, cot, want=())
+        assert today["rays"] is None and today["poses"] is None
+        assert torch.equal(g["z"], today["z"])
+    cg.compare(got, truth, ref32, what)
+    cg.compare_per_view(got, truth, ref32, what)
+
+
+MULTI_REPEAT = [("points", 3089), ("rays", (43, 24))]
+
+
+@pytest.mark.parametrize("kind,key", MULTI_REPEAT, ids=["points-3089", "rays-43x24"])
+def test_multi_chunk_runs_repeat(kind, key):
+    """Four chunks (two in rays mode) folded in chunk order: two runs give the same bits in every camera output."""
+    _, cot, _, _ = cg.multi_truth(kind, key, "full")
+    a, b = _multi_run(kind, key, cot), _multi_run(kind, key, cot)
+    for k in CAM_KEYS + (("rays", "z") if kind == "rays" else ("xyz", "dirs")):
+        assert torch.equal(a[k], b[k]), k
+
+
+GUARD = 4096
+
+
+@pytest.mark.parametrize("kind,key", MULTI_REPEAT, ids=["points-3089", "rays-43x24"])
+def test_camera_workspace_stays_inside_its_size(kind, key, monkeypatch):
+    """The backward's workspace handed over as a slice of a larger buffer, 4096 bytes of 0xA5 in front and behind: the size
+    asked for is pnr_train_bwd_cam_workspace_bytes with every camera output wanted, both guards keep their pattern, and
+    the gradients are the bits of the same call on the ordinary scratch (the slice itself starts as 0xA5 too: nothing is
+    read before it is written)."""
+    from pixel_nerf_multiscale_amd import _native as N
+    case, cot, _, _ = cg.multi_truth(kind, key, "full")
+    plain = _multi_run(kind, key, cot)
+    net, _ = _net(case)
+    v, _k = net.views_struct("fp32")
+    m, _k2 = net.mlp_struct(net.mlp_coarse, "fp32", v)
+    n_points = cot.shape[0] * cot.shape[1]
+    size_of = N.lib.pnr_train_bwd_cam_workspace_bytes
+    expect = int(size_of(C.byref(m), C.byref(v), n_points, 1, 1))
+    assert expect > int(N.lib.pnr_train_bwd_workspace_bytes(C.byref(m), C.byref(v), n_points))
+    log = dict(pending=None, flags=[], held=[])
+
+    def sized(*a):
+        log["pending"] = int(size_of(*a))
+        log["flags"].append((int(a[2]), int(a[3]), int(a[4])))
+        return log["pending"]
+
+    scratch = N.scratch
+
+    def guarded(nbytes, dev):
+        pending, log["pending"] = log["pending"], None
+        if pending is None or int(nbytes) != pending:
+            return scratch(nbytes, dev)
+        big = torch.full((GUARD + pending + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+        ws = big[GUARD:GUARD + pending]
+        assert ws.data_ptr() % 256 == 0
+        log["held"].append((big, pending))
+        return ws
+
+    monkeypatch.setattr(N.lib, "pnr_train_bwd_cam_workspace_bytes", sized)
+    monkeypatch.setattr(N, "scratch", guarded)
+    got = _multi_run(kind, key, cot)
+    torch.cuda.synchronize()
+    assert log["flags"] == [(n_points, 1, 1)] and len(log["held"]) == 1
+    big, nbytes = log["held"][0]
+    assert nbytes == expect
+    pattern = torch.full((GUARD,), 0xA5, dtype=torch.uint8, device=big.device)
+    assert torch.equal(big[:GUARD], pattern), "bytes in front of the workspace were written"
+    assert torch.equal(big[GUARD + nbytes:], pattern), "bytes behind the workspace were written"
+    assert plain.keys() == got.keys()
+    for k in plain:
+        assert (plain[k] is None) == (got[k] is None) and (plain[k] is None or torch.equal(plain[k], got[k])), k
