@@ -32,7 +32,8 @@ extern "C" {
                                   * pnr_view_strip / pnr_image_to_tensor; the approximate evaluation's batched metrics, pnr_eval_frames /
                                   * pnr_eval_frames_workspace_bytes; the metrics of saved 8-bit images, pnr_eval_frames_u8 /
                                   * pnr_eval_frames_u8_workspace_bytes; the camera gradients, pnr_point_mlp_bwd_cam /
-                                  * pnr_train_bwd_cam_workspace_bytes */
+                                  * pnr_train_bwd_cam_workspace_bytes; the data layer's 8-bit batches, pnr_train_batch_u8 /
+                                  * pnr_views_to_tensor_u8 */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -583,6 +584,41 @@ int32_t pnr_view_strip(const float* images /* (NS, 3, H, W) */, int32_t NS, int3
                        uint8_t* out_u8 /* (H, NS W, 3) */, void* stream);
 int32_t pnr_image_to_tensor(const uint8_t* img_u8 /* (H, W, 3) */, int32_t W, int32_t H, int32_t balanced,
                             float* out /* (3, H, W) */, void* stream);
+
+/* ---- data layer: batches whose images stay 8-bit on the device, csrc/data.hip ---------------------------------------------------
+ * The images of a batch are the bytes their files hold, interleaved: images_u8 (SB, NV, H, W, C), C = 3 or 4 (a fourth channel
+ * is stepped over).  T(b, balanced) below is exactly the fp32 value pnr_image_to_tensor writes for byte b (one device function
+ * serves all three entry points).  images_u8 may start at ANY byte (a slice of a pool does); whole-dword loads are used only
+ * where the addresses allow them, byte loads otherwise, and the output bits do not depend on the route.  No floating-point
+ * atomics; nothing is allocated or read back; all checks run before any launch.
+ *
+ * pnr_train_batch_u8: pnr_train_batch with images_u8 in place of the fp32 images.
+ *   rays_out            bit-identical to what pnr_train_batch writes for the same poses, intrinsics and indices (one device
+ *                       function builds the ray in both kernels)
+ *   rgb_gt_out[o, i, k] 0.5f * T(b, balanced) + 0.5f for the byte b of channel k at the pixel: bit-identical to pnr_train_batch
+ *                       on the fp32 image T would have produced
+ *   an index outside [0, NV*H*W) reads nothing and leaves a NaN row in both outputs, as in pnr_train_batch
+ *   PNR_E_NULL   as for pnr_train_batch (images_u8 may be NULL with rgb_gt_out NULL)
+ *   PNR_E_SHAPE  C not 3 or 4, balanced not 0 or 1, or pnr_train_batch's size conditions
+ *   B == 0 returns 0 and launches nothing
+ *
+ * pnr_views_to_tensor_u8: the selected source views of a batch, converted where they lie.
+ *   out[o, j, k, row, col] = T(images_u8[o, view_ord[o, j], row, col, k], balanced): per view what pnr_image_to_tensor gives on
+ *   that view, bit for bit.  view_ord is never read on the host, so the kernel is the range check: a view index outside
+ *   [0, NV) reads nothing and fills that view's three planes with NaN; a view may be named more than once.  No byte outside the
+ *   selected views is read and nothing outside `out` is written.
+ *   PNR_E_NULL   images_u8, view_ord or out NULL
+ *   PNR_E_SHAPE  SB, NV, NS, W or H < 1, NV * H * W >= 2^31, C not 3 or 4, balanced not 0 or 1; SB * NS views of
+ *                ceil(H W / 1024) workgroups each that do not fit one launch (2^31 - 1 workgroups)
+ *   PNR_E_ALIGN  out not 4-byte aligned */
+int32_t pnr_train_batch_u8(const uint8_t* images_u8 /* (SB, NV, H, W, C), any byte alignment; may be NULL with rgb_gt_out NULL */,
+                           const float* poses /* (SB, NV, 4, 4) */, const float* focal /* (SB, 2) */,
+                           const float* c /* (SB, 2) or NULL */, int32_t SB, int32_t NV, int32_t W, int32_t H, float z_near,
+                           float z_far, const int64_t* pix_inds /* (SB, B) */, int64_t B, float* rays_out /* (SB, B, 8) */,
+                           float* rgb_gt_out /* (SB, B, 3) or NULL */, int32_t C, int32_t balanced, void* stream);
+int32_t pnr_views_to_tensor_u8(const uint8_t* images_u8 /* (SB, NV, H, W, C), any byte alignment */,
+                               const int64_t* view_ord /* (SB, NS), device */, int32_t SB, int32_t NV, int32_t NS, int32_t W,
+                               int32_t H, int32_t C, int32_t balanced, float* out /* (SB, NS, 3, H, W) */, void* stream);
 
 /* Mesh extraction (util/recon.py: marching_cubes, with util.gen_grid util.py:98-115 and PyMCubes behind it), csrc/mesh.hip.
  *

@@ -1,5 +1,6 @@
 // Shared by the kernels around a rendered frame and the optimiser step (eval.hip, vis.hip, optim.hip): the workgroup fold
-// their bit-exact sums and extrema go through, the byte quantisation, and the 16 x 16 pixel tiling of a frame.
+// their bit-exact sums and extrema go through, the byte quantisation and its inverse (video.hip, data.hip), and the 16 x 16
+// pixel tiling of a frame.
 #pragma once
 #include "pnr_common.h"
 
@@ -22,6 +23,13 @@ template <int N, class Fold> __device__ __forceinline__ void block_fold(int tid,
 __device__ __forceinline__ float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
 // (x * 255).astype(uint8) of a clamped value: ONE fp32 product, then truncation ((k / 255) * 255 may land just below k); NaN -> 0
 __device__ __forceinline__ uint8_t quant_u8(float x) { return x == x ? (uint8_t)(int)__fmul_rn(x, 255.0f) : (uint8_t)0; }
+// T(b, balanced), an image byte as the network's input (include/pnr.h, pnr_image_to_tensor): float(b) / 255.0f, ONE correctly
+// rounded division (torchvision's ToTensor); balanced: then (. - 0.5f) / 0.5f, each operation rounded on its own (Normalize(0.5,
+// 0.5)).  The only place this arithmetic exists: pnr_image_to_tensor, pnr_views_to_tensor_u8 and pnr_train_batch_u8 call it.
+__device__ __forceinline__ float u8_to_tensor(uint32_t b, int balanced) {
+    const float v = __fdiv_rn((float)b, 255.0f);
+    return balanced ? __fdiv_rn(__fsub_rn(v, 0.5f), 0.5f) : v;
+}
 
 // ---------------------------------------------------------------- a frame as 16 x 16 pixel tiles, one workgroup per tile
 constexpr int FRAME_TILE = 16;                              // pixels per tile edge; one thread per pixel

@@ -2,6 +2,7 @@
 // ray-major: one wavefront (64 lanes) per ray, lanes stride the samples so every global access is a
 // coalesced 256-B (float) or 1-KiB (float4) row segment.
 #include "pnr_common.h"
+#include "train_batch.h"
 
 namespace pnr {
 
@@ -112,9 +113,9 @@ __global__ void k_gen_rays(RayCam c, int64_t pix0, int64_t n, float* __restrict_
 
 // ------------------------------------------------------------------ training batch  (train/train.py:280-311)
 // One thread per sampled ray: pix_inds[o, i] = view * H * W + row * W + col names a pixel of one of object o's NV views; the
-// ray is that camera's pinhole_ray (the RayCam built here from the pose row: bit-identical to k_gen_rays for the same camera
-// and pixel), the colour the three channel planes at that pixel mapped from [-1, 1] to [0, 1].  The indices live on the
-// device, so the range guard is here: an index outside [0, NV*H*W) reads nothing and leaves a NaN row.
+// ray is batch_ray's (train_batch.h, shared with the 8-bit kernel of data.hip), the colour the three channel planes at that
+// pixel mapped from [-1, 1] to [0, 1].  The indices live on the device, so the range guard is in batch_ray: an index outside
+// [0, NV*H*W) reads nothing and leaves a NaN row.
 __global__ void __launch_bounds__(256) k_train_batch(const float* __restrict__ images, const float* __restrict__ poses,
                                                      const float* __restrict__ focal, const float* __restrict__ c, int NV, int W,
                                                      int H, float z_near, float z_far, const int64_t* __restrict__ pix_inds,
@@ -123,44 +124,17 @@ __global__ void __launch_bounds__(256) k_train_batch(const float* __restrict__ i
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int64_t o = i / B;
-    const int64_t idx = pix_inds[i];
-    const int HW = H * W;                               // NV * H * W < 2^31 (checked by the entry point)
+    const BatchCams cams{poses, focal, c, NV, W, H, z_near, z_far};
     const float nan = __int_as_float(0x7fc00000);
-    float r[8] = {nan, nan, nan, nan, nan, nan, nan, nan}, g[3] = {nan, nan, nan};
-    if (idx >= 0 && idx < (int64_t)NV * HW) {
-        const int v = (int)idx / HW, pix = (int)idx - v * HW;
-        const float* P = poses + (o * NV + v) * 16;
-        RayCam cam;
+    float r[8], g[3] = {nan, nan, nan};
+    int v, pix;
+    if (batch_ray(cams, o, pix_inds[i], r, v, pix) && rgb_out) {
+        const int HW = H * W;
+        const float* im = images + (o * NV + v) * 3 * (int64_t)HW + pix;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            cam.R[a * 3 + 0] = P[a * 4 + 0]; cam.R[a * 3 + 1] = P[a * 4 + 1]; cam.R[a * 3 + 2] = P[a * 4 + 2];
-            cam.o[a] = P[a * 4 + 3];
-        }
-        cam.fx = focal[o * 2]; cam.fy = focal[o * 2 + 1];
-        cam.cx = c ? c[o * 2] : (float)W * 0.5f;
-        cam.cy = c ? c[o * 2 + 1] : (float)H * 0.5f;
-        cam.zn = z_near; cam.zf = z_far; cam.W = W; cam.H = H;
-        r[0] = cam.o[0]; r[1] = cam.o[1]; r[2] = cam.o[2];
-        pinhole_ray(cam, pix, r + 3);
-        r[6] = cam.zn; r[7] = cam.zf;
-        if (rgb_out) {
-            const float* im = images + (o * NV + v) * 3 * (int64_t)HW + pix;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) g[k] = fmaf(im[(int64_t)k * HW], 0.5f, 0.5f);
-        }
+        for (int k = 0; k < 3; ++k) g[k] = fmaf(im[(int64_t)k * HW], 0.5f, 0.5f);
     }
-    float* ro = rays_out + i * 8;
-    if ((((uintptr_t)rays_out) & 15) == 0) {            // 32-byte rows: two 16-byte stores
-        ((float4*)ro)[0] = make_float4(r[0], r[1], r[2], r[3]);
-        ((float4*)ro)[1] = make_float4(r[4], r[5], r[6], r[7]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) ro[k] = r[k];
-    }
-    if (rgb_out) {
-        float* go = rgb_out + i * 3;
-        go[0] = g[0]; go[1] = g[1]; go[2] = g[2];
-    }
+    batch_store(rays_out, rgb_out, i, r, g);
 }
 
 }  // namespace pnr
@@ -263,8 +237,7 @@ extern "C" int32_t pnr_train_batch(const float* images, const float* poses, cons
                                    int32_t NV, int32_t W, int32_t H, float z_near, float z_far, const int64_t* pix_inds,
                                    int64_t B, float* rays_out, float* rgb_gt_out, void* stream) {
     if (!poses || !focal || !pix_inds || !rays_out || (rgb_gt_out && !images)) return PNR_E_NULL;
-    if (SB <= 0 || NV <= 0 || W <= 0 || H <= 0 || B < 0 || (int64_t)NV * H * W >= ((int64_t)1 << 31)) return PNR_E_SHAPE;
-    if (B > (((int64_t)1 << 39) / SB)) return PNR_E_SHAPE;          // SB * B / 256 workgroups fit the grid
+    if (!batch_shape_ok(SB, NV, W, H, B)) return PNR_E_SHAPE;
     if (B == 0) return PNR_OK;
     const int64_t total = (int64_t)SB * B;
     hipLaunchKernelGGL(k_train_batch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, images, poses,

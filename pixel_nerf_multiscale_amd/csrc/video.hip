@@ -101,11 +101,7 @@ __global__ void __launch_bounds__(VF_THREADS) k_image_to_tensor(const uint8_t* _
     const int64_t pix = (int64_t)blockIdx.x * VF_THREADS + threadIdx.x;
     if (pix >= HW) return;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float v = __fdiv_rn((float)img[pix * 3 + c], 255.0f);
-        if (balanced) v = __fdiv_rn(__fsub_rn(v, 0.5f), 0.5f);
-        out[c * HW + pix] = v;
-    }
+    for (int c = 0; c < 3; ++c) out[c * HW + pix] = u8_to_tensor(img[pix * 3 + c], balanced);
 }
 
 static inline unsigned blocks_for(int64_t threads) { return (unsigned)((threads + VF_THREADS - 1) / VF_THREADS); }

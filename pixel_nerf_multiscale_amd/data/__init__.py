@@ -1,0 +1,44 @@
+"""
+The data layer: upstream pixelNeRF's data package (src/data: get_split_dataset, SRNDataset, DVRDataset) restated for this
+package's drivers, plus ResidentSplit, which keeps a whole split on the card as the bytes its image files hold.
+
+PARITY UNPINNED.  The reference fork's scripts import src/data and do not ship it, and upstream's code is not available where
+this package is developed, so nothing here was compared against either: the specification is the two on-disk layouts the class
+docstrings state (SRN cars / chairs, and the ShapeNet sub-format of DVR / NMR).  Where evalio.metrics_map already relies on a
+layout fact ("image" / "rgb" folders, "<list_name>.lst"), this package agrees with it.
+
+Items come in two modes.  as_bytes=False (the default) is what evaluate, evaluate_approx, gen_video and vis_step take:
+float32 images (NV, 3, H, W).  as_bytes=True is for train.calc_losses: uint8 images (NV, H, W, 3), a quarter of the bytes,
+converted on the device only where a step needs them (util.train_batch_u8, util.views_to_tensor_u8) to the bits the float
+item holds.
+"""
+from .dvr import DVRDataset
+from .resident import ResidentSplit
+from .srn import SRNDataset
+
+__all__ = ["get_split_dataset", "SRNDataset", "DVRDataset", "ResidentSplit"]
+
+
+def get_split_dataset(dataset_type, datadir, want_split="all", training=True, **kwargs):
+    """The dataset(s) of one folder.  dataset_type "srn" -> SRNDataset, "dvr" -> DVRDataset, "dvr_gen" -> DVRDataset with the
+    "gen_" object lists; want_split "train" | "val" | "test" returns that one set, anything else the (train, val, test) triple.
+    kwargs go to the dataset class (image_size, world_scale, balanced, as_bytes, ...).  `training` is accepted for upstream's
+    signature; it only steered settings of the dataset types that are refused here."""
+    if dataset_type == "srn":
+        cls, flags = SRNDataset, {}
+    elif dataset_type == "dvr":
+        cls, flags = DVRDataset, {}
+    elif dataset_type == "dvr_gen":
+        cls, flags = DVRDataset, {"list_prefix": "gen_"}
+    elif dataset_type == "dvr_dtu":
+        raise NotImplementedError("dataset type 'dvr_dtu': the DTU sub-format decomposes its projection matrices with "
+                                  "cv2.decomposeProjectionMatrix, and this package does not depend on cv2")
+    elif dataset_type == "multi_obj":
+        raise NotImplementedError("dataset type 'multi_obj': the multi-object layout (transforms.json per scene) is not "
+                                  "specified by anything in this package and no driver here uses it")
+    else:
+        raise NotImplementedError(f"unsupported dataset type {dataset_type!r}")
+    flags.update(kwargs)
+    if want_split in ("train", "val", "test"):
+        return cls(datadir, stage=want_split, **flags)
+    return tuple(cls(datadir, stage=stage, **flags) for stage in ("train", "val", "test"))

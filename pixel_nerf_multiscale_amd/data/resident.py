@@ -1,0 +1,79 @@
+"""A whole split on the card: the images as the bytes their files hold, so a training step uploads only its indices."""
+import torch
+
+from .. import util
+
+
+class ResidentSplit:
+    """Loads every object of an as_bytes dataset ONCE and keeps one device pool of bytes (N, NV, H, W, 3), one of poses
+    (N, NV, 4, 4), and the boxes and intrinsics on the host (they steer host-side draws).  A whole SRN or NMR training split is
+    under 10 GB this way.  Refuses a dataset whose objects differ in NV, H or W, and a pool above max_bytes (checked before
+    anything is allocated).
+
+    batch(ids) returns the loader's dict for train.calc_losses — device bytes and poses gathered by pool[ids], host bbox /
+    focal / c — and batches() iterates an epoch of them.  Neither reads anything back from the device.  z_near, z_far, lindisp
+    and balanced are the dataset's."""
+
+    def __init__(self, dataset, device, max_bytes=None):
+        if not getattr(dataset, "as_bytes", False):
+            raise ValueError("ResidentSplit needs a dataset built with as_bytes=True")
+        N = len(dataset)
+        if N == 0:
+            raise ValueError("ResidentSplit needs at least one object")
+        self.device = torch.device(device)
+        self.balanced = bool(getattr(dataset, "balanced", True))
+        for name in ("z_near", "z_far", "lindisp"):
+            setattr(self, name, getattr(dataset, name, None))
+        self.paths, bbox, focal, c = [], [], [], []
+        for i in range(N):
+            item = dataset[i]
+            images = item["images"]
+            if i == 0:
+                NV, H, W, C = (int(s) for s in images.shape)
+                nbytes = N * NV * H * W * C
+                if max_bytes is not None and nbytes > max_bytes:
+                    raise ValueError(f"the split needs a pool of {nbytes} bytes, above max_bytes = {max_bytes}")
+                self.images = torch.empty(N, NV, H, W, C, dtype=torch.uint8, device=self.device)
+                self.poses = torch.empty(N, NV, 4, 4, dtype=torch.float32, device=self.device)
+            elif tuple(images.shape) != (NV, H, W, C):
+                raise ValueError(f"{item['path']}: images {tuple(images.shape)}, the objects before it {(NV, H, W, C)}; "
+                                 "a resident pool needs one shape")
+            self.images[i].copy_(images)
+            self.poses[i].copy_(item["poses"])
+            self.paths.append(item["path"])
+            bbox.append(item["bbox"])
+            focal.append(torch.as_tensor(item["focal"], dtype=torch.float32))
+            c.append(item.get("c"))
+        self.bbox = torch.stack(bbox)
+        self.focal = torch.stack(focal)
+        self.c = None if c[0] is None else torch.stack(c)
+
+    def __len__(self):
+        return len(self.paths)
+
+    @property
+    def nbytes(self):
+        return self.images.numel()
+
+    def batch(self, ids):
+        """ids: object indices (a sequence or a host int tensor) -> {"path", "img_id", "images" (SB, NV, H, W, 3) uint8 and
+        "poses" on the device, "bbox", "focal", "c" (when the dataset has one) on the host}."""
+        ids = torch.as_tensor(ids, dtype=torch.long).reshape(-1)
+        if ids.is_cuda:
+            raise ValueError("ids must be host indices: they also select the host-side boxes and intrinsics")
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= len(self)):
+            raise IndexError(f"object index outside [0, {len(self)})")
+        on_dev = util.upload(ids, self.device)
+        data = {"path": [self.paths[i] for i in ids.tolist()], "img_id": ids, "images": self.images[on_dev],
+                "poses": self.poses[on_dev], "bbox": self.bbox[ids], "focal": self.focal[ids]}
+        if self.c is not None:
+            data["c"] = self.c[ids]
+        return data
+
+    def batches(self, batch_size, shuffle=True, generator=None, drop_last=True):
+        """One epoch: batch() over a permutation (torch.randperm under `generator`) or over the objects in order."""
+        N = len(self)
+        order = torch.randperm(N, generator=generator) if shuffle else torch.arange(N)
+        stop = N - N % batch_size if drop_last else N
+        for first in range(0, stop, batch_size):
+            yield self.batch(order[first:first + batch_size])

@@ -10,16 +10,27 @@ import torch
 from . import util
 
 
-def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=True, is_train=True):
+def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=True, is_train=True, balanced=True):
     """The front end of calc_losses (train/train.py:243-317): host draws, ONE upload of the (SB, ray_batch_size) pixel
     indices (the source-view choice rides in the same buffer) and one of the intrinsics, both from pinned memory, one launch
     for the rays and colours, and the source views picked on the device.
     -> rays (SB, B, 8), rgb_gt (SB, B, 3), src_images (SB, NS, 3, H, W), src_poses (SB, NS, 4, 4), focal (SB, 2),
     c (SB, 2) or None — the last two on the device, for net.encode.  Never waits for the device.  See calc_losses for `data`
-    and the order of the random draws."""
+    and the order of the random draws.
+
+    An 8-bit batch — data["images"] uint8 (SB, NV, H, W, 3 | 4), on the host or already on the device (data.ResidentSplit) —
+    moves and keeps a quarter of the bytes: the same draws, then util.train_batch_u8 and util.views_to_tensor_u8 convert only
+    the sampled pixels and the chosen source views, to the bits the float batch gives.  `balanced` names the float image such
+    a batch stands for (the dataset's .balanced); a float batch ignores it."""
+    as_bytes = data["images"].dtype == torch.uint8
+    if as_bytes and (data["images"].dim() != 5 or data["images"].shape[-1] not in (3, 4)):
+        raise ValueError(f"a uint8 batch must be (SB, NV, H, W, 3 | 4), got {tuple(data['images'].shape)}")
     all_images = util.upload(data["images"], device)
     all_poses = util.upload(data["poses"], device)
-    SB, NV, _, H, W = all_images.shape
+    if as_bytes:
+        SB, NV, H, W, _ = all_images.shape
+    else:
+        SB, NV, _, H, W = all_images.shape
     all_bboxes = data.get("bbox") if (is_train and use_bbox) else None
     if all_bboxes is not None and all_bboxes.is_cuda:
         raise ValueError("data['bbox'] must be a host tensor: it steers host-side draws and is never read from the device")
@@ -57,19 +68,28 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
     focal = focal.contiguous()
     c = None if c is None else c.contiguous()
 
-    rays, rgb_gt = util.train_batch(all_images, all_poses, focal, c, pix_inds, z_near, z_far)
-    return (rays, rgb_gt, util.batched_index_select_nd(all_images, image_ord),
-            util.batched_index_select_nd(all_poses, image_ord), focal, c)
+    if as_bytes:
+        rays, rgb_gt = util.train_batch_u8(all_images, all_poses, focal, c, pix_inds, z_near, z_far, balanced=balanced)
+        src_images = util.views_to_tensor_u8(all_images, image_ord, balanced=balanced)
+    else:
+        rays, rgb_gt = util.train_batch(all_images, all_poses, focal, c, pix_inds, z_near, z_far)
+        src_images = util.batched_index_select_nd(all_images, image_ord)
+    return rays, rgb_gt, src_images, util.batched_index_select_nd(all_poses, image_ord), focal, c
 
 
-def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far, loss, use_bbox=True, is_train=True):
+def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far, loss, use_bbox=True, is_train=True,
+                balanced=True):
     """One batch of the data loader -> (loss, loss_dict), ready for loss.backward().
 
     net          PixelNeRFNet (on the device)
     render_par   renderer.bind_parallel(net, ...): (rays, want_weights=True) -> nested dict
     data         the loader's dict: images (SB, NV, 3, H, W) in [-1, 1], poses (SB, NV, 4, 4), focal (SB,) or (SB, 2),
                  optional c (SB, 2) and bbox (SB, NV, 4) = cmin, rmin, cmax, rmax.  bbox is read on the host (it steers
-                 host-side draws), so it must be a host tensor, as the loader gives it.
+                 host-side draws), so it must be a host tensor, as the loader gives it.  images may instead be the files'
+                 bytes, uint8 (SB, NV, H, W, 3 | 4) on the host or the device (an as_bytes dataset of the data package, or
+                 data.ResidentSplit.batch): see make_batch.
+    balanced     for an 8-bit batch, the dataset's .balanced: whether its float images would lie in [-1, 1] (True) or
+                 [0, 1]; ignored for a float batch
     nviews       the source-view counts to draw from (the reference's --nviews list)
     loss         model.loss.RenderLoss
     use_bbox     the reference's self.use_bbox (its switch-off at args.no_bbox_step is the caller's schedule)
@@ -87,7 +107,8 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
         return {}
     dev = net.poses.device
     all_rays, all_rgb_gt, src_images, src_poses, focal, c = make_batch(
-        data, dev, ray_batch_size=ray_batch_size, nviews=nviews, z_near=z_near, z_far=z_far, use_bbox=use_bbox, is_train=is_train)
+        data, dev, ray_batch_size=ray_batch_size, nviews=nviews, z_near=z_near, z_far=z_far, use_bbox=use_bbox, is_train=is_train,
+        balanced=balanced)
     net.encode(src_images, src_poses, focal, c=c)
 
     render_dict = render_par(all_rays, want_weights=True)

@@ -309,6 +309,62 @@ def train_batch(images, poses, focal, c, pix_inds, z_near, z_far):
     return rays, rgb_gt
 
 
+def _images_u8(images_u8):
+    """A uint8 batch (SB, NV, H, W, 3 | 4), made contiguous when it is not (a slice of a pool along its first axis is), and its
+    shape."""
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 5 or images_u8.shape[4] not in (3, 4):
+        raise ValueError(f"images_u8 must be uint8 (SB, NV, H, W, 3 | 4), got {getattr(images_u8, 'dtype', None)} "
+                         f"{tuple(getattr(images_u8, 'shape', ()))}")
+    return images_u8.contiguous(), tuple(int(s) for s in images_u8.shape)
+
+
+def train_batch_u8(images_u8, poses, focal, c, pix_inds, z_near, z_far, balanced=True):
+    """train_batch for a batch whose images stay 8-bit on the device (pnr_train_batch_u8): images_u8 (SB, NV, H, W, 3 | 4)
+    uint8, interleaved as the files hold them (a fourth channel is stepped over), at any byte offset of a larger allocation;
+    the other arguments as train_batch takes them.  balanced says what the FLOAT image of the loader would have been —
+    (b / 255 - 0.5) / 0.5 in [-1, 1] (True) or b / 255 (False) — and rgb_gt = 0.5 * that + 0.5, bit for bit what train_batch
+    gives on that float image; the rays are train_batch's bits.  -> rays (SB, B, 8), rgb_gt (SB, B, 3)."""
+    from . import _native as N
+    images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
+    dev = N.same_device(images_u8, poses, pix_inds)
+    if tuple(poses.shape) != (SB, NV, 4, 4):
+        raise ValueError(f"poses must be ({SB}, {NV}, 4, 4), got {tuple(poses.shape)}")
+    if pix_inds.dim() != 2 or pix_inds.shape[0] != SB or pix_inds.dtype != torch.long:
+        raise ValueError(f"pix_inds must be ({SB}, B) int64, got {tuple(pix_inds.shape)} {pix_inds.dtype}")
+    poses, pix_inds = N.f32c(poses), pix_inds.contiguous()
+    focal = upload(torch.as_tensor(focal, dtype=torch.float32), dev)
+    if focal.dim() <= 1:
+        focal = focal.reshape(-1, 1).expand(-1, 2)
+    focal = focal.expand(SB, 2).contiguous()
+    if c is not None:
+        c = upload(torch.as_tensor(c, dtype=torch.float32), dev).reshape(-1, 2).expand(SB, 2).contiguous()
+    B = pix_inds.shape[1]
+    rays = torch.empty(SB, B, 8, device=dev)
+    rgb_gt = torch.empty(SB, B, 3, device=dev)
+    N.check(N.lib.pnr_train_batch_u8(N.ptr(images_u8), N.ptr(poses), N.ptr(focal), N.ptr(c), SB, NV, W, H, float(z_near),
+                                     float(z_far), pix_inds.data_ptr(), B, N.ptr(rays), N.ptr(rgb_gt), C, int(bool(balanced)),
+                                     N.current_stream(dev)), "pnr_train_batch_u8")
+    return rays, rgb_gt
+
+
+def views_to_tensor_u8(images_u8, view_ord, balanced=True):
+    """The selected views of an 8-bit batch as the network's input, converted where they lie (pnr_views_to_tensor_u8):
+    images_u8 (SB, NV, H, W, 3 | 4) uint8 and view_ord (SB, NS) long, both on the device -> (SB, NS, 3, H, W) float32, per view
+    what image_to_tensor gives on it, bit for bit.  In place of batched_index_select_nd over float images.  A view index
+    outside [0, NV) gives NaN planes (the indices are never read on the host); a repeated view is allowed."""
+    from . import _native as N
+    images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
+    dev = N.same_device(images_u8, view_ord)
+    if view_ord.dim() != 2 or view_ord.shape[0] != SB or view_ord.shape[1] < 1 or view_ord.dtype != torch.long:
+        raise ValueError(f"view_ord must be ({SB}, NS >= 1) int64, got {tuple(view_ord.shape)} {view_ord.dtype}")
+    view_ord = view_ord.contiguous()
+    NS = int(view_ord.shape[1])
+    out = torch.empty(SB, NS, 3, H, W, dtype=torch.float32, device=dev)
+    N.check(N.lib.pnr_views_to_tensor_u8(N.ptr(images_u8), view_ord.data_ptr(), SB, NV, NS, W, H, C, int(bool(balanced)),
+                                         N.ptr(out), N.current_stream(dev)), "pnr_views_to_tensor_u8")
+    return out
+
+
 def _record_stride(t, lead, last, name):
     """Floats per element of a tensor of shape lead [+ (last,)] — lead = (H, W) for a frame, (n,) for per-ray outputs — that is
     dense or a regular view into a packed per-element record: unit stride inside the element and, for a frame, row-major
