@@ -33,7 +33,7 @@ extern "C" {
                                   * pnr_eval_frames_workspace_bytes; the metrics of saved 8-bit images, pnr_eval_frames_u8 /
                                   * pnr_eval_frames_u8_workspace_bytes; the camera gradients, pnr_point_mlp_bwd_cam /
                                   * pnr_train_bwd_cam_workspace_bytes; the data layer's 8-bit batches, pnr_train_batch_u8 /
-                                  * pnr_views_to_tensor_u8 */
+                                  * pnr_views_to_tensor_u8; the training draws, pnr_train_draw */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -619,6 +619,37 @@ int32_t pnr_train_batch_u8(const uint8_t* images_u8 /* (SB, NV, H, W, C), any by
 int32_t pnr_views_to_tensor_u8(const uint8_t* images_u8 /* (SB, NV, H, W, C), any byte alignment */,
                                const int64_t* view_ord /* (SB, NS), device */, int32_t SB, int32_t NV, int32_t NS, int32_t W,
                                int32_t H, int32_t C, int32_t balanced, float* out /* (SB, NS, 3, H, W) */, void* stream);
+
+/* ---- training draws on the device, csrc/train_draw.hip ---------------------------------------------------------------------------
+ * pnr_train_draw: the pixels a training step samples and the source views it encodes (train/train.py:268-300: per object
+ * np.random.choice for the views, util.bbox_sample or a uniform randint for the pixels), drawn by one launch of SB * B + SB work
+ * items from philox4x32 keyed by `seed` — the caller's per-step key — so a step's batch depends on (seed) alone and a resumed run
+ * sees the batches the uninterrupted run would have.  The outputs are the index buffers pnr_train_batch, pnr_train_batch_u8 and
+ * pnr_views_to_tensor_u8 take.  All arithmetic is integer; mulhi(x, n) = (uint64(x) * n) >> 32, a value in [0, n).  Draw ids
+ * 8 (pixels) and 9 (views) — 0..3 are the render samplers' — in the counter layout of the samplers: key = (seed lo32, seed hi32),
+ * counter = (index lo32, index hi32, draw id, block).
+ *
+ * Pixel (o, j), r = o * B + j:  (x, y, z, _) = philox4x32(seed, lo32(r), hi32(r), 8, 0);  view = mulhi(x, NV).
+ *   without boxes (bbox NULL)   col = mulhi(y, W), row = mulhi(z, H)
+ *   with boxes                  (cmin, rmin, cmax, rmax) = the four floats of bbox[o, view] truncated towards zero; the box is
+ *                               valid iff all four are finite and 0 <= cmin <= cmax < W and 0 <= rmin <= rmax < H;
+ *                               col = cmin + mulhi(y, cmax + 1 - cmin), row = rmin + mulhi(z, rmax + 1 - rmin)
+ *   pix_inds_out[o, j] = view * H * W + row * W + col; -1 for an invalid box, which pnr_train_batch turns into a NaN row.  The
+ *   boxes are never read on the host, so this kernel is their range check; it reads nothing else.
+ * Views of object o (NS <= NV, NS <= 64), s = 0 .. NS - 1 in order: word_s = word s & 3 of philox4x32(seed, lo32(o), hi32(o), 9,
+ *   s >> 2); t = mulhi(word_s, NV - s); walk the views chosen so far in ascending order and increment t for each chosen c with
+ *   t >= c; view_ord_out[o, s] = t.  A uniformly random ordered subset, with no NV-sized array.
+ *
+ * Deliberately not the reference's stream, only its distribution (a uniform view, then a uniform cell of its box): without boxes
+ * view, row and column are drawn separately instead of one randint(NV * H * W), and the reference's float form
+ * rand * (cmax + 1 - cmin) + cmin can round up to cmax + 1 where the integer form cannot.
+ *   PNR_E_SHAPE  NS < 0, NS > 64, NS > NV, or pnr_train_batch's size conditions (SB, NV, W, H < 1, B < 0, NV * H * W >= 2^31,
+ *                more work items than one launch holds)
+ *   PNR_E_NULL   pix_inds_out NULL with B > 0, view_ord_out NULL with NS > 0
+ *   B == 0 and NS == 0 returns 0 and launches nothing */
+int32_t pnr_train_draw(const float* bbox /* (SB, NV, 4) cmin rmin cmax rmax, or NULL */, int32_t SB, int32_t NV, int32_t W,
+                       int32_t H, int64_t B, int32_t NS, uint64_t seed, int64_t* pix_inds_out /* (SB, B) */,
+                       int64_t* view_ord_out /* (SB, NS), NULL iff NS == 0 */, void* stream);
 
 /* Mesh extraction (util/recon.py: marching_cubes, with util.gen_grid util.py:98-115 and PyMCubes behind it), csrc/mesh.hip.
  *

@@ -11,7 +11,7 @@ __all__ = ["PixelNeRFNet", "NeRFRenderer", "make_model", "util"]
 
 _LAZY = {"PixelNeRFNet": ".model", "make_model": ".model", "NeRFRenderer": ".render", "util": ".util",
          "model": ".model", "render": ".render", "parallel": ".parallel", "evalio": ".evalio", "train": ".train", "recon": ".recon", "optim": ".optim",
-         "video": ".video", "data": ".data", "DeviceAdam": ".optim", "_native": "._native"}
+         "video": ".video", "data": ".data", "trainer": ".trainer", "DeviceAdam": ".optim", "_native": "._native"}
 
 
 def __getattr__(name):

@@ -12,9 +12,13 @@ class ResidentSplit:
 
     batch(ids) returns the loader's dict for train.calc_losses — device bytes and poses gathered by pool[ids], host bbox /
     focal / c — and batches() iterates an epoch of them.  Neither reads anything back from the device.  z_near, z_far, lindisp
-    and balanced are the dataset's."""
+    and balanced are the dataset's.
 
-    def __init__(self, dataset, device, max_bytes=None):
+    device_boxes=True also keeps the boxes on the card, float32 (N, NV, 4), and batch() adds "bbox_dev", their rows gathered
+    on the device: what train.make_batch(draws="device") draws inside without an upload.  With the default the dict is
+    unchanged."""
+
+    def __init__(self, dataset, device, max_bytes=None, device_boxes=False):
         if not getattr(dataset, "as_bytes", False):
             raise ValueError("ResidentSplit needs a dataset built with as_bytes=True")
         N = len(dataset)
@@ -47,6 +51,7 @@ class ResidentSplit:
         self.bbox = torch.stack(bbox)
         self.focal = torch.stack(focal)
         self.c = None if c[0] is None else torch.stack(c)
+        self.bbox_dev = util.upload(self.bbox.to(torch.float32).contiguous(), self.device) if device_boxes else None
 
     def __len__(self):
         return len(self.paths)
@@ -68,6 +73,8 @@ class ResidentSplit:
                 "poses": self.poses[on_dev], "bbox": self.bbox[ids], "focal": self.focal[ids]}
         if self.c is not None:
             data["c"] = self.c[ids]
+        if self.bbox_dev is not None:
+            data["bbox_dev"] = self.bbox_dev[on_dev]
         return data
 
     def batches(self, batch_size, shuffle=True, generator=None, drop_last=True):

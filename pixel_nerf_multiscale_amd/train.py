@@ -10,7 +10,14 @@ import torch
 from . import util
 
 
-def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=True, is_train=True, balanced=True):
+def curr_nviews_for(nviews, seed):
+    """The source-view count of the step keyed `seed` under device draws: nviews[seed % len(nviews)].  Computed on the host,
+    because it fixes the shapes of the step."""
+    return int(nviews[int(seed) % len(nviews)])
+
+
+def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=True, is_train=True, balanced=True,
+               draws="host", seed=None):
     """The front end of calc_losses (train/train.py:243-317): host draws, ONE upload of the (SB, ray_batch_size) pixel
     indices (the source-view choice rides in the same buffer) and one of the intrinsics, both from pinned memory, one launch
     for the rays and colours, and the source views picked on the device.
@@ -21,7 +28,18 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
     An 8-bit batch — data["images"] uint8 (SB, NV, H, W, 3 | 4), on the host or already on the device (data.ResidentSplit) —
     moves and keeps a quarter of the bytes: the same draws, then util.train_batch_u8 and util.views_to_tensor_u8 convert only
     the sampled pixels and the chosen source views, to the bits the float batch gives.  `balanced` names the float image such
-    a batch stands for (the dataset's .balanced); a float batch ignores it."""
+    a batch stands for (the dataset's .balanced); a float batch ignores it.
+
+    draws="device" with seed, the per-step key (parallel.frame_seed(base_seed, global_step)): no host draw and no index
+    upload — curr_nviews = nviews[seed % len(nviews)], then ONE util.train_draw launch makes the pixel indices and the source
+    views on the device from the key alone (include/pnr.h, pnr_train_draw), and the same gather calls follow.  The boxes are
+    data["bbox_dev"] (data.ResidentSplit(device_boxes=True)) or data["bbox"] uploaded.  The batch of a step then depends on
+    (seed) only, not on torch's and numpy's global generators, so a run resumed from a checkpoint sees the batches the
+    uninterrupted run would have seen.  The stream is not the reference's, the distribution is (see pnr.h)."""
+    if draws not in ("host", "device"):
+        raise ValueError(f"draws must be 'host' or 'device', got {draws!r}")
+    if draws == "device" and seed is None:
+        raise ValueError("draws='device' needs seed, the per-step key: parallel.frame_seed(base_seed, global_step)")
     as_bytes = data["images"].dtype == torch.uint8
     if as_bytes and (data["images"].dim() != 5 or data["images"].shape[-1] not in (3, 4)):
         raise ValueError(f"a uint8 batch must be (SB, NV, H, W, 3 | 4), got {tuple(data['images'].shape)}")
@@ -31,12 +49,24 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
         SB, NV, H, W, _ = all_images.shape
     else:
         SB, NV, _, H, W = all_images.shape
+    B = int(ray_batch_size)
+    if draws == "device":
+        boxes = None
+        if is_train and use_bbox:
+            boxes = data.get("bbox_dev")
+            if boxes is None and data.get("bbox") is not None:
+                boxes = util.upload(torch.as_tensor(data["bbox"], dtype=torch.float32), device)
+        if boxes is not None:
+            boxes = boxes.to(device=device, dtype=torch.float32)
+        pix_inds, image_ord = util.train_draw(boxes, SB, NV, W, H, B, curr_nviews_for(nviews, seed), seed,
+                                              out_pix=torch.empty(SB, B, dtype=torch.long, device=device))
+        return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced)
+
     all_bboxes = data.get("bbox") if (is_train and use_bbox) else None
     if all_bboxes is not None and all_bboxes.is_cuda:
         raise ValueError("data['bbox'] must be a host tensor: it steers host-side draws and is never read from the device")
 
     curr_nviews = nviews[int(torch.randint(0, len(nviews), ()))]
-    B = int(ray_batch_size)
     host = torch.empty(SB * (B + curr_nviews), dtype=torch.long, pin_memory=True)
     pix_inds, image_ord = host[:SB * B].view(SB, B), host[SB * B:].view(SB, curr_nviews)
     if curr_nviews == 1:
@@ -51,7 +81,14 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
             pix_inds[obj] = torch.randint(0, NV * H * W, (B,))
     on_dev = host.to(device, non_blocking=True)
     pix_inds, image_ord = on_dev[:SB * B].view(SB, B), on_dev[SB * B:].view(SB, curr_nviews)
+    return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced)
 
+
+def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced):
+    """make_batch behind its draws: the intrinsics' upload, the rays and colours of pix_inds (SB, B), the source views and
+    poses of image_ord (SB, NS)."""
+    as_bytes = all_images.dtype == torch.uint8
+    SB = all_images.shape[0]
     # the loader's focal (SB,) or (SB, 2) and c (SB, 2): one (SB, 4) block, uploaded once
     focal = torch.as_tensor(data["focal"], dtype=torch.float32)
     c = data.get("c")
@@ -78,7 +115,7 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
 
 
 def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far, loss, use_bbox=True, is_train=True,
-                balanced=True):
+                balanced=True, draws="host", seed=None):
     """One batch of the data loader -> (loss, loss_dict), ready for loss.backward().
 
     net          PixelNeRFNet (on the device)
@@ -93,6 +130,8 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     nviews       the source-view counts to draw from (the reference's --nviews list)
     loss         model.loss.RenderLoss
     use_bbox     the reference's self.use_bbox (its switch-off at args.no_bbox_step is the caller's schedule)
+    draws, seed  "host" (the default): the draws below; "device" with seed = the per-step key: make_batch's keyed draws on
+                 the device, which consume neither global generator
 
     loss_dict has "rc", "rf" (only with a fine pass) and "t".  Unlike the reference, which returns Python floats (three
     .item() calls, i.e. three host synchronisations per step), each value is a 0-dim view of ONE 3-float device buffer:
@@ -108,7 +147,7 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     dev = net.poses.device
     all_rays, all_rgb_gt, src_images, src_poses, focal, c = make_batch(
         data, dev, ray_batch_size=ray_batch_size, nviews=nviews, z_near=z_near, z_far=z_far, use_bbox=use_bbox, is_train=is_train,
-        balanced=balanced)
+        balanced=balanced, draws=draws, seed=seed)
     net.encode(src_images, src_poses, focal, c=c)
 
     render_dict = render_par(all_rays, want_weights=True)
@@ -265,3 +304,12 @@ def vis_step(net, renderer, render_par, data, *, nviews, z_near, z_far, idx=None
             print("{} alpha min {}, max {}".format(tag, s[2], s[3]))
         print("psnr", float(res.psnr))
     return (res.panel if out == "float" else res.panel_u8), {"psnr": res.psnr}
+
+
+def __getattr__(name):
+    """train.Trainer is trainer.Trainer, the epoch loop over the functions above (looked up on first use: trainer imports
+    this module)."""
+    if name == "Trainer":
+        from .trainer import Trainer
+        return Trainer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -365,6 +365,40 @@ def views_to_tensor_u8(images_u8, view_ord, balanced=True):
     return out
 
 
+def train_draw(bbox, SB, NV, W, H, B, NS, seed, out_pix=None, out_views=None):
+    """The draws of one training step on the device (pnr_train_draw; include/pnr.h writes the arithmetic down): B pixels per
+    object — a uniform view, then a uniform cell of its box, or of the whole image when bbox is None — and an ordered
+    subset of NS of its NV views, all keyed by `seed` alone (the caller's per-step key, parallel.frame_seed(base, step)).
+    bbox (SB, NV, 4) = cmin, rmin, cmax, rmax float32 on the device, or None; out_pix (SB, B) / out_views (SB, NS) int64 on
+    the device are filled when given (out_pix names the device when there are no boxes), else allocated on bbox's device or
+    the current one.  -> (pix_inds, view_ord) for train_batch / train_batch_u8 / views_to_tensor_u8 / batched_index_select_nd.
+    An invalid box (NaN, inverted, outside the image) gives index -1, a NaN row downstream.  Reads nothing back."""
+    from . import _native as N
+    SB, NV, W, H, B, NS, seed = int(SB), int(NV), int(W), int(H), int(B), int(NS), int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
+    if SB < 1 or NV < 1 or W < 1 or H < 1 or B < 0:
+        raise ValueError(f"train_draw needs SB, NV, W, H >= 1 and B >= 0, got {(SB, NV, W, H, B)}")
+    if not 0 <= NS <= min(NV, 64):
+        raise ValueError(f"NS must lie in [0, min(NV, 64)] = [0, {min(NV, 64)}], got {NS}")
+    if bbox is not None:
+        if not torch.is_tensor(bbox) or bbox.dtype != torch.float32 or tuple(bbox.shape) != (SB, NV, 4):
+            raise ValueError(f"bbox must be float32 ({SB}, {NV}, 4), got {getattr(bbox, 'dtype', None)} "
+                             f"{tuple(getattr(bbox, 'shape', ()))}")
+        bbox = bbox.contiguous()
+    for name, t, shape in (("out_pix", out_pix, (SB, B)), ("out_views", out_views, (SB, NS))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.long or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int64 {shape} tensor, got {getattr(t, 'dtype', None)} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    given = [t for t in (bbox, out_pix, out_views) if t is not None]
+    dev = N.same_device(*given) if given else torch.device("cuda", torch.cuda.current_device())
+    pix = torch.empty(SB, B, dtype=torch.long, device=dev) if out_pix is None else out_pix
+    views = torch.empty(SB, NS, dtype=torch.long, device=dev) if out_views is None else out_views
+    N.check(N.lib.pnr_train_draw(N.dptr(bbox), SB, NV, W, H, B, NS, seed, pix.data_ptr() if B else None,
+                                 views.data_ptr() if NS else None, N.current_stream(dev)), "pnr_train_draw")
+    return pix, views
+
+
 def _record_stride(t, lead, last, name):
     """Floats per element of a tensor of shape lead [+ (last,)] — lead = (H, W) for a frame, (n,) for per-ray outputs — that is
     dense or a regular view into a packed per-element record: unit stride inside the element and, for a frame, row-major
