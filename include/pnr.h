@@ -33,7 +33,8 @@ extern "C" {
                                   * pnr_eval_frames_workspace_bytes; the metrics of saved 8-bit images, pnr_eval_frames_u8 /
                                   * pnr_eval_frames_u8_workspace_bytes; the camera gradients, pnr_point_mlp_bwd_cam /
                                   * pnr_train_bwd_cam_workspace_bytes; the data layer's 8-bit batches, pnr_train_batch_u8 /
-                                  * pnr_views_to_tensor_u8; the training draws, pnr_train_draw */
+                                  * pnr_views_to_tensor_u8; the training draws, pnr_train_draw; the fused launch's work split as a
+                                  * host diagnostic, pnr_debug_point_split */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -824,6 +825,14 @@ int32_t pnr_event_destroy(void* ev);
 int64_t pnr_debug_gemm_grid(int32_t M, int32_t N, int32_t Rn, int32_t rows_per_split, int32_t split);
 int32_t pnr_debug_gemm_tile(int32_t block, int32_t M, int32_t N, int32_t Rn, int32_t rows_per_split, int32_t split,
                             int32_t* out3);
+
+/* Diagnostic of the fused point kernel's launch (csrc/point_mfma.hip point_split; a host function, no device work): how a call's
+ * work is split over workgroups.  max_wgs: the workgroup cap (the device's CUs, at most 512); n_stream_objs: objects with a
+ * projected weight stream of their own (<= 1: none — workgroups then share the whole call); K: 0 for a plain point launch,
+ * whose workgroups own runs of 128-point tiles, or the samples per ray of a fused render launch, whose workgroups own whole
+ * rays; count: the call's points (K = 0) or rays; per_obj: one object's points or rays (read with n_stream_objs > 1 only).
+ * out4 = (grid, tiles_per_wg, rays_per_wg, wgs_per_obj); returns PNR_OK, or the code the launch returns for such sizes. */
+int32_t pnr_debug_point_split(int32_t max_wgs, int32_t n_stream_objs, int32_t K, int64_t count, int64_t per_obj, int32_t* out4);
 
 /* Test entry into the training path's linear-layer dispatch (csrc/train_f32.hip: gemm, gemm16, grad_w, head_dx) and its bf16
  * copy kernels: ONE product on caller-owned device buffers, chosen by the production dispatchers from the same shape,

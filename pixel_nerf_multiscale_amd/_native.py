@@ -194,6 +194,7 @@ PROTOTYPES = {
     "pnr_event_destroy": (_i32, [_fp]),
     "pnr_debug_gemm_grid": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "pnr_debug_gemm_tile": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32)]),
+    "pnr_debug_point_split": (_i32, [_i32, _i32, _i32, _i64, _i64, C.POINTER(C.c_int32)]),
     "pnr_debug_linear": (_i32, [C.POINTER(pnr_debug_linear_args), _fp]),
     "pnr_debug_latent_grad_route": (_i32, [C.POINTER(pnr_views), _i64]),
 }

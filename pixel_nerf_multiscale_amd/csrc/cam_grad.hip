@@ -180,28 +180,34 @@ static inline uint64_t n_chunks_of(const pnr_views* vw, int64_t P) {
     const int64_t ppo = vw->n_objs > 0 ? P / vw->n_objs : 0;
     return (uint64_t)((ppo + CAMG_CHUNK - 1) / CAMG_CHUNK);
 }
-static inline uint64_t rec_bytes(const pnr_views* vw, int64_t P) { return round_up_256((uint64_t)vw->n_views * P * 64); }
-static inline uint64_t pt_bytes(int64_t P) { return round_up_256((uint64_t)P * 24); }
-static inline uint64_t part_bytes(const pnr_views* vw, int64_t P) {
-    return round_up_256((uint64_t)vw->n_objs * vw->n_views * n_chunks_of(vw, P) * 16 * 8);
+// Workspace (256-byte pieces behind a base rounded up to 256, + that slack): 6 floats per point for the ray or direction
+// gradients, and for the camera gradients 16 floats per (view, point) and 16 doubles per (object, view, chunk).
+struct CamGradWs { float* pt; float* rec; double* part; };
+static CamGradWs carve_cam_grad(Bump& b, const pnr_views* vw, int64_t P, bool want_point, bool want_cam) {
+    CamGradWs w{};
+    if (!want_point && !want_cam) return w;
+    if (want_point) w.pt = b.take<float>((uint64_t)P * 6, 256);
+    if (want_cam) {
+        w.rec = b.take<float>((uint64_t)vw->n_views * P * 16, 256);
+        w.part = b.take<double>((uint64_t)vw->n_objs * vw->n_views * n_chunks_of(vw, P) * 16, 256);
+    }
+    b.take<uint8_t>(256, 256);
+    return w;
 }
-
 uint64_t cam_grad_workspace_bytes(const pnr_views* vw, int64_t P, bool want_point, bool want_cam) {
-    if (!want_point && !want_cam) return 0;
-    return 256 + (want_point ? pt_bytes(P) : 0) + (want_cam ? rec_bytes(vw, P) + part_bytes(vw, P) : 0);
+    return bytes_of([&](Bump& b) { carve_cam_grad(b, vw, P, want_point, want_cam); });
 }
 
 int32_t cam_grad_launch(const pnr_params* prm, const pnr_views* vw, PointSrc src, int64_t P, int64_t pts_per_obj, int L,
                         const float* dzx, int ldz, const CamGradOut& out, hipStream_t s) {
     const bool want_cam = out.d_cam != nullptr, want_rays = out.d_rays != nullptr;
     if (!want_cam && !want_rays && !out.d_dirs) return PNR_OK;
-    if (out.ws_bytes < cam_grad_workspace_bytes(vw, P, want_rays || out.d_dirs, want_cam)) return PNR_E_WORKSPACE;
-    uint8_t* wp = (uint8_t*)round_up_256(out.ws);
-    float* pt = nullptr;
-    if (want_rays) { pt = (float*)wp; wp += pt_bytes(P); }
-    float* rec = nullptr;
-    double* part = nullptr;
-    if (want_cam) { rec = (float*)wp; wp += rec_bytes(vw, P); part = (double*)wp; }
+    Bump bump(round_up_256(out.ws));
+    const CamGradWs w = carve_cam_grad(bump, vw, P, want_rays || out.d_dirs, want_cam);
+    if (out.ws_bytes < bump.off) return PNR_E_WORKSPACE;
+    float* pt = want_rays ? w.pt : nullptr;         // the per-point records feed the ray fold alone; d_dirs is written directly
+    float* rec = w.rec;
+    double* part = w.part;
     hipLaunchKernelGGL(k_cam_grad, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, s, *vw, src, P, pts_per_obj, L,
                        prm->use_code_viewdirs, prm->num_freqs, prm->freq_factor, dzx, ldz, out.d_dirs, pt, (float4*)rec);
     PNR_LAUNCH_CHECK();

@@ -234,9 +234,13 @@ __global__ void __launch_bounds__(FRAME_THREADS) k_eval_finish(const double* __r
 
 using namespace pnr;
 
+// The metrics' workspace: one (squared error, SSIM) pair of partial sums per frame and tile.
+static double* carve_eval(Bump& b, int64_t frames, int W, int H) { return b.take<double>((uint64_t)frames * (uint64_t)frame_tiles(W, H) * 2); }
+static uint64_t eval_ws_bytes(int64_t frames, int W, int H) { return bytes_of([&](Bump& b) { carve_eval(b, frames, W, H); }); }
+
 extern "C" uint64_t pnr_eval_frame_workspace_bytes(int32_t W, int32_t H) {
     if (!frame_pixels_ok(W, H)) return 0;                  // not the tile limit: pnr_eval_frame refuses such a frame itself
-    return (uint64_t)frame_tiles(W, H) * 2 * sizeof(double);
+    return eval_ws_bytes(1, W, H);
 }
 
 extern "C" int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride, const float* depth, int32_t depth_stride, const float* gt,
@@ -261,11 +265,12 @@ extern "C" int32_t pnr_eval_frame(const float* rgb, int32_t rgb_stride, const fl
     a.rgb_stride = rgb_stride; a.depth_stride = depth_stride; a.W = W; a.H = H; a.tiles_x = frame_tiles_x(W);
     a.z_near = z_near; a.z_range = z_far - z_near;
     a.rgb_u8 = rgb_u8; a.compare_u8 = compare_u8; a.depth_norm = depth_norm;
-    a.part = metrics ? (double*)workspace : nullptr;
+    Bump bump(workspace);
+    a.part = metrics ? carve_eval(bump, 1, W, H) : nullptr;
     hipLaunchKernelGGL(k_eval_frame, dim3((unsigned)tiles), dim3(FRAME_THREADS), 0, (hipStream_t)stream, a);
     PNR_LAUNCH_CHECK();
     if (metrics) {
-        hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)workspace, (int)tiles, W,
+        hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)a.part, (int)tiles, W,
                            H, metrics);
         PNR_LAUNCH_CHECK();
     }
@@ -277,7 +282,7 @@ extern "C" uint64_t pnr_eval_frames_workspace_bytes(int32_t F, int32_t W, int32_
     if (F < 1 || !frame_pixels_ok(W, H) || W < EV_WIN || H < EV_WIN) return 0;
     const int64_t tiles = frame_tiles(W, H);
     if (tiles > FRAME_MAX_TILES / F) return 0;
-    return (uint64_t)F * (uint64_t)tiles * 2 * sizeof(double);
+    return eval_ws_bytes(F, W, H);
 }
 
 extern "C" int32_t pnr_eval_frames(const float* rgb, int32_t rgb_stride, int64_t frame_stride, const float* gt, int32_t F, int32_t W,
@@ -296,10 +301,11 @@ extern "C" int32_t pnr_eval_frames(const float* rgb, int32_t rgb_stride, int64_t
     EvalFramesArgs a;
     a.rgb = rgb; a.gt = gt; a.frame_stride = frame_stride;
     a.rgb_stride = rgb_stride; a.W = W; a.H = H; a.tiles_x = frame_tiles_x(W); a.tiles = (int)tiles; a.clamp = clamp;
-    a.part = (double*)workspace;
+    Bump bump(workspace);
+    a.part = carve_eval(bump, F, W, H);
     hipLaunchKernelGGL(k_eval_frames, dim3((unsigned)(F * tiles)), dim3(FRAME_THREADS), 0, (hipStream_t)stream, a);
     PNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)F), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)workspace,
+    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)F), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)a.part,
                        (int)tiles, W, H, metrics);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
@@ -323,10 +329,11 @@ extern "C" int32_t pnr_eval_frames_u8(const uint8_t* pred, int32_t pred_channels
     a.pred = pred; a.gt = gt; a.pred_ch = pred_channels; a.gt_ch = gt_channels;
     a.W = W; a.H = H; a.tiles_x = frame_tiles_x(W); a.tiles = (int)tiles;
     a.pred_planar = pred_planar; a.gt_planar = gt_planar;
-    a.part = (double*)workspace;
+    Bump bump(workspace);
+    a.part = carve_eval(bump, F, W, H);
     hipLaunchKernelGGL(k_eval_frames_u8, dim3((unsigned)(F * tiles)), dim3(FRAME_THREADS), 0, (hipStream_t)stream, a);
     PNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)F), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)workspace,
+    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)F), dim3(FRAME_THREADS), 0, (hipStream_t)stream, (const double*)a.part,
                        (int)tiles, W, H, metrics);
     PNR_LAUNCH_CHECK();
     return PNR_OK;

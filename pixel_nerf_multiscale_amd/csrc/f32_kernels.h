@@ -10,11 +10,13 @@ namespace pnr {
 // instruction (k_features_f32 ran at 0.4-0.5 TB/s, bound by the texture addresser).  With the channel innermost a tap is one
 // 256-byte row.  p[0] == NULL: none (the NCHW reads stay).  Built once per call into the caller's workspace / tape.
 struct LatCL { const float* p[PNR_MAX_LEVELS]; };
-static inline uint64_t latent_cl_bytes(const pnr_views& vw) {
-    uint64_t n = 0;
+// their place in a workspace / tape: one 256-byte piece per level
+static inline LatCL latent_cl_carve(Bump& b, const pnr_views& vw) {
+    LatCL cl{};
     for (int l = 0; l < vw.n_levels; ++l)
-        n += (((uint64_t)vw.n_objs * vw.n_views * vw.lat_c[l] * vw.lat_h[l] * vw.lat_w[l] * 4) + 255) & ~(uint64_t)255;
-    return n;
+        cl.p[l] = b.take<float>((uint64_t)vw.n_objs * vw.n_views * vw.lat_c[l] * vw.lat_h[l] * vw.lat_w[l], 256);
+    b.pad(256);
+    return cl;
 }
 static __global__ void k_latent_to_cl(const float* __restrict__ src, int64_t n_views, int C, int T, float* __restrict__ dst) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;          // over (view, texel, channel): coalesced stores
@@ -25,16 +27,14 @@ static __global__ void k_latent_to_cl(const float* __restrict__ src, int64_t n_v
     const int64_t v = r / T;
     dst[e] = src[(v * C + c) * T + t];
 }
-static inline LatCL latent_cl_build(const pnr_views& vw, void* base, hipStream_t s) {
-    LatCL cl{};
-    uint8_t* p = (uint8_t*)base;
-    for (int l = 0; l < vw.n_levels; ++l) {
+// fills the copies at `cl` (latent_cl_carve) and returns it; none if a map is missing
+static inline LatCL latent_cl_build(const pnr_views& vw, const LatCL& cl, hipStream_t s) {
+    for (int l = 0; l < vw.n_levels; ++l)
         if (!vw.latent[l]) return LatCL{};
+    for (int l = 0; l < vw.n_levels; ++l) {
         const int64_t nv = (int64_t)vw.n_objs * vw.n_views, n = nv * vw.lat_c[l] * vw.lat_h[l] * vw.lat_w[l];
         hipLaunchKernelGGL(k_latent_to_cl, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, vw.latent[l], nv, vw.lat_c[l],
-                           vw.lat_h[l] * vw.lat_w[l], (float*)p);
-        cl.p[l] = (const float*)p;
-        p += ((uint64_t)n * 4 + 255) & ~(uint64_t)255;
+                           vw.lat_h[l] * vw.lat_w[l], const_cast<float*>(cl.p[l]));
     }
     return cl;
 }

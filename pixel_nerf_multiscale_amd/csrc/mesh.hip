@@ -40,20 +40,17 @@ struct McGrid {
 // of a thread never need a tail): code uint16 | voff uint32 | toff uint32 | block totals uint2 (padded to MC_BLOCK entries).
 struct McWs { uint16_t* code; uint32_t* voff; uint32_t* toff; uint2* blk; };
 static inline int64_t mc_blocks(int64_t n) { return (n + MC_BLOCK - 1) / MC_BLOCK; }
-static inline uint64_t mc_ws_bytes(int64_t n) {
+static inline McWs mc_carve(Bump& b, int64_t n) {
     const int64_t B = mc_blocks(n), npad = B * MC_BLOCK, bpad = (B + MC_BLOCK - 1) / MC_BLOCK * MC_BLOCK;
-    return (uint64_t)npad * (2 + 4 + 4) + (uint64_t)bpad * sizeof(uint2);
-}
-static inline McWs mc_carve(void* ws, int64_t n) {
-    const int64_t npad = mc_blocks(n) * MC_BLOCK;
     McWs w;
-    char* p = (char*)ws;
-    w.code = (uint16_t*)p; p += npad * 2;
-    w.voff = (uint32_t*)p; p += npad * 4;
-    w.toff = (uint32_t*)p; p += npad * 4;
-    w.blk = (uint2*)p;
+    w.code = b.take<uint16_t>(npad);
+    w.voff = b.take<uint32_t>(npad);
+    w.toff = b.take<uint32_t>(npad);
+    w.blk = b.take<uint2>(bpad);
     return w;
 }
+static inline McWs mc_carve(const void* ws, int64_t n) { Bump b(const_cast<void*>(ws)); return mc_carve(b, n); }
+static inline uint64_t mc_ws_bytes(int64_t n) { return bytes_of([&](Bump& b) { mc_carve(b, n); }); }
 
 // code: bits 0-7 the cell's case (0 for a point that is no cell origin), bits 8-10 the owned-edge flags (axis 0, 1, 2)
 __device__ __forceinline__ int code_flags(uint32_t code) { return (int)(code >> 8) & 7; }
@@ -336,7 +333,7 @@ extern "C" int32_t pnr_mc_emit(const float* field, int32_t stride, int32_t nx, i
     for (int c = 0; c < 3; ++c) { o.origin[c] = origin[c]; o.scale[c] = scale[c]; }
     o.n_vertices = n_vertices; o.n_triangles = n_triangles; o.vertices = vertices; o.triangles = triangles;
     hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)mc_blocks(g.n)), dim3(MC_THREADS), 0, (hipStream_t)stream, g,
-                       mc_carve(const_cast<void*>(workspace), g.n), o);
+                       mc_carve(workspace, g.n), o);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
 }

@@ -217,7 +217,15 @@ __global__ void __launch_bounds__(OPT_THREADS) k_adam_apply(const pnr_optim_segm
     }
 }
 
-static inline uint64_t round_up_16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
+// pnr_adam_step's workspace, 16-byte pieces: every chunk's fp64 sum of squares | every chunk's non-finite flag
+struct OptimWs { double* part; int32_t* flag; };
+static OptimWs carve_optim(Bump& b, int64_t n_chunks) {
+    OptimWs w;
+    w.part = b.take<double>((uint64_t)n_chunks, 16);
+    w.flag = b.take<int32_t>((uint64_t)n_chunks, 16);
+    b.pad(16);
+    return w;
+}
 constexpr int64_t OPT_MAX_CHUNKS = (int64_t)1 << 31;      // 2^43 parameters
 
 }  // namespace pnr
@@ -246,7 +254,7 @@ extern "C" int64_t pnr_optim_plan(const int64_t* seg_n, int32_t n_segments, pnr_
 
 extern "C" uint64_t pnr_optim_workspace_bytes(int64_t n_chunks) {
     if (n_chunks < 0 || n_chunks >= OPT_MAX_CHUNKS) return 0;
-    return round_up_16((uint64_t)n_chunks * sizeof(double)) + round_up_16((uint64_t)n_chunks * sizeof(int32_t));
+    return bytes_of([&](Bump& b) { carve_optim(b, n_chunks); });
 }
 
 extern "C" int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_segments, const pnr_optim_chunk* chunks,
@@ -264,8 +272,10 @@ extern "C" int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_se
     if ((((uintptr_t)state | (uintptr_t)segments | (uintptr_t)chunks) & 7) != 0) return PNR_E_ALIGN;
     if (n_chunks == 0) return PNR_OK;                     // no gradient anywhere: torch's Adam does nothing either
 
-    double* part = (double*)workspace;
-    int32_t* flag = (int32_t*)((char*)workspace + round_up_16((uint64_t)n_chunks * sizeof(double)));
+    Bump bump(workspace);
+    const OptimWs ws = carve_optim(bump, n_chunks);
+    double* part = ws.part;
+    int32_t* flag = ws.flag;
     const int use_scaler = scaler ? 1 : 0;
     // at most OPT_MAX_GRID workgroups, every one with the same number of chunks (give or take one in the last round): 3500 chunks
     // run as 1750 workgroups of two, not as 2048 of which 1452 take a second one while the rest idle

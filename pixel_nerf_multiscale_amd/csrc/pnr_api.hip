@@ -57,7 +57,7 @@ extern "C" const char* pnr_error_string(int32_t code) {
 
 static int32_t check_model(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw) {
     if (!prm || !mlp || !vw) return PNR_E_NULL;
-    if (!mlp->lin_in_w || !mlp->lin_in_b || !mlp->lin_out_w || !mlp->lin_out_b) return PNR_E_NULL;
+    if (!mlp_pointers_set(mlp, 0, 0)) return PNR_E_NULL;       // lin_in / lin_out: a NULL there comes before a bad shape
     if (mlp->d_out != 4 || mlp->d_hidden <= 0 || mlp->n_blocks < 1 || mlp->n_blocks > PNR_MAX_BLOCKS) return PNR_E_SHAPE;
     if (mlp->combine_type != PNR_COMBINE_AVERAGE && mlp->combine_type != PNR_COMBINE_MAX) return PNR_E_UNSUPPORTED;
     if (prm->num_freqs < 1 || prm->num_freqs > 16) return PNR_E_SHAPE;
@@ -76,10 +76,7 @@ static int32_t check_model(const pnr_params* prm, const pnr_mlp* mlp, const pnr_
     if (L != mlp->d_latent) return PNR_E_SHAPE;
     const int nz = n_lin_z(mlp);
     if (nz < 0) return PNR_E_SHAPE;
-    for (int b = 0; b < mlp->n_blocks; ++b) {
-        if (!mlp->fc0_w[b] || !mlp->fc0_b[b] || !mlp->fc1_w[b] || !mlp->fc1_b[b]) return PNR_E_NULL;
-        if (b < nz && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return PNR_E_NULL;
-    }
+    if (!mlp_pointers_set(mlp, nz)) return PNR_E_NULL;
     if (vw->n_views > 1 && mlp->combine_layer >= mlp->n_blocks) return PNR_E_UNSUPPORTED;
     if (prm->precision != PNR_F32 && prm->precision != PNR_BF16 && prm->precision != PNR_F16 && prm->precision != PNR_BF16X3)
         return PNR_E_UNSUPPORTED;
@@ -139,13 +136,7 @@ static int32_t check_mlp_f32(const pnr_mlp* mlp) {
     if (!mlp) return PNR_E_NULL;
     if (mlp->d_in <= 0 || mlp->d_latent < 0 || mlp->d_hidden <= 0 || mlp->d_out <= 0 || mlp->n_blocks < 0 ||
         mlp->n_blocks > PNR_MAX_BLOCKS) return PNR_E_SHAPE;
-    if (!mlp->lin_in_w || !mlp->lin_in_b || !mlp->lin_out_w || !mlp->lin_out_b) return PNR_E_NULL;
-    const int nz = n_lin_z(mlp);
-    for (int b = 0; b < mlp->n_blocks; ++b) {
-        if (!mlp->fc0_w[b] || !mlp->fc0_b[b] || !mlp->fc1_w[b] || !mlp->fc1_b[b]) return PNR_E_NULL;
-        if (mlp->d_latent > 0 && b < nz && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return PNR_E_NULL;
-    }
-    return PNR_OK;
+    return mlp_pointers_set(mlp, mlp->d_latent > 0 ? n_lin_z(mlp) : 0) ? PNR_OK : PNR_E_NULL;
 }
 
 extern "C" uint64_t pnr_resnetfc_workspace_bytes(const pnr_mlp* mlp, int32_t n_inner_views) {
@@ -215,30 +206,18 @@ extern "C" int32_t pnr_point_mlp_train_fwd(const pnr_params* params, const pnr_m
     return point_train_fwd(params, mlp, views, src, n_points, points_per_obj, out, tape, tape_bytes, (hipStream_t)stream);
 }
 
-extern "C" int32_t pnr_point_mlp_bwd(const pnr_params* params, const pnr_mlp* mlp, const pnr_views* views,
-                                     const float* rays, const float* z, int32_t K, const float* xyz,
-                                     const float* viewdirs, int64_t n_points, int64_t points_per_obj,
-                                     const float* out, const float* d_out, void* tape, uint64_t tape_bytes,
-                                     const pnr_mlp_grads* grads, float* const* d_latent, float* d_xyz, float* d_z,
-                                     void* workspace, uint64_t workspace_bytes, void* stream) {
-    PointSrc src;
-    int32_t rc = point_args(params, mlp, views, rays, z, K, xyz, viewdirs, n_points, points_per_obj, &src);
-    if (rc) return rc;
-    if (!out || !d_out || !grads || ((!tape || !workspace) && n_points > 0)) return PNR_E_NULL;
-    if ((((uintptr_t)out | (uintptr_t)d_out) & 15) != 0) return PNR_E_ALIGN;
-    if (rays ? d_xyz != nullptr : d_z != nullptr) return PNR_E_SHAPE;   // d_z goes with rays, d_xyz with explicit points
-    if (n_points == 0) return PNR_OK;
-    return point_bwd(params, mlp, views, src, n_points, points_per_obj, out, d_out, tape, tape_bytes, grads, d_latent,
-                     d_xyz, d_z, workspace, workspace_bytes, (hipStream_t)stream);
+// The camera outputs' scratch follows the backward's own workspace, on the next 256-byte boundary.
+struct BwdCamWs { uint8_t* cam; };
+static BwdCamWs carve_bwd_cam(Bump& b, const pnr_mlp* mlp, const pnr_views* views, int64_t n_points, bool want_point, bool want_cam) {
+    b.take<uint8_t>(train_bwd_workspace_bytes(mlp, views, n_points));
+    const uint64_t extra = cam_grad_workspace_bytes(views, n_points, want_point, want_cam);
+    return BwdCamWs{extra ? b.take<uint8_t>(extra, 256) : nullptr};
 }
 
-// The camera outputs' scratch follows the backward's own workspace, on the next 256-byte boundary.
 extern "C" uint64_t pnr_train_bwd_cam_workspace_bytes(const pnr_mlp* mlp, const pnr_views* views, int64_t n_points,
                                                       int32_t want_point, int32_t want_cam) {
     if (!mlp || !views || n_points < 0) return 0;
-    const uint64_t base = train_bwd_workspace_bytes(mlp, views, n_points);
-    const uint64_t extra = cam_grad_workspace_bytes(views, n_points, want_point != 0, want_cam != 0);
-    return extra ? round_up_256(base) + extra : base;
+    return bytes_of([&](Bump& b) { carve_bwd_cam(b, mlp, views, n_points, want_point != 0, want_cam != 0); });
 }
 
 extern "C" int32_t pnr_point_mlp_bwd_cam(const pnr_params* params, const pnr_mlp* mlp, const pnr_views* views,
@@ -261,37 +240,52 @@ extern "C" int32_t pnr_point_mlp_bwd_cam(const pnr_params* params, const pnr_mlp
     if (!want_point && !d_cam)
         return point_bwd(params, mlp, views, src, n_points, points_per_obj, out, d_out, tape, tape_bytes, grads, d_latent,
                          d_xyz, d_z, workspace, workspace_bytes, (hipStream_t)stream);
-    if (workspace_bytes < pnr_train_bwd_cam_workspace_bytes(mlp, views, n_points, want_point, d_cam != nullptr)) return PNR_E_WORKSPACE;
-    const uint64_t base = round_up_256(train_bwd_workspace_bytes(mlp, views, n_points));
-    const CamGradOut cam{d_dirs, d_rays, d_cam, (uint8_t*)workspace + base, workspace_bytes - base};
+    Bump bump(workspace);
+    const BwdCamWs w = carve_bwd_cam(bump, mlp, views, n_points, want_point, d_cam != nullptr);
+    if (workspace_bytes < bump.off) return PNR_E_WORKSPACE;
+    const uint64_t base = (uint64_t)(w.cam - (uint8_t*)workspace);
+    const CamGradOut cam{d_dirs, d_rays, d_cam, w.cam, workspace_bytes - base};
     return point_bwd(params, mlp, views, src, n_points, points_per_obj, out, d_out, tape, tape_bytes, grads, d_latent,
                      d_xyz, d_z, workspace, base, (hipStream_t)stream, &cam);
 }
 
-struct RenderWs { uint64_t zc, zf, rgbs, w, rgb, depth, rays, point, total; };
+// pnr_point_mlp_bwd_cam with no camera output asked for (include/pnr.h)
+extern "C" int32_t pnr_point_mlp_bwd(const pnr_params* params, const pnr_mlp* mlp, const pnr_views* views,
+                                     const float* rays, const float* z, int32_t K, const float* xyz,
+                                     const float* viewdirs, int64_t n_points, int64_t points_per_obj,
+                                     const float* out, const float* d_out, void* tape, uint64_t tape_bytes,
+                                     const pnr_mlp_grads* grads, float* const* d_latent, float* d_xyz, float* d_z,
+                                     void* workspace, uint64_t workspace_bytes, void* stream) {
+    return pnr_point_mlp_bwd_cam(params, mlp, views, rays, z, K, xyz, viewdirs, n_points, points_per_obj, out, d_out, tape, tape_bytes,
+                                 grads, d_latent, d_xyz, d_z, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
 
-// `fine` (may be NULL): the point workspace is shared by both passes, so it is sized for the larger of the two MLPs
-static RenderWs carve(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, int64_t n, const pnr_mlp* fine = nullptr) {
+// The render workspace (256-byte pieces behind a base rounded up to 256, + that slack): positions, the point pass's (rgb, sigma),
+// the coarse outputs a caller did not ask for, the rays pnr_render_camera materialises on the fp32 path, and the point
+// workspace — shared by both passes, so sized for the larger of the two MLPs (`fine` may be NULL).
+struct RenderWs { float *zc, *zf, *rgbs, *w, *rgb, *depth, *rays; uint8_t* point; };
+
+static RenderWs carve(Bump& b, const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, int64_t n, const pnr_mlp* fine = nullptr) {
     RenderWs r;
-    uint64_t Kc = prm->n_coarse, Kt = (uint64_t)prm->n_coarse + prm->n_fine, off = 0;
-    r.zc = off; off += round_up_256(n * Kc * 4);
-    r.zf = off; off += round_up_256(n * Kt * 4);
-    r.rgbs = off; off += round_up_256(n * Kt * 16);
-    r.w = off; off += round_up_256(n * Kt * 4);
-    r.rgb = off; off += round_up_256(n * 12);
-    r.depth = off; off += round_up_256(n * 4);
-    r.rays = off; off += round_up_256(n * 32);          // pnr_render_camera on the fp32 path materialises its rays here
+    const uint64_t Kc = prm->n_coarse, Kt = (uint64_t)prm->n_coarse + prm->n_fine;
+    r.zc = b.take<float>(n * Kc, 256);
+    r.zf = b.take<float>(n * Kt, 256);
+    r.rgbs = b.take<float>(n * Kt * 4, 256);
+    r.w = b.take<float>(n * Kt, 256);
+    r.rgb = b.take<float>(n * 3, 256);
+    r.depth = b.take<float>(n, 256);
+    r.rays = b.take<float>(n * 8, 256);
     uint64_t pw = point_workspace_bytes(prm, mlp, vw);
     if (fine) { uint64_t pf = point_workspace_bytes(prm, fine, vw); if (pf > pw) pw = pf; }
-    r.point = off; off += round_up_256(pw);
-    r.total = off + 256;
+    r.point = b.take<uint8_t>(pw, 256);
+    b.take<uint8_t>(256, 256);
     return r;
 }
 
 extern "C" uint64_t pnr_workspace_bytes(const pnr_params* params, const pnr_mlp* mlp, const pnr_views* views,
                                         int64_t n_rays) {
     if (!params || !mlp || !views || n_rays < 0) return 0;
-    return carve(params, mlp, views, n_rays).total;
+    return bytes_of([&](Bump& b) { carve(b, params, mlp, views, n_rays); });
 }
 
 // pnr_render / pnr_render_camera: `rays` or `cam` (+ first pixel)
@@ -308,18 +302,18 @@ static int32_t render_impl(const pnr_params* params, const pnr_mlp* coarse, cons
     if (n_rays < 0 || rays_per_obj <= 0 || n_rays != rays_per_obj * views->n_objs) return PNR_E_SHAPE;
     if (n_rays == 0) return PNR_OK;
     if (!workspace) return PNR_E_NULL;
-    RenderWs cw = carve(params, coarse, views, n_rays, params->n_fine > 0 ? fine : nullptr);
-    if (workspace_bytes < cw.total) return PNR_E_WORKSPACE;     // pnr_workspace_bytes of BOTH MLPs, the larger one
-    char* base = (char*)round_up_256(workspace);
+    Bump bump(round_up_256(workspace));
+    const RenderWs cw = carve(bump, params, coarse, views, n_rays, params->n_fine > 0 ? fine : nullptr);
+    if (workspace_bytes < bump.off) return PNR_E_WORKSPACE;     // pnr_workspace_bytes of BOTH MLPs, the larger one
     hipStream_t s = (hipStream_t)stream;
     const int Kc = params->n_coarse, Kf = params->n_fine, Kfd = params->n_fine_depth, Kt = Kc + Kf;
-    float* zc = outputs->z_coarse ? outputs->z_coarse : (float*)(base + cw.zc);
-    float* zf = outputs->z_fine ? outputs->z_fine : (float*)(base + cw.zf);
-    float* rgbs = (float*)(base + cw.rgbs);
-    float* w_c = outputs->coarse_weights ? outputs->coarse_weights : (float*)(base + cw.w);
-    float* rgb_c = outputs->coarse_rgb ? outputs->coarse_rgb : (float*)(base + cw.rgb);
-    float* dep_c = outputs->coarse_depth ? outputs->coarse_depth : (float*)(base + cw.depth);
-    void* pws = base + cw.point;
+    float* zc = outputs->z_coarse ? outputs->z_coarse : cw.zc;
+    float* zf = outputs->z_fine ? outputs->z_fine : cw.zf;
+    float* rgbs = cw.rgbs;
+    float* w_c = outputs->coarse_weights ? outputs->coarse_weights : cw.w;
+    float* rgb_c = outputs->coarse_rgb ? outputs->coarse_rgb : cw.rgb;
+    float* dep_c = outputs->coarse_depth ? outputs->coarse_depth : cw.depth;
+    void* pws = cw.point;
     uint64_t pws_bytes = workspace_bytes - (uint64_t)((char*)pws - (char*)workspace);
     const pnr_noise nz = noise ? *noise : pnr_noise{nullptr, nullptr, nullptr, nullptr, 0};
     if (Kf > 0 && (!outputs->fine_rgb || !outputs->fine_depth)) return PNR_E_NULL;
@@ -376,7 +370,7 @@ static int32_t render_impl(const pnr_params* params, const pnr_mlp* coarse, cons
 
     // fp32 path: the stages as separate launches
     if (!rays) {
-        float* rbuf = (float*)(base + cw.rays);
+        float* rbuf = cw.rays;
         // c2w back from the RayCam for the stage entry point
         const float m[16] = {cam->R[0], cam->R[1], cam->R[2], cam->o[0], cam->R[3], cam->R[4], cam->R[5], cam->o[1],
                              cam->R[6], cam->R[7], cam->R[8], cam->o[2], 0.f, 0.f, 0.f, 1.f};

@@ -31,6 +31,60 @@ inline int n_lin_z(const pnr_mlp* mlp) { return mlp->combine_layer < mlp->n_bloc
 inline uint64_t round_up_256(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
 template <typename T> inline T* round_up_256(T* p) { return (T*)round_up_256((uint64_t)(uintptr_t)p); }
 
+// A caller's workspace, handed out piece by piece.  Every layout of the library is ONE function that takes its pieces from a
+// Bump in their order and returns them as typed pointers; run on a null base the same function only counts, and `off` is then
+// the layout's *_bytes — size and pointers cannot disagree.  take() starts a piece on the next multiple of `align` from the
+// base (the layouts that want aligned addresses round their base up first and add that slack to their size).
+struct Bump {
+    uint8_t* base;
+    uint64_t off = 0;
+    explicit Bump(void* b) : base((uint8_t*)b) {}
+    template <typename T> T* take(uint64_t count, uint64_t align = 1) {
+        off = (off + align - 1) / align * align;
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += count * sizeof(T);
+        return p;
+    }
+    void pad(uint64_t align) { take<uint8_t>(0, align); }      // the next piece, or the end, on a multiple of `align`
+};
+// the bytes a layout function asks for: carve(Bump&) on a null base
+template <typename Carve> inline uint64_t bytes_of(Carve carve) { Bump b(nullptr); carve(b); return b.off; }
+
+// Are the weight and bias pointers of an MLP set: lin_in, lin_out, fc_0 / fc_1 of every block, and lin_z of the first
+// n_lin_z_required blocks (every caller has its own count).  n_blocks: the blocks to look at — a caller that has not yet
+// checked mlp->n_blocks against PNR_MAX_BLOCKS passes 0 and asks about lin_in / lin_out alone.
+inline bool mlp_pointers_set(const pnr_mlp* mlp, int n_lin_z_required, int n_blocks) {
+    if (!mlp->lin_in_w || !mlp->lin_in_b || !mlp->lin_out_w || !mlp->lin_out_b) return false;
+    for (int b = 0; b < n_blocks; ++b) {
+        if (!mlp->fc0_w[b] || !mlp->fc0_b[b] || !mlp->fc1_w[b] || !mlp->fc1_b[b]) return false;
+        if (b < n_lin_z_required && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return false;
+    }
+    return true;
+}
+inline bool mlp_pointers_set(const pnr_mlp* mlp, int n_lin_z_required) { return mlp_pointers_set(mlp, n_lin_z_required, mlp->n_blocks); }
+
+// One int per device, zero until set: what the library remembers about a device (an immutable attribute, a function
+// attribute that sticks once raised) — not library state in the sense of pnr.h.  slot(): the current device's, or null
+// without a device.
+struct PerDevice {
+    int v[64] = {0};
+    int* slot() {
+        int dev = 0;
+        return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) ? &v[dev] : nullptr;
+    }
+};
+// An integer attribute of the current device, asked once per device (hipDeviceGetAttribute is slow); `fallback` without a
+// device or where the runtime gives nothing usable.
+inline int device_attr(PerDevice& cache, hipDeviceAttribute_t attr, int fallback) {
+    int* c = cache.slot();
+    if (!c) return fallback;
+    if (*c == 0) {
+        int n = 0;
+        *c = (hipDeviceGetAttribute(&n, attr, (int)(c - cache.v)) == hipSuccess && n > 0) ? n : fallback;
+    }
+    return *c;
+}
+
 // ---------------------------------------------------------------- counter-based RNG (Philox4x32-10)
 // Keyed by (seed, global ray index, draw id); the same ray gets the same draws on any GPU / any
 // sharding, so an N-GPU frame is bit-identical to the 1-GPU frame.

@@ -21,9 +21,23 @@ static int32_t linear(const float* X, int ldx, const float* W, const float* b, f
 // against 0.64 (24576: 0.62; 98304 / 196608: 0.64 / 0.65).  Workspace: ~5.3 KB per point and view.
 static const int F32_CHUNK = 49152;
 
+// The workspace of a call, behind a base rounded up to 256: the assembled rows, the residual stream, fc_0's output and the head's
+// output of one chunk, back to back; the channels-last latent copies of the call; 512 bytes of slack for the two roundings.
+struct PointF32Ws { float *zx, *x, *h, *o4; LatCL cl; };
+static PointF32Ws carve_point_f32(Bump& b, const pnr_mlp* mlp, const pnr_views* vw) {
+    const uint64_t rows = (uint64_t)F32_CHUNK * vw->n_views;
+    PointF32Ws w;
+    w.zx = b.take<float>(rows * feature_stride(mlp));
+    w.x = b.take<float>(rows * mlp->d_hidden);
+    w.h = b.take<float>(rows * mlp->d_hidden);
+    w.o4 = b.take<float>((uint64_t)F32_CHUNK * 4);
+    b.pad(256);
+    w.cl = latent_cl_carve(b, *vw);
+    b.take<uint8_t>(512);
+    return w;
+}
 uint64_t point_f32_workspace_bytes(const pnr_mlp* mlp, const pnr_views* vw) {
-    uint64_t per_pt = (uint64_t)vw->n_views * (feature_stride(mlp) + 2ull * mlp->d_hidden) + 4;
-    return per_pt * F32_CHUNK * sizeof(float) + 512 + latent_cl_bytes(*vw);      // + the channels-last latent copies of a call
+    return bytes_of([&](Bump& b) { carve_point_f32(b, mlp, vw); });
 }
 
 // ResnetFC.forward (resnetfc.py:203-236) on M = CH * NS assembled rows zx (row = view * CH + point, [z | x], row stride E):
@@ -53,17 +67,15 @@ static int32_t chain_f32(const pnr_mlp* mlp, const float* zx, int E, int CH, int
 
 int32_t point_f32(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, PointSrc src, int64_t n_points,
                   int64_t pts_per_obj, float* out, void* workspace, uint64_t ws_bytes, hipStream_t s) {
-    if (ws_bytes < point_f32_workspace_bytes(mlp, vw)) return PNR_E_WORKSPACE;
+    Bump bump(round_up_256(workspace));
+    const PointF32Ws w = carve_point_f32(bump, mlp, vw);
+    if (ws_bytes < bump.off) return PNR_E_WORKSPACE;
     if (mlp->d_out != 4) return PNR_E_SHAPE;
-    const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden;
+    const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in;
     const int E = feature_stride(mlp);
-    float* zx = (float*)round_up_256(workspace);
-    float* x = zx + (size_t)F32_CHUNK * NS * E;
-    float* h = x + (size_t)F32_CHUNK * NS * H;
-    float* o4 = h + (size_t)F32_CHUNK * NS * H;
+    float *zx = w.zx, *x = w.x, *h = w.h, *o4 = w.o4;
     // channels-last copies of the maps, once per call (a frame is many chunks): the feature build then reads whole rows
-    void* cl_base = round_up_256(o4 + (size_t)F32_CHUNK * 4);
-    const LatCL cl = (L > 0 && n_points >= 4096) ? latent_cl_build(*vw, cl_base, s) : LatCL{};
+    const LatCL cl = (L > 0 && n_points >= 4096) ? latent_cl_build(*vw, w.cl, s) : LatCL{};
     PNR_LAUNCH_CHECK();
     for (int64_t g0 = 0; g0 < n_points; g0 += F32_CHUNK) {
         int CH = (int)((n_points - g0 < F32_CHUNK) ? (n_points - g0) : F32_CHUNK);
@@ -78,17 +90,27 @@ int32_t point_f32(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
 }
 
 // ResnetFC.forward on caller-assembled rows (pnr_resnetfc_forward): zx (outer, NS, B, E) -> out (outer, B, d_out).
+// workspace, behind a base rounded up to 256 (+ that slack): a chunk's gathered rows, the residual stream and fc_0's output
+struct ResnetfcWs { float *zc, *x, *h; };
+static ResnetfcWs carve_resnetfc(Bump& b, const pnr_mlp* mlp, int NS) {
+    const uint64_t rows = (uint64_t)F32_CHUNK * NS;
+    ResnetfcWs w;
+    w.zc = b.take<float>(rows * (mlp->d_latent + mlp->d_in));
+    w.x = b.take<float>(rows * mlp->d_hidden);
+    w.h = b.take<float>(rows * mlp->d_hidden);
+    b.take<uint8_t>(256);
+    return w;
+}
 uint64_t resnetfc_f32_workspace_bytes(const pnr_mlp* mlp, int NS) {
-    uint64_t per_pt = (uint64_t)NS * (mlp->d_latent + mlp->d_in + 2ull * mlp->d_hidden);
-    return per_pt * F32_CHUNK * sizeof(float) + 256;
+    return bytes_of([&](Bump& b) { carve_resnetfc(b, mlp, NS); });
 }
 int32_t resnetfc_f32(const pnr_mlp* mlp, const float* zx, int64_t outer, int NS, int64_t B, float* out, void* workspace,
                      uint64_t ws_bytes, hipStream_t s) {
-    if (ws_bytes < resnetfc_f32_workspace_bytes(mlp, NS)) return PNR_E_WORKSPACE;
-    const int H = mlp->d_hidden, E = mlp->d_latent + mlp->d_in;
-    float* zc = (float*)round_up_256(workspace);
-    float* x = zc + (size_t)F32_CHUNK * NS * E;
-    float* h = x + (size_t)F32_CHUNK * NS * H;
+    Bump bump(round_up_256(workspace));
+    const ResnetfcWs w = carve_resnetfc(bump, mlp, NS);
+    if (ws_bytes < bump.off) return PNR_E_WORKSPACE;
+    const int E = mlp->d_latent + mlp->d_in;
+    float *zc = w.zc, *x = w.x, *h = w.h;
     for (int64_t o = 0; o < outer; ++o)
         for (int64_t p0 = 0; p0 < B; p0 += F32_CHUNK) {
             const int CH = (int)((B - p0 < F32_CHUNK) ? (B - p0) : F32_CHUNK);

@@ -1034,16 +1034,8 @@ __global__ void __launch_bounds__(256, 1) k_point_mfma(MfmaArgs a) {
 
 // ---------------------------------------------------------------------------- host side
 static int num_cus() {
-    // immutable per-device property, cached (hipGetDeviceProperties is slow); not library state in the sense of pnr.h
-    static int cached[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cached[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cached[dev] = n;
-    }
-    return cached[dev];
+    static PerDevice cache;
+    return device_attr(cache, hipDeviceAttributeMultiprocessorCount, 256);
 }
 static constexpr int MAX_GRID = 512;
 
@@ -1053,11 +1045,52 @@ static int cached_groups(const pnr_mlp* mlp, const pnr_views* vw) {
     const int groups = mlp->d_latent / 256;
     return groups > 1 ? groups : 0;
 }
-static uint64_t spill_bytes(const pnr_views* vw) {
-    return vw->n_views > 1 ? (uint64_t)MAX_GRID * 4 * (vw->n_views - 1) * 4096 * sizeof(float4) : 0;
+// Workspace (behind a base rounded up to 256, + that slack), per workgroup slot and wave: the parked accumulators of the
+// views before the last, 64 x 64 float4 each, and the cached lin_z images.
+struct MfmaWs { float4* spill; char* gcache; };
+static MfmaWs carve_point_mfma(Bump& b, const pnr_mlp* mlp, const pnr_views* vw) {
+    MfmaWs w;
+    w.spill = b.take<float4>(vw->n_views > 1 ? (uint64_t)MAX_GRID * 4 * (vw->n_views - 1) * 4096 : 0);
+    w.gcache = b.take<char>((uint64_t)MAX_GRID * 4 * cached_groups(mlp, vw) * ZBUF_BYTES);
+    b.take<uint8_t>(256);
+    return w;
 }
 uint64_t point_mfma_workspace_bytes(const pnr_mlp* mlp, const pnr_views* vw) {
-    return 256 + spill_bytes(vw) + (uint64_t)MAX_GRID * 4 * cached_groups(mlp, vw) * ZBUF_BYTES;
+    return bytes_of([&](Bump& b) { carve_point_mfma(b, mlp, vw); });
+}
+
+// How a launch's work is split over workgroups (pnr_debug_point_split in pnr.h).  Workgroups share the whole call, or, with
+// projected streams of several objects, each object has its own so that a workgroup streams ONE object's weights.  A plain
+// launch gives every workgroup the same run of tiles; a fused render launch whole rays, at least about a tile's worth of
+// points each.  The grid is then what that share leaves occupied.
+struct PointSplit { int grid, tiles_per_wg, rays_per_wg, wgs_per_obj; };
+static int32_t point_split(int max_wgs, int n_stream_objs, int K, int64_t count, int64_t per_obj, PointSplit* o) {
+    *o = PointSplit{};
+    const bool per_object = n_stream_objs > 1;
+    int64_t wgs = max_wgs, n = count;
+    if (per_object) {
+        wgs = max_wgs / n_stream_objs;
+        if (wgs < 1) wgs = 1;
+        if (wgs * n_stream_objs > MAX_GRID) return PNR_E_UNSUPPORTED;
+        n = per_obj;
+    }
+    if (K > 0) {
+        int64_t rpw = (n + wgs - 1) / wgs;
+        const int64_t min_rpw = (TILE_PTS + K - 1) / K;
+        if (rpw < min_rpw) rpw = min_rpw;
+        if (rpw * K >= 0x7fffffffLL) return PNR_E_SHAPE;
+        o->rays_per_wg = (int)rpw;
+        wgs = (n + rpw - 1) / rpw;
+    } else {
+        const int64_t tiles = (n + TILE_PTS - 1) / TILE_PTS;
+        const int64_t tpw = (tiles + wgs - 1) / wgs;
+        if (tpw * TILE_PTS >= 0x7fffffffLL) return PNR_E_SHAPE;
+        o->tiles_per_wg = (int)tpw;
+        wgs = (tiles + tpw - 1) / tpw;
+    }
+    if (per_object) { o->wgs_per_obj = (int)wgs; wgs *= n_stream_objs; }
+    o->grid = (int)wgs;
+    return PNR_OK;
 }
 
 int32_t point_mfma(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw, PointSrc src, int64_t n_points,
@@ -1085,7 +1118,9 @@ int32_t point_mfma(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* v
             if (vw->lat_c[i] % 32 != 0) return PNR_E_UNSUPPORTED;   // a k-step of the gather is 32 channels of one level
         }
     }
-    if (ws_bytes < point_mfma_workspace_bytes(mlp, vw)) return PNR_E_WORKSPACE;
+    Bump bump(round_up_256(workspace));
+    const MfmaWs ws = carve_point_mfma(bump, mlp, vw);
+    if (ws_bytes < bump.off) return PNR_E_WORKSPACE;
     if (vw->n_views > 1 && y.nb1 == 0) return PNR_E_UNSUPPORTED;     // reduction before the first block
     if (prm->use_code_viewdirs ? (mlp->d_in != 6 + 12 * prm->num_freqs) : (mlp->d_in != 6 + 6 * prm->num_freqs)) return PNR_E_SHAPE;
     if (prm->num_freqs != 6) return PNR_E_UNSUPPORTED;     // the LIN_IN slot layout is built for 6 frequencies (every shipped config)
@@ -1096,8 +1131,8 @@ int32_t point_mfma(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* v
     a.stream = (const char*)mlp->packed + y.btab_bytes;
     for (int i = 0; i < PNR_MAX_LEVELS; ++i) a.lat[i] = (const char*)vw->latent_packed[i];
     a.out = out;
-    a.spill = (float4*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    a.gcache = (char*)a.spill + spill_bytes(vw);
+    a.spill = ws.spill;
+    a.gcache = ws.gcache;
     a.n_cached = cached_groups(mlp, vw);
     a.n_tiles = (int)((n_points + TILE_PTS - 1) / TILE_PTS);
     a.NS = vw->n_views; a.combine_max = mlp->combine_type == PNR_COMBINE_MAX;
@@ -1106,58 +1141,23 @@ int32_t point_mfma(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* v
     a.btab_floats = y.btab_floats; a.d_in = mlp->d_in; a.proj = proj; a.Gg = y.Gg;
     a.ldP1 = proj ? y.PV * y.P1 : y.P1; a.ldNS = proj ? 1 : vw->n_views;
     a.use_code_viewdirs = prm->use_code_viewdirs; a.num_freqs = prm->num_freqs; a.freq_factor = prm->freq_factor;
-    int grid = num_cus();
-    if (grid > MAX_GRID) grid = MAX_GRID;
     a.job = RayJob{};
-    a.tiles_per_wg = 0;
-    a.wgs_per_obj = 0;
-    a.obj_stream_stride = 0;
-    if (proj && vw->n_objs > 1) {
-        // several objects with projected streams: workgroups per object, so that a workgroup streams ONE object's weights
-        const int n_objs = vw->n_objs;
-        int wpo = grid / n_objs;
-        if (wpo < 1) wpo = 1;
-        if ((int64_t)wpo * n_objs > MAX_GRID) return PNR_E_UNSUPPORTED;
-        a.obj_stream_stride = (int64_t)y.stream_bytes;
-        if (job && job->on) {
-            a.job = *job;
-            if (a.job.K < 1 || a.job.n_rays * a.job.K != n_points || !a.job.rgb_out || !a.job.depth_out) return PNR_E_SHAPE;
-            if (a.job.gen_z ? !a.job.z_out : !src.z) return PNR_E_NULL;
-            if (!a.job.from_cam && !src.rays) return PNR_E_NULL;
-            const int64_t rays_per_obj = pts_per_obj / a.job.K;
-            int64_t rpw = (rays_per_obj + wpo - 1) / wpo;
-            const int64_t min_rpw = (TILE_PTS + a.job.K - 1) / a.job.K;
-            if (rpw < min_rpw) rpw = min_rpw;
-            if (rpw * a.job.K >= 0x7fffffffLL) return PNR_E_SHAPE;
-            a.job.rays_per_wg = (int)rpw;
-            wpo = (int)((rays_per_obj + rpw - 1) / rpw);
-        } else {
-            const int64_t tiles_obj = (pts_per_obj + TILE_PTS - 1) / TILE_PTS;
-            int64_t tpw = (tiles_obj + wpo - 1) / wpo;
-            if (tpw * TILE_PTS >= 0x7fffffffLL) return PNR_E_SHAPE;
-            a.tiles_per_wg = (int)tpw;
-            wpo = (int)((tiles_obj + tpw - 1) / tpw);
-        }
-        a.wgs_per_obj = wpo;
-        grid = wpo * n_objs;
-    } else if (job && job->on) {
-        // whole rays per workgroup, at least about a tile's worth of points each
+    const bool fused = job && job->on;
+    if (fused) {
         a.job = *job;
         if (a.job.K < 1 || a.job.n_rays * a.job.K != n_points || !a.job.rgb_out || !a.job.depth_out) return PNR_E_SHAPE;
         if (a.job.gen_z ? !a.job.z_out : !src.z) return PNR_E_NULL;
         if (!a.job.from_cam && !src.rays) return PNR_E_NULL;
-        int64_t rpw = (a.job.n_rays + grid - 1) / grid;
-        const int64_t min_rpw = (TILE_PTS + a.job.K - 1) / a.job.K;
-        if (rpw < min_rpw) rpw = min_rpw;
-        if (rpw * a.job.K >= 0x7fffffffLL) return PNR_E_SHAPE;
-        a.job.rays_per_wg = (int)rpw;
-        grid = (int)((a.job.n_rays + rpw - 1) / rpw);
-    } else {
-        int64_t tpw = ((int64_t)a.n_tiles + grid - 1) / grid;
-        if (tpw * TILE_PTS >= 0x7fffffffLL) return PNR_E_SHAPE;
-        a.tiles_per_wg = (int)tpw;
-        grid = (int)((a.n_tiles + tpw - 1) / tpw);
     }
+    const int cus = num_cus(), K = fused ? a.job.K : 0;
+    PointSplit split;
+    PNR_TRY(point_split(cus < MAX_GRID ? cus : MAX_GRID, proj ? vw->n_objs : 1, K, fused ? a.job.n_rays : n_points,
+                        fused ? pts_per_obj / K : pts_per_obj, &split));
+    const int grid = split.grid;
+    a.tiles_per_wg = split.tiles_per_wg;
+    a.job.rays_per_wg = split.rays_per_wg;
+    a.wgs_per_obj = split.wgs_per_obj;
+    a.obj_stream_stride = split.wgs_per_obj ? (int64_t)y.stream_bytes : 0;
     size_t lds = LDS_BTAB + (size_t)y.btab_floats * 4;
     // compositing from the LDS ring: fused render launches whose rays are at most a tile long, where the ring fits behind the
     // bias table; everything else composites from the (rgb, sigma) / z the launch leaves in global memory
@@ -1232,11 +1232,7 @@ extern "C" int32_t pnr_pack_mlp_projected(const pnr_mlp* mlp, const pnr_views* v
     const int n_objs = views->n_objs;
     if (out_bytes < y.btab_bytes + (uint64_t)n_objs * (y.stream_bytes + y.proj_bytes)) return PNR_E_WORKSPACE;
     if (((uintptr_t)out & 15) != 0) return PNR_E_ALIGN;
-    if (!mlp->lin_in_w || !mlp->lin_in_b || !mlp->lin_out_w || !mlp->lin_out_b) return PNR_E_NULL;
-    for (int b = 0; b < mlp->n_blocks; ++b) {
-        if (!mlp->fc0_w[b] || !mlp->fc0_b[b] || !mlp->fc1_w[b] || !mlp->fc1_b[b]) return PNR_E_NULL;
-        if (b < y.nb1 && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return PNR_E_NULL;
-    }
+    if (!mlp_pointers_set(mlp, y.nb1)) return PNR_E_NULL;
     // blob: [bias table][stream of object 0][stream of object 1]..[fp32 M scratch of object 0]..
     const int last = views->n_levels - 1;
     const size_t lat_obj = (size_t)views->n_views * views->lat_c[last] * T;          // floats of one object's views in the last level
@@ -1261,11 +1257,7 @@ extern "C" int32_t pnr_pack_mlp(const pnr_mlp* mlp, int32_t dtype, void* out, ui
     if (dtype != PNR_BF16 && dtype != PNR_F16) return PNR_E_UNSUPPORTED;
     if (out_bytes < y.total_bytes) return PNR_E_WORKSPACE;
     if (((uintptr_t)out & 15) != 0) return PNR_E_ALIGN;
-    if (!mlp->lin_in_w || !mlp->lin_in_b || !mlp->lin_out_w || !mlp->lin_out_b) return PNR_E_NULL;
-    for (int b = 0; b < mlp->n_blocks; ++b) {
-        if (!mlp->fc0_w[b] || !mlp->fc0_b[b] || !mlp->fc1_w[b] || !mlp->fc1_b[b]) return PNR_E_NULL;
-        if (b < y.nb1 && (!mlp->lin_z_w[b] || !mlp->lin_z_b[b])) return PNR_E_NULL;
-    }
+    if (!mlp_pointers_set(mlp, y.nb1)) return PNR_E_NULL;
     if (dtype == PNR_BF16) hipLaunchKernelGGL(k_pack_mlp<PNR_BF16>, dim3(2048), dim3(256), 0, (hipStream_t)stream, *mlp, y, (char*)out, (const float*)nullptr);
     else hipLaunchKernelGGL(k_pack_mlp<PNR_F16>, dim3(2048), dim3(256), 0, (hipStream_t)stream, *mlp, y, (char*)out, (const float*)nullptr);
     PNR_LAUNCH_CHECK();
@@ -1291,5 +1283,15 @@ extern "C" int32_t pnr_pack_latents(const pnr_views* views, int32_t dtype, void*
     if (dtype == PNR_BF16) hipLaunchKernelGGL(k_pack_latents<PNR_BF16>, dim3(1024), dim3(256), 0, (hipStream_t)stream, *views, lp, (char*)out);
     else hipLaunchKernelGGL(k_pack_latents<PNR_F16>, dim3(1024), dim3(256), 0, (hipStream_t)stream, *views, lp, (char*)out);
     PNR_LAUNCH_CHECK();
+    return PNR_OK;
+}
+
+extern "C" int32_t pnr_debug_point_split(int32_t max_wgs, int32_t n_stream_objs, int32_t K, int64_t count, int64_t per_obj,
+                                         int32_t* out4) {
+    if (!out4) return PNR_E_NULL;
+    if (max_wgs < 1 || max_wgs > MAX_GRID || K < 0 || count < 1 || (n_stream_objs > 1 && per_obj < 1)) return PNR_E_SHAPE;
+    PointSplit sp;
+    PNR_TRY(point_split(max_wgs, n_stream_objs, K, count, per_obj, &sp));
+    out4[0] = sp.grid; out4[1] = sp.tiles_per_wg; out4[2] = sp.rays_per_wg; out4[3] = sp.wgs_per_obj;
     return PNR_OK;
 }

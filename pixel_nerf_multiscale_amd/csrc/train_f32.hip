@@ -1797,7 +1797,7 @@ struct Tape {
     // row-contiguous operand k_sgemm_dma wants for the dX products
     float* Wt32[2 * PNR_MAX_BLOCKS];
     float* Wzt32[PNR_MAX_BLOCKS];
-    void* lat_cl;                        // channels-last fp32 copies of the latent maps for the feature build (latent_cl_build)
+    LatCL lat_cl;                        // channels-last fp32 copies of the latent maps for the feature build (latent_cl_build)
 
     // the fp32 residual stream entering block b (b = n_blocks: entering lin_out, read by non-MFMA kernels): its tape slot, or
     // on the 16-bit tape the ping-pong buffer of that block — every block writes the other one
@@ -1826,10 +1826,9 @@ static Tape carve_tape(const pnr_mlp* mlp, const pnr_views* vw, int64_t P, void*
     t.h16 = h16;
     t.H = mlp->d_hidden; t.L = mlp->d_latent; t.E = feature_stride(mlp);
     const int NS = vw->n_views, H = t.H, L = t.L, nz = n_lin_z(mlp);
-    uint8_t* p = (uint8_t*)round_up_256(base);
-    uint64_t off = 0;
-    auto take = [&](uint64_t floats) { float* r = (float*)(p + off); off += round_up_256(floats * 4); return r; };
-    auto take16 = [&](uint64_t halves) { uint16_t* r = (uint16_t*)(p + off); off += round_up_256(halves * 2); return r; };
+    Bump bump(round_up_256(base));      // 256-byte pieces, + 256 for the rounding
+    auto take = [&](uint64_t floats) { return bump.take<float>(floats, 256); };
+    auto take16 = [&](uint64_t halves) { return bump.take<uint16_t>(halves, 256); };
     t.zx = take((uint64_t)NS * P * t.E);
     if (h16) {
         t.xw[0] = take((uint64_t)NS * P * H);
@@ -1849,7 +1848,7 @@ static Tape carve_tape(const pnr_mlp* mlp, const pnr_views* vw, int64_t P, void*
     t.o4 = take((uint64_t)P * 4);
     if (h16 && dma_gemm_ok(mlp))
         for (int i = 0; i < 2 * mlp->n_blocks; ++i) { t.Wb[i] = take16((uint64_t)H * H); t.Wt[i] = take16((uint64_t)H * H); }
-    if (L > 0) { t.lat_cl = (void*)(p + off); off += latent_cl_bytes(*vw); }
+    if (L > 0) { bump.pad(256); t.lat_cl = latent_cl_carve(bump, *vw); }
     if (!h16 && H % 16 == 0) {
         for (int i = 0; i < 2 * mlp->n_blocks; ++i) t.Wt32[i] = take((uint64_t)H * H);
         if (L > 0 && L % 4 == 0)
@@ -1859,7 +1858,8 @@ static Tape carve_tape(const pnr_mlp* mlp, const pnr_views* vw, int64_t P, void*
         t.z16 = take16((uint64_t)NS * P * L);
         for (int b = 0; b < nz; ++b) { t.Wz[b] = take16((uint64_t)H * L); t.Wzt[b] = take16((uint64_t)H * L); }
     }
-    t.total = off + 256;
+    bump.take<uint8_t>(256, 256);
+    t.total = bump.off;
     return t;
 }
 
@@ -1887,17 +1887,10 @@ static uint64_t det_ws_floats(const pnr_mlp* mlp) {
 static size_t latent_grad_lds_bytes(const pnr_views* vw) {
     return (size_t)vw->lat_c[0] * vw->lat_h[0] * vw->lat_w[0] * 4 + (size_t)LATG_PPB * 4 * 8;
 }
-// LDS a block may ask for on this device (gfx950: 160 KiB), cached per device like num_cus() — an immutable property
+// LDS a block may ask for on this device (gfx950: 160 KiB)
 static size_t lds_per_block_limit() {
-    static size_t cached[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 64 * 1024;
-    if (cached[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || n <= 0) n = 64 * 1024;
-        cached[dev] = (size_t)n;
-    }
-    return cached[dev];
+    static PerDevice cache;
+    return (size_t)device_attr(cache, hipDeviceAttributeMaxSharedMemoryPerBlock, 64 * 1024);
 }
 static bool latent_grad_in_lds(const pnr_views* vw) {
     // the real requirement (map + tap table) against what the device grants; maps up to 64 KiB as before
@@ -1918,10 +1911,31 @@ static uint64_t latent_q_bytes(const pnr_views* vw) {
         n += (uint64_t)vw->n_objs * vw->n_views * vw->lat_c[l] * vw->lat_h[l] * vw->lat_w[l];
     return n * 8 + 256;
 }
+// The backward's workspace (256-byte pieces behind a base rounded up to 256, + that slack): the gradient stream and its second
+// buffer, dh (16-bit tape: the two bf16 streams overlay it, see point_bwd), the gradient at the assembled rows, at the head's
+// output, the weight-gradient slices, and the latent gradient's partial maps or fixed-point maps.
+struct TrainBwdWs {
+    float *dx, *dx2, *dh, *dzx, *do4;
+    DetWs dws;
+    float* lat_part;
+    uint8_t* lat_q;        // [scale words (256 B)][fixed-point maps], latent_q_bytes
+};
+static TrainBwdWs carve_train_bwd(Bump& b, const pnr_mlp* mlp, const pnr_views* vw, int64_t P) {
+    const uint64_t MV = (uint64_t)vw->n_views * P, H = mlp->d_hidden, E = feature_stride(mlp);
+    TrainBwdWs w;
+    w.dx = b.take<float>(MV * H, 256);
+    w.dx2 = b.take<float>(MV * H, 256);
+    w.dh = b.take<float>(MV * H, 256);
+    w.dzx = b.take<float>(MV * E, 256);
+    w.do4 = b.take<float>((uint64_t)P * 4, 256);
+    w.dws = DetWs{b.take<float>(det_ws_floats(mlp), 256), det_ws_floats(mlp)};
+    w.lat_part = (float*)b.take<uint8_t>(latent_part_bytes(vw, P), 256);
+    w.lat_q = b.take<uint8_t>(latent_q_bytes(vw), 256);
+    b.take<uint8_t>(256, 256);
+    return w;
+}
 uint64_t train_bwd_workspace_bytes(const pnr_mlp* mlp, const pnr_views* vw, int64_t P) {
-    const uint64_t NS = vw->n_views, H = mlp->d_hidden, E = feature_stride(mlp);
-    return round_up_256(NS * P * H * 4) * 3 + round_up_256(NS * P * E * 4) + round_up_256((uint64_t)P * 16) +
-           round_up_256(det_ws_floats(mlp) * 4) + round_up_256(latent_part_bytes(vw, P)) + round_up_256(latent_q_bytes(vw)) + 256;
+    return bytes_of([&](Bump& b) { carve_train_bwd(b, mlp, vw, P); });
 }
 
 static inline int vec_flags(const float* A, int lda, const float* B, int ldb) {
@@ -2335,7 +2349,7 @@ int32_t point_train_fwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_vie
     const int half = prm->precision == PNR_BF16 ? 1 : prm->precision == PNR_BF16X3 ? 3 : 0;
     const int tape_mode = t.h16 ? (int)PNR_DBG_MODE_TAPE16 : half;
     PNR_TRY(features_launch(*vw, src, 0, (int)P, pts_per_obj, L, Din, prm->use_code_viewdirs, prm->num_freqs, prm->freq_factor, t.zx, E, s,
-                            (t.lat_cl && P >= 4096) ? latent_cl_build(*vw, t.lat_cl, s) : LatCL{}));
+                            (t.lat_cl.p[0] && P >= 4096) ? latent_cl_build(*vw, t.lat_cl, s) : LatCL{}));
     PNR_LAUNCH_CHECK();
     if (t.Wb[0]) {      // bf16 copies of the hidden weights (as stored + transposed) for the LDS-DMA GEMMs of forward and backward
         PNR_TRY(weight_copies<W16Table>(k_w_to_bf16, mlp, t.z16 ? nz : 0, [&](W16Table& tb, int e, int i, bool lin_z) {
@@ -2404,7 +2418,9 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
                   const pnr_mlp_grads* gr, float* const* d_latent, float* d_xyz, float* d_z, void* workspace,
                   uint64_t ws_bytes, hipStream_t s, const CamGradOut* cam /* camera gradients (cam_grad.hip), or null */) {
     if (tape_bytes < train_tape_bytes_p(prm, mlp, vw, P)) return PNR_E_WORKSPACE;
-    if (ws_bytes < train_bwd_workspace_bytes(mlp, vw, P)) return PNR_E_WORKSPACE;
+    Bump bump(round_up_256(workspace));
+    const TrainBwdWs w = carve_train_bwd(bump, mlp, vw, P);
+    if (ws_bytes < bump.off) return PNR_E_WORKSPACE;
     const int NS = vw->n_views, L = mlp->d_latent, Din = mlp->d_in, H = mlp->d_hidden, E = feature_stride(mlp);
     const int nb = mlp->n_blocks, cl = mlp->combine_layer, nz = n_lin_z(mlp);
     if (NS > 1 && cl >= nb) return PNR_E_UNSUPPORTED;
@@ -2412,15 +2428,9 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
     const int64_t MV = (int64_t)NS * P;
     const int half = prm->precision == PNR_BF16 ? 1 : prm->precision == PNR_BF16X3 ? 3 : 0;
     const int tape_mode = t.h16 ? (int)PNR_DBG_MODE_TAPE16 : half;
-    uint8_t* wp = (uint8_t*)round_up_256(workspace);
-    float* dx = (float*)wp;                wp += round_up_256((uint64_t)MV * H * 4);
-    float* dx2 = (float*)wp;               wp += round_up_256((uint64_t)MV * H * 4);
-    float* dh = (float*)wp;                wp += round_up_256((uint64_t)MV * H * 4);
-    float* dzx = (float*)wp;               wp += round_up_256((uint64_t)MV * E * 4);
-    float* do4 = (float*)wp;               wp += round_up_256((uint64_t)P * 16);
-    const DetWs dws{(float*)wp, det_ws_floats(mlp)};  wp += round_up_256(det_ws_floats(mlp) * 4);
-    float* lat_part = (float*)wp;          wp += round_up_256(latent_part_bytes(vw, P));
-    uint8_t* lat_q = wp;                   // [scale words (256 B)][fixed-point maps], latent_q_bytes
+    float *dx = w.dx, *dx2 = w.dx2, *dh = w.dh, *dzx = w.dzx, *do4 = w.do4, *lat_part = w.lat_part;
+    const DetWs dws = w.dws;
+    uint8_t* lat_q = w.lat_q;
     const bool want_p = d_xyz || d_z;
     const bool want_code = want_p || cam;      // the gradient at the code columns of dzx
     bool want_lat = false;
@@ -2493,13 +2503,12 @@ int32_t point_bwd(const pnr_params* prm, const pnr_mlp* mlp, const pnr_views* vw
         const size_t lds = latent_grad_lds_bytes(vw);
         const int nbx = (int)((pts_per_obj + LATG_PPB - 1) / LATG_PPB);
         if (lds > 48 * 1024) {          // only above the default limit, and once per device (the attribute sticks to the function)
-            static bool raised[64] = {false};
-            int dev = 0;
-            PNR_HIP_CHECK(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 64 || !raised[dev]) {
+            static PerDevice raised;
+            int* done = raised.slot();
+            if (!done || !*done) {
                 PNR_HIP_CHECK(hipFuncSetAttribute((const void*)k_latent_grad_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                   (int)lds_per_block_limit()));
-                if (dev >= 0 && dev < 64) raised[dev] = true;
+                if (done) *done = 1;
             }
         }
         hipLaunchKernelGGL(k_latent_grad_lds, dim3(nbx, views), dim3(256), lds, s, *vw, src, P, pts_per_obj, L, dzx, E, lat_part);

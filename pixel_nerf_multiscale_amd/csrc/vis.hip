@@ -225,9 +225,17 @@ __global__ void __launch_bounds__(FRAME_THREADS) k_vis_write(VisArgs a) {
 
 using namespace pnr;
 
+// pnr_cmap's workspace: the fold's record | (min, max) partials of every tile
+struct CmapWs { float* record; float* part; };
+static CmapWs carve_cmap(Bump& b, int W, int H) {
+    CmapWs w;
+    w.record = b.take<float>(VS_RECORD_BYTES / sizeof(float));
+    w.part = b.take<float>((uint64_t)frame_tiles(W, H) * 2);
+    return w;
+}
 extern "C" uint64_t pnr_cmap_workspace_bytes(int32_t W, int32_t H) {
     if (!frame_shape_ok(W, H)) return 0;
-    return VS_RECORD_BYTES + (uint64_t)frame_tiles(W, H) * 2 * sizeof(float);
+    return bytes_of([&](Bump& b) { carve_cmap(b, W, H); });
 }
 
 extern "C" int32_t pnr_cmap(const float* map, int32_t stride, int32_t W, int32_t H, const uint8_t* lut, uint8_t* out_u8,
@@ -237,10 +245,11 @@ extern "C" int32_t pnr_cmap(const float* map, int32_t stride, int32_t W, int32_t
     if (!frame_shape_ok(W, H)) return PNR_E_SHAPE;
     if (stride == 0) stride = 1;
     if (stride < 1) return PNR_E_SHAPE;
-    if (workspace_bytes < pnr_cmap_workspace_bytes(W, H)) return PNR_E_WORKSPACE;
+    Bump bump(workspace);
+    const CmapWs ws = carve_cmap(bump, W, H);
+    if (workspace_bytes < bump.off) return PNR_E_WORKSPACE;
     const int tiles = (int)frame_tiles(W, H), tiles_x = frame_tiles_x(W);
-    float* record = (float*)workspace;
-    float* part = (float*)((char*)workspace + VS_RECORD_BYTES);
+    float *record = ws.record, *part = ws.part;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_cmap_reduce, dim3((unsigned)tiles), dim3(FRAME_THREADS), 0, s, map, stride, W, H, tiles_x, part);
     PNR_LAUNCH_CHECK();
@@ -253,11 +262,19 @@ extern "C" int32_t pnr_cmap(const float* map, int32_t stride, int32_t W, int32_t
 }
 
 // workspace: record (64 bytes) | squared-error partials (tiles doubles) | extrema partials (n_pass, tiles, 6) | alpha (n_pass, H W)
+struct VisWs { float* record; double* se_part; float* mm_part; float* alpha; };
+static VisWs carve_vis(Bump& b, int W, int H, int n_pass) {
+    const uint64_t tiles = (uint64_t)frame_tiles(W, H);
+    VisWs w;
+    w.record = b.take<float>(VS_RECORD_BYTES / sizeof(float));
+    w.se_part = b.take<double>(tiles);
+    w.mm_part = b.take<float>((uint64_t)n_pass * tiles * 6);
+    w.alpha = b.take<float>((uint64_t)n_pass * (uint64_t)W * (uint64_t)H);
+    return w;
+}
 extern "C" uint64_t pnr_vis_panel_workspace_bytes(int32_t W, int32_t H, int32_t n_pass) {
     if (!frame_shape_ok(W, H) || n_pass < 1 || n_pass > 2) return 0;
-    const uint64_t tiles = (uint64_t)frame_tiles(W, H);
-    return VS_RECORD_BYTES + tiles * sizeof(double) + (uint64_t)n_pass * tiles * 6 * sizeof(float) +
-           (uint64_t)n_pass * (uint64_t)W * (uint64_t)H * sizeof(float);
+    return bytes_of([&](Bump& b) { carve_vis(b, W, H, n_pass); });
 }
 
 extern "C" int32_t pnr_vis_panel(const float* images, int32_t NV, const int32_t* src_views, int32_t NS, int32_t gt_view,
@@ -288,18 +305,16 @@ extern "C" int32_t pnr_vis_panel(const float* images, int32_t NV, const int32_t*
     }
     if (n_pass == 1) a.pass[1] = a.pass[0];
     if (!any) return PNR_OK;
-    if (workspace_bytes < pnr_vis_panel_workspace_bytes(W, H, n_pass)) return PNR_E_WORKSPACE;
+    Bump bump(workspace);
+    const VisWs ws = carve_vis(bump, W, H, n_pass);
+    if (workspace_bytes < bump.off) return PNR_E_WORKSPACE;
     const int64_t tiles = frame_tiles(W, H);
     a.images = images;
     for (int i = 0; i < PNR_VIS_MAX_SRC; ++i) a.src[i] = i < NS ? src_views[i] : 0;
     a.NS = NS; a.gt_view = gt_view; a.n_pass = n_pass; a.W = W; a.H = H;
     a.tiles_x = frame_tiles_x(W); a.tiles = (int)tiles;
     a.lut = lut; a.panel_f32 = panel_f32; a.panel_u8 = panel_u8; a.alpha_out = alpha; a.stats = stats; a.mse = mse;
-    char* ws = (char*)workspace;
-    a.record = (float*)ws;
-    a.se_part = (double*)(ws + VS_RECORD_BYTES);
-    a.mm_part = (float*)(ws + VS_RECORD_BYTES + (uint64_t)tiles * sizeof(double));
-    a.alpha_ws = a.mm_part + (int64_t)n_pass * tiles * 6;
+    a.record = ws.record; a.se_part = ws.se_part; a.mm_part = ws.mm_part; a.alpha_ws = ws.alpha;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_vis_reduce, dim3((unsigned)tiles), dim3(FRAME_THREADS), 0, s, a);
     PNR_LAUNCH_CHECK();

@@ -17,17 +17,6 @@ _memo = {}
 
 
 # ----------------------------------------------------------------------------- the C ABI
-def test_new_exports_and_argtypes():
-    from pixel_nerf_multiscale_amd import _native as N
-    res, args = N.PROTOTYPES["pnr_point_mlp_bwd_cam"]
-    old = N.PROTOTYPES["pnr_point_mlp_bwd"][1]
-    assert res is C.c_int32 and args[:18] == old[:18] and args[18:21] == [C.c_void_p] * 3 and args[21:] == old[18:]
-    assert N.PROTOTYPES["pnr_train_bwd_cam_workspace_bytes"] == (
-        C.c_uint64, N.PROTOTYPES["pnr_train_bwd_workspace_bytes"][1] + [C.c_int32, C.c_int32])
-    assert N.lib._cdll.pnr_point_mlp_bwd_cam.argtypes == args
-    assert N.lib.pnr_version() == 102
-
-
 def _structs(SB=1, NS=1):
     """Descriptors that pass the argument checks, over addresses nothing dereferences before the checks are through."""
     from pixel_nerf_multiscale_amd import _native as N

@@ -16,14 +16,56 @@ import golden_util as gu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_exports_every_declared_symbol():
-    from pixel_nerf_multiscale_amd import _native as N
+def _header_declarations():
+    """(name, return kind, [parameter kinds]) of every function include/pnr.h declares, comments stripped.  Kinds: "pointer",
+    "int32_t", "int64_t", "uint64_t", "float", "double" (and "void" for a return)."""
     hdr = open(os.path.join(ROOT, "include", "pnr.h")).read()
-    declared = set(re.findall(r"\b(pnr_[a-z0-9_]+)\s*\(", hdr))
-    assert declared, "no prototypes parsed"
-    assert declared == set(N.PROTOTYPES), declared ^ set(N.PROTOTYPES)
-    for name in declared:
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    hdr = re.sub(r"^\s*#.*$", " ", hdr, flags=re.M)
+
+    def kind(decl):
+        decl = decl.strip()
+        if "*" in decl or "[" in decl:
+            return "pointer"
+        words = [w for w in decl.split() if w not in ("const", "unsigned", "signed")]
+        base = next((w for w in words if w in ("int32_t", "int64_t", "uint64_t", "float", "double", "void", "int")), None)
+        assert base is not None, decl
+        return "int32_t" if base == "int" else base
+
+    out = []
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(pnr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr):
+        params = params.strip()
+        out.append((name, kind(ret), [] if params in ("", "void") else [kind(q) for q in params.split(",")]))
+    return out
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or hasattr(t, "contents"):          # POINTER(...) types carry `contents`
+        return "pointer"
+    return {ctypes.c_int32: "int32_t", ctypes.c_int64: "int64_t", ctypes.c_uint64: "uint64_t", ctypes.c_float: "float",
+            ctypes.c_double: "double"}[t]
+
+
+def test_library_exports_every_declared_symbol():
+    """Every function of include/pnr.h has a prototype in _native.PROTOTYPES and the other way round, with the header's return
+    type and the kind of every parameter, and the loaded library's functions carry exactly those."""
+    from pixel_nerf_multiscale_amd import _native as N
+    decls = _header_declarations()
+    declared = [d[0] for d in decls]
+    assert declared and len(declared) == len(set(declared)), "no prototypes parsed, or one parsed twice"
+    assert set(declared) == set(N.PROTOTYPES), set(declared) ^ set(N.PROTOTYPES)
+    wrong = []
+    for name, ret, params in decls:
+        res, args = N.PROTOTYPES[name]
+        if (_ctypes_kind(res), [_ctypes_kind(a) for a in args]) != (ret, params):
+            wrong.append((name, ret, params, _ctypes_kind(res), [_ctypes_kind(a) for a in args]))
         assert hasattr(N.lib, name), name
+        fn = getattr(N.lib._cdll, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    assert not wrong, wrong
     assert N.lib.pnr_version() == 102
     assert N.lib.pnr_error_string(-4).decode() == "workspace too small"
 
@@ -438,3 +480,217 @@ def test_dptr_takes_any_dtype_on_the_device_only():
     with pytest.raises(RuntimeError):
         N.dptr(N.scratch(8, "cpu"))
     assert N.scratch(0, "cpu").numel() == 16 and N.scratch(100, "cpu").numel() == 100 and N.scratch(1, "cpu").dtype == torch.uint8
+
+
+# ----------------------------------------------------------------------------- the C host layer: layouts, checks, the work split
+def _size_mlp(N, L, H=512, cl=3):
+    return N.pnr_mlp(d_in=42, d_latent=L, d_hidden=H, d_out=4, n_blocks=5, combine_layer=cl)
+
+
+def _size_views(N, L, SB=1, NS=1):
+    vw = N.pnr_views(n_objs=SB, n_views=NS, n_levels=1)
+    vw.lat_c[0], vw.lat_h[0], vw.lat_w[0] = L, 8, 8
+    return vw
+
+
+def _host_sizes():
+    """(what, bytes) of every size function whose layout is carved by one function (csrc/pnr_common.h Bump), in a fixed order.
+    The training maps are (L, 8, 8) with L = 100 (25 KiB: the latent gradient's LDS route on any device, and without one) and
+    L = 512 (128 KiB: the fixed-point route on any device)."""
+    import ctypes as C
+    from pixel_nerf_multiscale_amd import _native as N
+    lib, r = N.lib, C.byref
+    for prec in (N.PNR_F32, N.PNR_F16):
+        prm = N.pnr_params(n_coarse=64, n_fine=32, precision=prec)
+        for NS in (1, 3):
+            vw = _size_views(N, 512, 1, NS)
+            for L in (512, 1024):                       # the coarse MLP, and a fine MLP of larger d_latent
+                for n in (0, 1, 4096):
+                    yield ("workspace", prec, NS, L, n), lib.pnr_workspace_bytes(r(prm), r(_size_mlp(N, L)), r(vw), n)
+    for L in (100, 512):
+        for SB in (1, 2):
+            for NS in (1, 3):
+                mlp, vw = _size_mlp(N, L), _size_views(N, L, SB, NS)
+                for P in (0, 1, 4096):
+                    yield ("train_bwd", L, SB, NS, P), lib.pnr_train_bwd_workspace_bytes(r(mlp), r(vw), P)
+                    for wp, wc in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                        yield ("train_bwd_cam", L, SB, NS, P, wp, wc), lib.pnr_train_bwd_cam_workspace_bytes(r(mlp), r(vw), P, wp, wc)
+    for L, H in ((0, 64), (512, 512), (100, 120)):
+        for NS in (1, 2):
+            yield ("resnetfc", L, H, NS), lib.pnr_resnetfc_workspace_bytes(r(_size_mlp(N, L, H)), NS)
+    for g in ((1, 1, 1), (16, 16, 16), (17, 16, 15)):
+        yield ("mc",) + g, lib.pnr_mc_workspace_bytes(*g)
+    for W, H in ((16, 16), (17, 16), (1, 1)):
+        yield ("cmap", W, H), lib.pnr_cmap_workspace_bytes(W, H)
+        for n_pass in (1, 2):
+            yield ("vis_panel", W, H, n_pass), lib.pnr_vis_panel_workspace_bytes(W, H, n_pass)
+    for n in (0, 1, 3, 4):
+        yield ("optim", n), lib.pnr_optim_workspace_bytes(n)
+    for W, H in ((7, 7), (16, 17)):
+        yield ("eval_frame", W, H), lib.pnr_eval_frame_workspace_bytes(W, H)
+        for F in (1, 3):
+            yield ("eval_frames", F, W, H), lib.pnr_eval_frames_workspace_bytes(F, W, H)
+            yield ("eval_frames_u8", F, W, H), lib.pnr_eval_frames_u8_workspace_bytes(F, W, H)
+
+
+# _host_sizes() in its order, recorded from the library before the layouts moved onto one allocator
+_HOST_SIZES = (
+    311558912, 311562496, 322241280, 412222208, 412225792, 422904576, 933102336, 933105920, 943784704, 1235092224,
+    1235095808, 1245774592, 67109376, 67112960, 77791744, 134218240, 134221824, 144900608, 335544832, 335548416,
+    346227200, 402653696, 402657280, 413336064, 67240192, 67240192, 67240448, 67240448, 67240448, 67272960, 67272960,
+    67273728, 67273472, 67273984, 95240448, 95240448, 95503360, 95339008, 95601664, 67240192, 67240192, 67240448,
+    67240448, 67240448, 67337472, 67337472, 67338496, 67337984, 67338752, 151109888, 151109888, 151898112, 151208448,
+    151996416, 67240192, 67240192, 67240448, 67240448, 67240448, 67247360, 67247360, 67247872, 67247872, 67248128,
+    95240448, 95240448, 95503360, 95339008, 95601664, 67240192, 67240192, 67240448, 67240448, 67240448, 67260672,
+    67260672, 67261184, 67261184, 67261440, 151109888, 151109888, 151898112, 151208448, 151996416, 67502592, 67502592,
+    67502848, 67502848, 67502848, 67511296, 67511296, 67512064, 67511808, 67512320, 101843456, 101843456, 102106368,
+    101942016, 102204672, 68026880, 68026880, 68027136, 68027136, 68027136, 68052480, 68052480, 68053504, 68052992,
+    68053760, 170918400, 170918400, 171706624, 171016960, 171804928, 67764736, 67764736, 67764992, 67764992, 67764992,
+    67773440, 67773440, 67773952, 67773952, 67774208, 102105600, 102105600, 102368512, 102204160, 102466816, 68813312,
+    68813312, 68813568, 68813568, 68813568, 68838912, 68838912, 68839424, 68839424, 68839680, 171704832, 171704832,
+    172493056, 171803392, 172591360, 33423616, 66846976, 310247680, 620495104, 75104512, 150208768, 0, 49152, 49152, 72,
+    1120, 2168, 80, 1216, 2352, 72, 100, 128, 0, 32, 48, 48, 16, 16, 16, 48, 48, 32, 32, 32, 96, 96,
+)
+
+
+def test_workspace_sizes_are_pinned():
+    got = list(_host_sizes())
+    assert len(got) == len(_HOST_SIZES)
+    wrong = [(what, v, want) for (what, v), want in zip(got, _HOST_SIZES) if v != want]
+    assert not wrong, wrong[:8]
+
+
+def _mlp_check_codes():
+    """Return codes of the entry points that check an MLP's pointers, for an MLP with fc1_b[2] NULL, one with lin_z_w[0] NULL, one
+    with lin_z_w[0] NULL and d_out = 3, one with lin_in_w NULL and d_out = 3 — and the whole one, which every call here stops
+    behind its MLP checks by another argument (a misaligned output, no rows, a blob of no bytes), so that nothing is launched."""
+    import ctypes as C
+    from pixel_nerf_multiscale_amd import _native as N
+    lib, r, p = N.lib, C.byref, 0x10000
+
+    def model(broken):
+        prm = N.pnr_params(num_freqs=6, freq_factor=1.5, precision=N.PNR_F32)
+        m = _size_mlp(N, 256)
+        m.lin_in_w = m.lin_in_b = m.lin_out_w = m.lin_out_b = p
+        for b in range(5):
+            for f in ("fc0_w", "fc0_b", "fc1_w", "fc1_b", "lin_z_w", "lin_z_b"):
+                getattr(m, f)[b] = p
+        v = _size_views(N, 256)
+        v.n_focal = v.n_c = 1
+        v.w2c = v.focal = v.c = v.latent[0] = p
+        if broken == "fc1_b[2]":
+            m.fc1_b[2] = None
+        if broken in ("lin_z_w[0]", "lin_z_w[0] + d_out"):
+            m.lin_z_w[0] = None
+        if broken == "lin_in_w + d_out":
+            m.lin_in_w = None
+        if broken.endswith("d_out"):
+            m.d_out = 3
+        return prm, m, v
+
+    for broken in ("fc1_b[2]", "lin_z_w[0]", "lin_z_w[0] + d_out", "lin_in_w + d_out", "whole"):
+        prm, m, v = model(broken)
+        whole = broken == "whole"
+        g = N.pnr_mlp_grads()
+        pts = (None, None, 0, p, p, 8, 8)                    # explicit points
+        yield (broken, "pnr_point_mlp"), lib.pnr_point_mlp(r(prm), r(m), r(v), *pts, p + 4, p, 1 << 40, None)
+        yield (broken, "pnr_resnetfc_forward"), lib.pnr_resnetfc_forward(r(m), p, 0, 1, 8, p, p, 1 << 40, None)
+        yield (broken, "pnr_pack_mlp"), lib.pnr_pack_mlp(r(m), N.PNR_BF16, p, 0 if whole else 1 << 40, None)
+        yield (broken, "pnr_pack_mlp_projected"), lib.pnr_pack_mlp_projected(r(m), r(v), N.PNR_BF16, p, 0 if whole else 1 << 40, None)
+        yield (broken, "pnr_point_mlp_train_fwd"), lib.pnr_point_mlp_train_fwd(r(prm), r(m), r(v), *pts, p + 4, p, 1 << 40, None)
+        bwd = (r(prm), r(m), r(v), *pts, p + 4, p, p, 1 << 40, r(g), None, None, None)
+        yield (broken, "pnr_point_mlp_bwd"), lib.pnr_point_mlp_bwd(*bwd, p, 1 << 40, None)
+        yield (broken, "pnr_point_mlp_bwd_cam"), lib.pnr_point_mlp_bwd_cam(*bwd, None, None, None, p, 1 << 40, None)
+
+
+# _mlp_check_codes() in its order, recorded from the library before the four checks became one
+_MLP_CHECK_CODES = (
+    -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -2, -1, -3, -3, -2, -2, -2, -1, -1, -3, -3, -1, -1, -1, -5,
+    0, -4, -4, -5, -5, -5,
+)
+
+
+def test_mlp_pointer_checks_keep_their_codes_and_order():
+    got = list(_mlp_check_codes())
+    assert len(got) == len(_MLP_CHECK_CODES) == 35
+    wrong = [(what, v, want) for (what, v), want in zip(got, _MLP_CHECK_CODES) if v != want]
+    assert not wrong, wrong
+
+
+_TILE_PTS, _MAX_GRID, _E_SHAPE, _E_UNSUPPORTED = 128, 512, -2, -3
+
+
+def _split_reference(grid, n_objs, proj, fused, K, n_points, pts_per_obj):
+    """The four branches of the fused launch's work split as point_mfma() spelled them out before point_split: returns
+    (grid, tiles_per_wg, rays_per_wg, wgs_per_obj) or an error code."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    tiles_per_wg = rays_per_wg = wgs_per_obj = 0
+    n_rays = n_points // K if fused else 0
+    if proj and n_objs > 1:
+        wpo = max(grid // n_objs, 1)
+        if wpo * n_objs > _MAX_GRID:
+            return _E_UNSUPPORTED
+        if fused:
+            rays_per_obj = pts_per_obj // K
+            rpw = max(cdiv(rays_per_obj, wpo), cdiv(_TILE_PTS, K))
+            if rpw * K >= 0x7fffffff:
+                return _E_SHAPE
+            rays_per_wg = rpw
+            wpo = cdiv(rays_per_obj, rpw)
+        else:
+            tiles_obj = cdiv(pts_per_obj, _TILE_PTS)
+            tpw = cdiv(tiles_obj, wpo)
+            if tpw * _TILE_PTS >= 0x7fffffff:
+                return _E_SHAPE
+            tiles_per_wg = tpw
+            wpo = cdiv(tiles_obj, tpw)
+        wgs_per_obj = wpo
+        grid = wpo * n_objs
+    elif fused:
+        rpw = max(cdiv(n_rays, grid), cdiv(_TILE_PTS, K))
+        if rpw * K >= 0x7fffffff:
+            return _E_SHAPE
+        rays_per_wg = rpw
+        grid = cdiv(n_rays, rpw)
+    else:
+        n_tiles = cdiv(n_points, _TILE_PTS)
+        tpw = cdiv(n_tiles, grid)
+        if tpw * _TILE_PTS >= 0x7fffffff:
+            return _E_SHAPE
+        tiles_per_wg = tpw
+        grid = cdiv(n_tiles, tpw)
+    return (grid, tiles_per_wg, rays_per_wg, wgs_per_obj)
+
+
+def test_point_split_is_the_four_branches_it_replaced():
+    """pnr_debug_point_split (csrc/point_mfma.hip point_split) against the branches restated above: every cap, plain launches
+    round the tile size and the int32 limit, fused launches round the ray counts at which a workgroup's share changes, and the
+    same per object for 2, 3 and 16 objects with projected streams."""
+    import ctypes as C
+    from pixel_nerf_multiscale_amd import _native as N
+    out = (C.c_int32 * 4)()
+
+    def split(cap, objs, K, count, per_obj):
+        rc = N.lib.pnr_debug_point_split(cap, objs, K, count, per_obj, out)
+        return tuple(out) if rc == 0 else rc
+
+    n_checked = n_refused = 0
+    for cap in (1, 8, 256, 512):
+        for objs in (1, 2, 3, 16):
+            proj = objs > 1
+            for n in (1, 127, 128, 129, 65536, 65537, 1 << 33):                 # points (per object); 2^33: past int32 on one workgroup
+                want = _split_reference(cap, objs, proj, False, 0, n * objs, n)
+                assert split(cap, objs, 0, n * objs, n) == want, (cap, objs, n, want)
+                n_refused += want == _E_SHAPE
+                n_checked += 1
+            for K in (1, 16, 96, 128, 129):
+                for rays in (1, 511, 512, 513, 16384):                         # rays (per object)
+                    want = _split_reference(cap, objs, proj, True, K, rays * objs * K, rays * K)
+                    assert split(cap, objs, K, rays * objs, rays) == want, (cap, objs, K, rays, want)
+                    n_checked += 1
+    assert n_checked == 4 * 4 * (7 + 25) and n_refused > 0
+    # without projected streams several objects share the workgroups: the object count does not enter
+    assert split(256, 1, 96, 16384, 4096) == _split_reference(256, 4, False, True, 96, 16384 * 96, 4096 * 96)
+    assert split(256, 4, 96, 16384, 4096) == _split_reference(256, 4, True, True, 96, 16384 * 96, 4096 * 96) != split(256, 1, 96, 16384, 4096)
+    assert N.lib.pnr_debug_point_split(256, 1, 0, 4096, 4096, None) == -1
+    assert N.lib.pnr_debug_point_split(0, 1, 0, 4096, 4096, out) == -2 and N.lib.pnr_debug_point_split(256, 1, 0, 0, 0, out) == -2
