@@ -34,7 +34,9 @@ extern "C" {
                                   * pnr_eval_frames_u8_workspace_bytes; the camera gradients, pnr_point_mlp_bwd_cam /
                                   * pnr_train_bwd_cam_workspace_bytes; the data layer's 8-bit batches, pnr_train_batch_u8 /
                                   * pnr_views_to_tensor_u8; the training draws, pnr_train_draw; the fused launch's work split as a
-                                  * host diagnostic, pnr_debug_point_split */
+                                  * host diagnostic, pnr_debug_point_split; the colour-jitter augmentation of 8-bit batches,
+                                  * pnr_color_jitter_workspace_bytes / pnr_color_jitter_plan / pnr_train_batch_u8_jitter /
+                                  * pnr_views_to_tensor_u8_jitter */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -620,6 +622,66 @@ int32_t pnr_train_batch_u8(const uint8_t* images_u8 /* (SB, NV, H, W, C), any by
 int32_t pnr_views_to_tensor_u8(const uint8_t* images_u8 /* (SB, NV, H, W, C), any byte alignment */,
                                const int64_t* view_ord /* (SB, NS), device */, int32_t SB, int32_t NV, int32_t NS, int32_t W,
                                int32_t H, int32_t C, int32_t balanced, float* out /* (SB, NS, 3, H, W) */, void* stream);
+
+/* ---- colour jitter of 8-bit batches, csrc/jitter.hip ----------------------------------------------------------------------------
+ * Upstream pixelNeRF trains DTU under ColorJitterDataset: ONE brightness / contrast / saturation / hue draw per object, applied
+ * on the host to every float view.  Here the draw is a record on the device and the two gathers above apply it to what a step
+ * uses only — the sampled pixels and the chosen source views.  PARITY UNPINNED: the chain is torchvision's tensor arithmetic for
+ * float images in [0, 1] as remembered; torchvision is not importable where this library is developed, so this text is the
+ * specification.
+ *
+ * pnr_color_jitter_plan writes record_out[o] = [brightness, contrast, saturation, hue, mean, order code as a float 0..23, 0, 0].
+ *   Draws: philox4x32 in the samplers' counter layout (key = seed, counter = (lo32(o), hi32(o), draw id 10, block)); ids 0..3, 8
+ *   and 9 are taken, 4..7 are left free for the render path.  Block 0 gives one word each for brightness, contrast, saturation
+ *   and hue, word 0 of block 1 the order code.  u = float(word >> 8) * 2^-24;  factor = lo + (hi - lo) * u with lo, hi =
+ *   1 -+ range (hue: -+ range) in fp32, the difference, the product and the sum each rounded on their own.  Order: q =
+ *   mulhi(word, 24), a Lehmer code over [brightness, contrast, saturation, hue]: q / 6, then (q % 6) / 2, then q % 2, each picking
+ *   from what is left; the last operation is the one left over.
+ *   mean: computed iff the object's contrast factor is not exactly 1 (else 0).  m = the mean over ALL NV * H * W pixels of the
+ *   object of gray(T<(x)), x = float(b) / 255.0f per channel, T< the chain of the operations that precede contrast in the
+ *   record's order.  One value per object, not per view: an object's views share ONE colour map, so source and target views stay
+ *   photo-consistent.  The fp32 greys are summed in fp64 in a fixed order — per workgroup the partial of a block of
+ *   PNR_JITTER_BLOCK consecutive pixels, then one fold per object — divided by the count in fp64 and rounded once to fp32.  No
+ *   atomics: the same bytes give the same bits; one object's bytes do not enter another's record.  With ranges[1] == 0 no
+ *   reduction is launched and neither images_u8 nor workspace is looked at.
+ *   ranges: HOST array of 4 (brightness, contrast, saturation, hue).  workspace: pnr_color_jitter_workspace_bytes(SB, NV, W, H)
+ *   bytes, 8-byte aligned (0 bytes for sizes the plan refuses).
+ *   PNR_E_NULL       ranges or record_out NULL; images_u8 or workspace NULL with ranges[1] != 0
+ *   PNR_E_SHAPE      a brightness, contrast or saturation range outside [0, 1], a hue range outside [0, 0.5], C not 3 or 4, or
+ *                    the size conditions of pnr_train_batch_u8 (SB, NV, W, H < 1, NV * H * W >= 2^31); more blocks than one launch
+ *   PNR_E_ALIGN      workspace not 8-byte aligned;  PNR_E_WORKSPACE  ws_bytes too small
+ *
+ * The chain, y = chain(x) on one pixel x = (r, g, b) in [0, 1].  Every fp32 operation is rounded on its own; clamp is to [0, 1];
+ * the operations run in the record's order; an operation whose factor is exactly its identity (1, 1, 1, hue 0) is skipped, so an
+ * identity record gives the bits of the entry points without a record.
+ *   gray(x)        (0.2989f r + 0.587f g) + 0.114f b
+ *   brightness f   clamp(f x)
+ *   contrast f     clamp(f x + (1 - f) m), m the record's mean, 1 - f rounded once
+ *   saturation f   clamp(f x + (1 - f) gray(x))
+ *   hue h          RGB -> HSV: maxc, minc, eq = (maxc == minc); s = (maxc - minc) / (eq ? 1 : maxc); d = eq ? 1 : maxc - minc;
+ *                  rc = (maxc - r) / d, gc and bc alike; H = [maxc == r] (bc - gc) + [maxc == g and maxc != r] ((2 + rc) - bc) +
+ *                  [maxc != g and maxc != r] ((4 + gc) - rc); H = fmod(H / 6 + 1, 1); v = maxc.
+ *                  shift: t = H + h; H' = t - floor(t); a result of 1.0f becomes 0.0f.
+ *                  HSV -> RGB: i = floor(6 H'), f = 6 H' - i, i mod 6; p = clamp(v (1 - s)), q = clamp(v (1 - s f)),
+ *                  t = clamp(v (1 - s (1 - f))); (r, g, b) = (v,t,p), (q,v,p), (p,v,t), (p,q,v), (t,p,v), (v,p,q) for i = 0..5.
+ *
+ * pnr_train_batch_u8_jitter / pnr_views_to_tensor_u8_jitter: pnr_train_batch_u8 / pnr_views_to_tensor_u8 with the record
+ * `jitter` (SB, 8) (one kernel body each, the chain compiled in).  Per selected pixel x = float(b) / 255.0f, y = chain(x) under
+ * the pixel's object's record, then the existing map on y: balanced (y - 0.5f) / 0.5f, and 0.5f T + 0.5f for rgb_gt.  Rays, NaN
+ * rows and planes for bad indices, checks and return codes are those of the entry points without a record; PNR_E_NULL also for
+ * jitter NULL.  The record is device data and is never read on the host: the chain indexes no memory, so any record is safe. */
+#define PNR_JITTER_BLOCK 4096    /* pixels per partial sum of pnr_color_jitter_plan's mean */
+uint64_t pnr_color_jitter_workspace_bytes(int32_t SB, int32_t NV, int32_t W, int32_t H);
+int32_t pnr_color_jitter_plan(const uint8_t* images_u8 /* (SB, NV, H, W, C), any byte alignment */, int32_t SB, int32_t NV, int32_t W,
+                              int32_t H, int32_t C, const float* ranges /* HOST, 4 */, uint64_t seed,
+                              float* record_out /* (SB, 8) */, void* workspace, uint64_t ws_bytes, void* stream);
+int32_t pnr_train_batch_u8_jitter(const uint8_t* images_u8, const float* poses, const float* focal, const float* c, int32_t SB,
+                                  int32_t NV, int32_t W, int32_t H, float z_near, float z_far, const int64_t* pix_inds, int64_t B,
+                                  float* rays_out, float* rgb_gt_out, int32_t C, int32_t balanced,
+                                  const float* jitter /* (SB, 8) */, void* stream);
+int32_t pnr_views_to_tensor_u8_jitter(const uint8_t* images_u8, const int64_t* view_ord, int32_t SB, int32_t NV, int32_t NS,
+                                      int32_t W, int32_t H, int32_t C, int32_t balanced, float* out,
+                                      const float* jitter /* (SB, 8) */, void* stream);
 
 /* ---- training draws on the device, csrc/train_draw.hip ---------------------------------------------------------------------------
  * pnr_train_draw: the pixels a training step samples and the source views it encodes (train/train.py:268-300: per object

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("PNR_LIB") or os.path.join(HERE, "lib", "libpnr_hip.so
 PNR_MAX_LEVELS = 5
 PNR_MAX_BLOCKS = 8
 PNR_VIS_MAX_SRC = 8
+PNR_JITTER_BLOCK = 4096
 PNR_F32, PNR_BF16, PNR_F16 = 0, 1, 2
 PNR_BF16X3 = 3     # training entry points only
 PRECISIONS = {"fp32": PNR_F32, "f32": PNR_F32, "bf16": PNR_BF16, "fp16": PNR_F16, "f16": PNR_F16, "bf16x3": PNR_BF16X3}
@@ -173,6 +174,11 @@ PROTOTYPES = {
     "pnr_image_to_tensor": (_i32, [_fp, _i32, _i32, _i32, _fp, _fp]),
     "pnr_train_batch_u8": (_i32, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _f, _f, _fp, _i64, _fp, _fp, _i32, _i32, _fp]),
     "pnr_views_to_tensor_u8": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp]),
+    "pnr_color_jitter_workspace_bytes": (_u64, [_i32, _i32, _i32, _i32]),
+    "pnr_color_jitter_plan": (_i32, [_fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float), _u64, _fp, _fp, _u64, _fp]),  # ranges: HOST
+    "pnr_train_batch_u8_jitter": (_i32, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _f, _f, _fp, _i64, _fp, _fp, _i32, _i32, _fp,
+                                         _fp]),
+    "pnr_views_to_tensor_u8_jitter": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
     "pnr_train_draw": (_i32, [_fp, _i32, _i32, _i32, _i32, _i64, _i32, _u64, _fp, _fp, _fp]),
     "pnr_grid_points": (_i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _i64, _i64, _i32, _fp, _fp, _fp]),
     "pnr_mc_workspace_bytes": (_u64, [_i32, _i32, _i32]),

@@ -26,9 +26,10 @@ __device__ __forceinline__ uint8_t quant_u8(float x) { return x == x ? (uint8_t)
 // T(b, balanced), an image byte as the network's input (include/pnr.h, pnr_image_to_tensor): float(b) / 255.0f, ONE correctly
 // rounded division (torchvision's ToTensor); balanced: then (. - 0.5f) / 0.5f, each operation rounded on its own (Normalize(0.5,
 // 0.5)).  The only place this arithmetic exists: pnr_image_to_tensor, pnr_views_to_tensor_u8 and pnr_train_batch_u8 call it.
+// unit_to_tensor is its second half on its own: the colour-jitter gathers (data_u8.h) put their chain between the two.
+__device__ __forceinline__ float unit_to_tensor(float v, int balanced) { return balanced ? __fdiv_rn(__fsub_rn(v, 0.5f), 0.5f) : v; }
 __device__ __forceinline__ float u8_to_tensor(uint32_t b, int balanced) {
-    const float v = __fdiv_rn((float)b, 255.0f);
-    return balanced ? __fdiv_rn(__fsub_rn(v, 0.5f), 0.5f) : v;
+    return unit_to_tensor(__fdiv_rn((float)b, 255.0f), balanced);
 }
 
 // ---------------------------------------------------------------- a frame as 16 x 16 pixel tiles, one workgroup per tile

@@ -3,8 +3,8 @@ The data layer: upstream pixelNeRF's data package (src/data: get_split_dataset, 
 package's drivers, plus ResidentSplit, which keeps a whole split on the card as the bytes its image files hold.
 
 PARITY UNPINNED.  The reference fork's scripts import src/data and do not ship it, and upstream's code is not available where
-this package is developed, so nothing here was compared against either: the specification is the two on-disk layouts the class
-docstrings state (SRN cars / chairs, and the ShapeNet sub-format of DVR / NMR).  Where evalio.metrics_map already relies on a
+this package is developed, so nothing here was compared against either: the specification is the on-disk layouts the class
+docstrings state (SRN cars / chairs, the ShapeNet sub-format of DVR / NMR, and the DTU sub-format of DVR).  Where evalio.metrics_map already relies on a
 layout fact ("image" / "rgb" folders, "<list_name>.lst"), this package agrees with it.
 
 Items come in two modes.  as_bytes=False (the default) is what evaluate, evaluate_approx, gen_video and vis_step take:
@@ -12,24 +12,29 @@ float32 images (NV, 3, H, W).  as_bytes=True is for train.calc_losses: uint8 ima
 converted on the device only where a step needs them (util.train_batch_u8, util.views_to_tensor_u8) to the bits the float
 item holds.
 """
+from .dtu import ColorJitter, DTUDataset
 from .dvr import DVRDataset
 from .resident import ResidentSplit
 from .srn import SRNDataset
 
-__all__ = ["get_split_dataset", "SRNDataset", "DVRDataset", "ResidentSplit"]
+__all__ = ["get_split_dataset", "SRNDataset", "DVRDataset", "DTUDataset", "ColorJitter", "ResidentSplit"]
 
 
 def get_split_dataset(dataset_type, datadir, want_split="all", training=True, **kwargs):
     """The dataset(s) of one folder.  dataset_type "srn" -> SRNDataset, "dvr" -> DVRDataset, "dvr_gen" -> DVRDataset with the
-    "gen_" object lists; want_split "train" | "val" | "test" returns that one set, anything else the (train, val, test) triple.
-    kwargs go to the dataset class (image_size, world_scale, balanced, as_bytes, ...).  `training` is accepted for upstream's
-    signature; it only steered settings of the dataset types that are refused here."""
+    "gen_" object lists, "dtu" -> DTUDataset; want_split "train" | "val" | "test" returns that one set, anything else the
+    (train, val, test) triple.  kwargs go to the dataset class (image_size, world_scale, balanced, as_bytes, ...).  `training`
+    is upstream's switch: for "dtu" it sets max_imgs=49 (a training item is a random 49 of a scan's views); the other types
+    ignore it.  "dvr_dtu", upstream's name for the DTU sub-format, stays refused, because upstream reads it through cv2 and
+    nothing here was compared against that: "dtu" is the working name of this package's own reading of the layout."""
     if dataset_type == "srn":
         cls, flags = SRNDataset, {}
     elif dataset_type == "dvr":
         cls, flags = DVRDataset, {}
     elif dataset_type == "dvr_gen":
         cls, flags = DVRDataset, {"list_prefix": "gen_"}
+    elif dataset_type == "dtu":
+        cls, flags = DTUDataset, ({"max_imgs": 49} if training else {})
     elif dataset_type == "dvr_dtu":
         raise NotImplementedError("dataset type 'dvr_dtu': the DTU sub-format decomposes its projection matrices with "
                                   "cv2.decomposeProjectionMatrix, and this package does not depend on cv2")

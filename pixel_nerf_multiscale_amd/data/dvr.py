@@ -17,7 +17,7 @@ class DVRDataset(torch.utils.data.Dataset):
     present, else the inverse of world_mat_i (a 3 x 4 matrix is extended by the row 0 0 0 1); camera_mat_i[0, 0] must equal
     [1, 1]; fx = camera_mat_i[0, 0] * W / 2 with scale_focal and must be one value over the object; pose = Tw @ pose @ Tc with
     Tw = [[1,0,0,0],[0,0,-1,0],[0,1,0,0],[0,0,0,1]] and Tc = diag(1, -1, -1, 1).  An object with more than max_imgs views
-    yields a random subset of them (numpy's global generator).  The DTU sub-format is not covered (get_split_dataset says why).
+    yields a random subset of them (numpy's global generator).  The DTU sub-format is DTUDataset's (data/dtu.py).
 
     Item: {"path", "img_id", "focal": 0-dim float32 tensor, "images", "masks", "bbox", "poses"}; there is no "c" (the
     principal point is the image centre).  Attributes: z_near, z_far, lindisp = False, balanced."""

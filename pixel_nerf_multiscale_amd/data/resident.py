@@ -16,7 +16,10 @@ class ResidentSplit:
 
     device_boxes=True also keeps the boxes on the card, float32 (N, NV, 4), and batch() adds "bbox_dev", their rows gathered
     on the device: what train.make_batch(draws="device") draws inside without an upload.  With the default the dict is
-    unchanged."""
+    unchanged.
+
+    A dataset whose items carry no "bbox" (DTUDataset on scans without masks) is taken too: self.bbox is None and batch() has
+    no "bbox" key, so the draws cover the whole image; device_boxes=True on such a dataset raises ValueError."""
 
     def __init__(self, dataset, device, max_bytes=None, device_boxes=False):
         if not getattr(dataset, "as_bytes", False):
@@ -45,10 +48,15 @@ class ResidentSplit:
             self.images[i].copy_(images)
             self.poses[i].copy_(item["poses"])
             self.paths.append(item["path"])
-            bbox.append(item["bbox"])
+            if i > 0 and ("bbox" in item) != bool(bbox):
+                raise ValueError(f"{item['path']}: {'' if 'bbox' in item else 'no '}boxes, unlike the objects before it")
+            if "bbox" in item:
+                bbox.append(item["bbox"])
             focal.append(torch.as_tensor(item["focal"], dtype=torch.float32))
             c.append(item.get("c"))
-        self.bbox = torch.stack(bbox)
+        if device_boxes and not bbox:
+            raise ValueError("device_boxes=True needs a dataset whose items have a 'bbox'")
+        self.bbox = torch.stack(bbox) if bbox else None
         self.focal = torch.stack(focal)
         self.c = None if c[0] is None else torch.stack(c)
         self.bbox_dev = util.upload(self.bbox.to(torch.float32).contiguous(), self.device) if device_boxes else None
@@ -62,7 +70,7 @@ class ResidentSplit:
 
     def batch(self, ids):
         """ids: object indices (a sequence or a host int tensor) -> {"path", "img_id", "images" (SB, NV, H, W, 3) uint8 and
-        "poses" on the device, "bbox", "focal", "c" (when the dataset has one) on the host}."""
+        "poses" on the device, "bbox" and "c" (when the dataset has them) and "focal" on the host}."""
         ids = torch.as_tensor(ids, dtype=torch.long).reshape(-1)
         if ids.is_cuda:
             raise ValueError("ids must be host indices: they also select the host-side boxes and intrinsics")
@@ -70,7 +78,10 @@ class ResidentSplit:
             raise IndexError(f"object index outside [0, {len(self)})")
         on_dev = util.upload(ids, self.device)
         data = {"path": [self.paths[i] for i in ids.tolist()], "img_id": ids, "images": self.images[on_dev],
-                "poses": self.poses[on_dev], "bbox": self.bbox[ids], "focal": self.focal[ids]}
+                "poses": self.poses[on_dev]}
+        if self.bbox is not None:
+            data["bbox"] = self.bbox[ids]
+        data["focal"] = self.focal[ids]
         if self.c is not None:
             data["c"] = self.c[ids]
         if self.bbox_dev is not None:

@@ -17,7 +17,7 @@ def curr_nviews_for(nviews, seed):
 
 
 def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=True, is_train=True, balanced=True,
-               draws="host", seed=None):
+               draws="host", seed=None, jitter=None):
     """The front end of calc_losses (train/train.py:243-317): host draws, ONE upload of the (SB, ray_batch_size) pixel
     indices (the source-view choice rides in the same buffer) and one of the intrinsics, both from pinned memory, one launch
     for the rays and colours, and the source views picked on the device.
@@ -35,12 +35,24 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
     views on the device from the key alone (include/pnr.h, pnr_train_draw), and the same gather calls follow.  The boxes are
     data["bbox_dev"] (data.ResidentSplit(device_boxes=True)) or data["bbox"] uploaded.  The batch of a step then depends on
     (seed) only, not on torch's and numpy's global generators, so a run resumed from a checkpoint sees the batches the
-    uninterrupted run would have seen.  The stream is not the reference's, the distribution is (see pnr.h)."""
+    uninterrupted run would have seen.  The stream is not the reference's, the distribution is (see pnr.h).
+
+    jitter, a data.ColorJitter, with an 8-bit batch, draws="device" and is_train: upstream's colour augmentation where the
+    bytes lie.  ONE util.color_jitter_plan launch keyed by the same seed draws a record per object (four factors, the order of
+    the operations, the object's grey mean over all its views), and the two gathers apply it to the sampled pixels and the
+    chosen source views only: no host read and no further upload.  The record depends on (seed) and the bytes alone, so
+    checkpoints need nothing new.  A float batch or draws="host" with jitter raises ValueError; is_train=False ignores it;
+    None makes the calls made without it."""
     if draws not in ("host", "device"):
         raise ValueError(f"draws must be 'host' or 'device', got {draws!r}")
     if draws == "device" and seed is None:
         raise ValueError("draws='device' needs seed, the per-step key: parallel.frame_seed(base_seed, global_step)")
     as_bytes = data["images"].dtype == torch.uint8
+    if not is_train:
+        jitter = None
+    if jitter is not None and not (as_bytes and draws == "device"):
+        raise ValueError("jitter needs an 8-bit batch (uint8 images) and draws='device': the augmentation runs on the device, "
+                         "keyed by the step's seed")
     if as_bytes and (data["images"].dim() != 5 or data["images"].shape[-1] not in (3, 4)):
         raise ValueError(f"a uint8 batch must be (SB, NV, H, W, 3 | 4), got {tuple(data['images'].shape)}")
     all_images = util.upload(data["images"], device)
@@ -60,7 +72,8 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
             boxes = boxes.to(device=device, dtype=torch.float32)
         pix_inds, image_ord = util.train_draw(boxes, SB, NV, W, H, B, curr_nviews_for(nviews, seed), seed,
                                               out_pix=torch.empty(SB, B, dtype=torch.long, device=device))
-        return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced)
+        record = None if jitter is None else util.color_jitter_plan(all_images, jitter, seed)
+        return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced, record)
 
     all_bboxes = data.get("bbox") if (is_train and use_bbox) else None
     if all_bboxes is not None and all_bboxes.is_cuda:
@@ -84,9 +97,9 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
     return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced)
 
 
-def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced):
+def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced, jitter=None):
     """make_batch behind its draws: the intrinsics' upload, the rays and colours of pix_inds (SB, B), the source views and
-    poses of image_ord (SB, NS)."""
+    poses of image_ord (SB, NS).  jitter: the colour-jitter record (SB, 8) of an 8-bit batch, or None."""
     as_bytes = all_images.dtype == torch.uint8
     SB = all_images.shape[0]
     # the loader's focal (SB,) or (SB, 2) and c (SB, 2): one (SB, 4) block, uploaded once
@@ -106,8 +119,9 @@ def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_ne
     c = None if c is None else c.contiguous()
 
     if as_bytes:
-        rays, rgb_gt = util.train_batch_u8(all_images, all_poses, focal, c, pix_inds, z_near, z_far, balanced=balanced)
-        src_images = util.views_to_tensor_u8(all_images, image_ord, balanced=balanced)
+        kw = {} if jitter is None else {"jitter": jitter}
+        rays, rgb_gt = util.train_batch_u8(all_images, all_poses, focal, c, pix_inds, z_near, z_far, balanced=balanced, **kw)
+        src_images = util.views_to_tensor_u8(all_images, image_ord, balanced=balanced, **kw)
     else:
         rays, rgb_gt = util.train_batch(all_images, all_poses, focal, c, pix_inds, z_near, z_far)
         src_images = util.batched_index_select_nd(all_images, image_ord)
@@ -115,7 +129,7 @@ def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_ne
 
 
 def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far, loss, use_bbox=True, is_train=True,
-                balanced=True, draws="host", seed=None):
+                balanced=True, draws="host", seed=None, jitter=None):
     """One batch of the data loader -> (loss, loss_dict), ready for loss.backward().
 
     net          PixelNeRFNet (on the device)
@@ -132,6 +146,8 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     use_bbox     the reference's self.use_bbox (its switch-off at args.no_bbox_step is the caller's schedule)
     draws, seed  "host" (the default): the draws below; "device" with seed = the per-step key: make_batch's keyed draws on
                  the device, which consume neither global generator
+    jitter       None, or a data.ColorJitter: the colour augmentation of make_batch (8-bit batch, draws="device", training
+                 only — is_train=False ignores it)
 
     loss_dict has "rc", "rf" (only with a fine pass) and "t".  Unlike the reference, which returns Python floats (three
     .item() calls, i.e. three host synchronisations per step), each value is a 0-dim view of ONE 3-float device buffer:
@@ -147,7 +163,7 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     dev = net.poses.device
     all_rays, all_rgb_gt, src_images, src_poses, focal, c = make_batch(
         data, dev, ray_batch_size=ray_batch_size, nviews=nviews, z_near=z_near, z_far=z_far, use_bbox=use_bbox, is_train=is_train,
-        balanced=balanced, draws=draws, seed=seed)
+        balanced=balanced, draws=draws, seed=seed, jitter=jitter)
     net.encode(src_images, src_poses, focal, c=c)
 
     render_dict = render_par(all_rays, want_weights=True)
@@ -167,7 +183,7 @@ def train_step(net, render_par, data, optim, *, grad_hook=None, **calc_losses_kw
     optim        optim.DeviceAdam: unscale, clip_grad_norm_, the found-inf skip, Adam and the scaler's update are its step()
     grad_hook    called with no arguments between backward and the step — the place for
                  parallel.allreduce_gradients(params); a gradient it replaces is re-adopted by optim.step()
-    the rest     calc_losses' keywords (ray_batch_size, nviews, z_near, z_far, loss, use_bbox, is_train)
+    the rest     calc_losses' keywords (ray_batch_size, nviews, z_near, z_far, loss, use_bbox, is_train, jitter)
 
     -> calc_losses' loss_dict with "grad_norm" added (the fp64 norm of the unscaled gradients before clipping, what
     clip_grad_norm_ returns): 0-dim device views, like the others.  Nothing in here waits for the device; whether the step

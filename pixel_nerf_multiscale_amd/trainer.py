@@ -89,6 +89,8 @@ class Trainer:
     no_bbox_step       steps with global_step >= no_bbox_step draw their pixels from the whole image
     freeze_enc         the encoder's parameters are left out of the optimiser, its latents detached, the encoder in eval()
     seed, draws        the base of every key; "device" (pnr_train_draw) or "host" — see the module text
+    jitter             None or a data.ColorJitter: training steps augment their 8-bit batch's colours on the device, keyed like
+                       the draws (train.make_batch); needs draws="device"; validation and the picture never see it
     print_interval (steps), save_interval / eval_interval / vis_interval (epochs), keep_last_checkpoints, save_strategy
     resume             False, True (latest.pth of this run if it exists) or a path (FileNotFoundError if missing)
     writer             None or an object with add_scalar(tag, value, step) / add_image(tag, hwc_uint8, step, dataformats="HWC")
@@ -103,7 +105,7 @@ class Trainer:
                  nviews, loss, num_epochs=100, lr=1e-4, lr_policy="none", gamma=0.1, step_size=10000, milestones=(10000, 20000),
                  grad_clip=None, scaler=None, no_bbox_step=100000, freeze_enc=False, seed=0, draws="device", print_interval=10,
                  save_interval=1, eval_interval=10, vis_interval=10, keep_last_checkpoints=20, save_strategy="keep_last",
-                 resume=False, writer=None, z_near=None, z_far=None):
+                 resume=False, writer=None, z_near=None, z_far=None, jitter=None):
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError(
@@ -116,6 +118,8 @@ class Trainer:
             raise ValueError(f"save_strategy must be one of {SAVE_STRATEGIES}, got {save_strategy!r}")
         if draws not in ("host", "device"):
             raise ValueError(f"draws must be 'host' or 'device', got {draws!r}")
+        if jitter is not None and draws != "device":
+            raise ValueError("jitter needs draws='device': the augmentation is keyed by the step's seed on the device")
         if isinstance(resume, (str, os.PathLike)) and not os.path.exists(resume):
             raise FileNotFoundError(f"checkpoint not found: {os.fspath(resume)}")
         self.net, self.renderer, self.name = net, renderer, name
@@ -129,6 +133,7 @@ class Trainer:
         self.z_near = float(train_data.z_near if z_near is None else z_near)
         self.z_far = float(train_data.z_far if z_far is None else z_far)
         self.balanced = bool(getattr(train_data, "balanced", True))
+        self.jitter = jitter
         self.device = next(net.parameters()).device
 
         self.log_dir = os.path.join(logs_path, name)
@@ -209,7 +214,7 @@ class Trainer:
         key = frame_seed(self.seed, global_step)
         with self._keyed(key):
             return train.train_step(self.net, self.render_par, data, self.optimizer,
-                                    **self._losses_kw(key, use_bbox=global_step < self.no_bbox_step))
+                                    **self._losses_kw(key, use_bbox=global_step < self.no_bbox_step, jitter=self.jitter))
 
     def _net_train(self):
         self.net.train()

@@ -318,15 +318,52 @@ def _images_u8(images_u8):
     return images_u8.contiguous(), tuple(int(s) for s in images_u8.shape)
 
 
-def train_batch_u8(images_u8, poses, focal, c, pix_inds, z_near, z_far, balanced=True):
+def _jitter_record(jitter, SB):
+    """A colour-jitter record for the gathers: float32 (SB, 8), contiguous (color_jitter_plan's output)."""
+    if not torch.is_tensor(jitter) or jitter.dtype != torch.float32 or tuple(jitter.shape) != (SB, 8):
+        raise ValueError(f"jitter must be a float32 ({SB}, 8) record, got {getattr(jitter, 'dtype', None)} "
+                         f"{tuple(getattr(jitter, 'shape', ()))}")
+    return jitter.contiguous()
+
+
+def color_jitter_plan(images_u8, ranges, seed, out=None):
+    """The colour-jitter records of one step (pnr_color_jitter_plan; include/pnr.h writes the arithmetic down): per object of
+    the uint8 batch images_u8 (SB, NV, H, W, 3 | 4) on the device, one brightness / contrast / saturation factor and hue shift
+    inside `ranges` (four host floats, or a data.ColorJitter), the order of the four operations, and — where contrast takes
+    part — the object's grey mean over ALL its views, all keyed by `seed` alone (the per-step key).  -> float32 (SB, 8) on the
+    device: [brightness, contrast, saturation, hue, mean, order code, 0, 0], what train_batch_u8 / views_to_tensor_u8 take as
+    `jitter`.  Reads nothing back; `out` (SB, 8) float32 contiguous is filled when given."""
+    from . import _native as N
+    import ctypes
+    images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
+    ranges = tuple(float(r) for r in getattr(ranges, "ranges", ranges))
+    seed = int(seed)
+    if len(ranges) != 4:
+        raise ValueError(f"ranges must be (brightness, contrast, saturation, hue), got {ranges}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
+    dev = N.same_device(images_u8, out)
+    rec = torch.empty(SB, 8, dtype=torch.float32, device=dev) if out is None else _jitter_record(out, SB)
+    if out is not None and rec.data_ptr() != out.data_ptr():
+        raise ValueError("out must be contiguous")
+    nbytes = int(N.lib.pnr_color_jitter_workspace_bytes(SB, NV, W, H)) if ranges[1] != 0.0 else 0
+    ws = N.scratch(nbytes, dev)
+    N.check(N.lib.pnr_color_jitter_plan(N.ptr(images_u8), SB, NV, W, H, C, (ctypes.c_float * 4)(*ranges), seed, N.ptr(rec),
+                                        ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_color_jitter_plan")
+    return rec
+
+
+def train_batch_u8(images_u8, poses, focal, c, pix_inds, z_near, z_far, balanced=True, jitter=None):
     """train_batch for a batch whose images stay 8-bit on the device (pnr_train_batch_u8): images_u8 (SB, NV, H, W, 3 | 4)
     uint8, interleaved as the files hold them (a fourth channel is stepped over), at any byte offset of a larger allocation;
     the other arguments as train_batch takes them.  balanced says what the FLOAT image of the loader would have been —
     (b / 255 - 0.5) / 0.5 in [-1, 1] (True) or b / 255 (False) — and rgb_gt = 0.5 * that + 0.5, bit for bit what train_batch
-    gives on that float image; the rays are train_batch's bits.  -> rays (SB, B, 8), rgb_gt (SB, B, 3)."""
+    gives on that float image; the rays are train_batch's bits.  -> rays (SB, B, 8), rgb_gt (SB, B, 3).
+    jitter: color_jitter_plan's record (SB, 8) — each sampled pixel goes through its object's colour chain between the
+    division by 255 and the balanced map (pnr_train_batch_u8_jitter); None: the call and the bits without it."""
     from . import _native as N
     images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
-    dev = N.same_device(images_u8, poses, pix_inds)
+    dev = N.same_device(images_u8, poses, pix_inds, jitter)
     if tuple(poses.shape) != (SB, NV, 4, 4):
         raise ValueError(f"poses must be ({SB}, {NV}, 4, 4), got {tuple(poses.shape)}")
     if pix_inds.dim() != 2 or pix_inds.shape[0] != SB or pix_inds.dtype != torch.long:
@@ -341,27 +378,37 @@ def train_batch_u8(images_u8, poses, focal, c, pix_inds, z_near, z_far, balanced
     B = pix_inds.shape[1]
     rays = torch.empty(SB, B, 8, device=dev)
     rgb_gt = torch.empty(SB, B, 3, device=dev)
-    N.check(N.lib.pnr_train_batch_u8(N.ptr(images_u8), N.ptr(poses), N.ptr(focal), N.ptr(c), SB, NV, W, H, float(z_near),
-                                     float(z_far), pix_inds.data_ptr(), B, N.ptr(rays), N.ptr(rgb_gt), C, int(bool(balanced)),
-                                     N.current_stream(dev)), "pnr_train_batch_u8")
+    args = (N.ptr(images_u8), N.ptr(poses), N.ptr(focal), N.ptr(c), SB, NV, W, H, float(z_near), float(z_far), pix_inds.data_ptr(),
+            B, N.ptr(rays), N.ptr(rgb_gt), C, int(bool(balanced)))
+    if jitter is None:
+        N.check(N.lib.pnr_train_batch_u8(*args, N.current_stream(dev)), "pnr_train_batch_u8")
+    else:
+        N.check(N.lib.pnr_train_batch_u8_jitter(*args, N.ptr(_jitter_record(jitter, SB)), N.current_stream(dev)),
+                "pnr_train_batch_u8_jitter")
     return rays, rgb_gt
 
 
-def views_to_tensor_u8(images_u8, view_ord, balanced=True):
+def views_to_tensor_u8(images_u8, view_ord, balanced=True, jitter=None):
     """The selected views of an 8-bit batch as the network's input, converted where they lie (pnr_views_to_tensor_u8):
     images_u8 (SB, NV, H, W, 3 | 4) uint8 and view_ord (SB, NS) long, both on the device -> (SB, NS, 3, H, W) float32, per view
     what image_to_tensor gives on it, bit for bit.  In place of batched_index_select_nd over float images.  A view index
-    outside [0, NV) gives NaN planes (the indices are never read on the host); a repeated view is allowed."""
+    outside [0, NV) gives NaN planes (the indices are never read on the host); a repeated view is allowed.
+    jitter: color_jitter_plan's record (SB, 8) — every pixel of a selected view goes through its object's colour chain
+    (pnr_views_to_tensor_u8_jitter); None: the call and the bits without it."""
     from . import _native as N
     images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
-    dev = N.same_device(images_u8, view_ord)
+    dev = N.same_device(images_u8, view_ord, jitter)
     if view_ord.dim() != 2 or view_ord.shape[0] != SB or view_ord.shape[1] < 1 or view_ord.dtype != torch.long:
         raise ValueError(f"view_ord must be ({SB}, NS >= 1) int64, got {tuple(view_ord.shape)} {view_ord.dtype}")
     view_ord = view_ord.contiguous()
     NS = int(view_ord.shape[1])
     out = torch.empty(SB, NS, 3, H, W, dtype=torch.float32, device=dev)
-    N.check(N.lib.pnr_views_to_tensor_u8(N.ptr(images_u8), view_ord.data_ptr(), SB, NV, NS, W, H, C, int(bool(balanced)),
-                                         N.ptr(out), N.current_stream(dev)), "pnr_views_to_tensor_u8")
+    args = (N.ptr(images_u8), view_ord.data_ptr(), SB, NV, NS, W, H, C, int(bool(balanced)), N.ptr(out))
+    if jitter is None:
+        N.check(N.lib.pnr_views_to_tensor_u8(*args, N.current_stream(dev)), "pnr_views_to_tensor_u8")
+    else:
+        N.check(N.lib.pnr_views_to_tensor_u8_jitter(*args, N.ptr(_jitter_record(jitter, SB)), N.current_stream(dev)),
+                "pnr_views_to_tensor_u8_jitter")
     return out
 
 
