@@ -154,36 +154,45 @@ def index_latent(uv, latents):
 
 
 # ------------------------------------------------------------------ a13/a14 model/resnetfc.py:53-62,173-236 ; util/util.py:466-476
-def resnetfc(sd, zx, d_latent, NS, P, n_blocks=5, combine_layer=3, combine_type="average", rnd=None):
+def resnetfc(sd, zx, d_latent, NS, P, n_blocks=5, combine_layer=3, combine_type="average", rnd=None, rec=None):
     """sd = state-dict (reference key names).  zx (SB*NS*P, d_latent + d_in) -> (SB*P, d_out).
     rnd: optional rounding hook rnd(tensor, kind) -> tensor for a mixed-precision emulation of the same network
     (tests/fused_fp64_util.py); None (every caller but that one) leaves the function as the reference wrote it.  Kinds:
     "weight" every weight matrix, "act" a layer input behind its ReLU, "park" the per-view residual stream in front of the
     view reduction; point_forward adds "latent" (the interpolated latent vector) and "sine" (the sine features).  Biases,
-    the raw lin_in inputs and the accumulation are never rounded."""
+    the raw lin_in inputs and the accumulation are never rounded.
+    rec: optional recorder rec(tensor, name) of every ReLU INPUT (tests/train_fp64_util.relu_margin_mask): "block{b}.in" and
+    "block{b}.fc_0" per block, "lin_out.in", and "park", the per-view stream in front of the view reduction; point_forward
+    adds "sigma", the density head in front of its ReLU.  It changes nothing that is computed."""
     q = (lambda t, kind: t) if rnd is None else rnd
+    note = (lambda t, name: None) if rec is None else rec
     lin = lambda x, k: torch.addmm(sd[k + ".bias"], x, q(sd[k + ".weight"], "weight").t())
     act = lambda x: q(torch.relu(x), "act")
     z, x = zx[:, :d_latent], zx[:, d_latent:]
     x = lin(x, "lin_in")
     for b in range(n_blocks):
         if b == combine_layer and NS > 1:
+            note(x, "park")
             x = q(x, "park").reshape(-1, NS, P, x.shape[-1])
             x = x.mean(dim=1) if combine_type == "average" else x.max(dim=1)[0]
             x = x.reshape(-1, x.shape[-1])
         if d_latent > 0 and b < combine_layer:
             x = x + lin(z, f"lin_z.{b}")
+        note(x, f"block{b}.in")
         net = lin(act(x), f"blocks.{b}.fc_0")
+        note(net, f"block{b}.fc_0")
         dx = lin(act(net), f"blocks.{b}.fc_1")
         x = x + dx
+    note(x, "lin_out.in")
     return lin(act(x), "lin_out")
 
 
 # ------------------------------------------------------------------ a10/a15 model/models.py.backup2:155-282
 def point_forward(sd, cam, latents, xyz, viewdirs, NS, use_code_viewdirs=False,
-                  n_blocks=5, combine_layer=3, combine_type="average", return_stages=False, rnd=None):
+                  n_blocks=5, combine_layer=3, combine_type="average", return_stages=False, rnd=None, rec=None):
     """xyz, viewdirs (SB,P,3) world space -> (SB,P,4) [sigmoid rgb, relu sigma].
-    cam = (w2c (SB*NS,3,4), focal (1|SB|SB*NS,2), c (1|SB|SB*NS,2)) from encode_cameras.  rnd: resnetfc's rounding hook."""
+    cam = (w2c (SB*NS,3,4), focal (1|SB|SB*NS,2), c (1|SB|SB*NS,2)) from encode_cameras.  rnd: resnetfc's rounding hook; rec: its
+    ReLU-input recorder."""
     w2c, focal, c = cam
     SB, P, _ = xyz.shape
     rep = lambda t: t.unsqueeze(1).expand(-1, NS, *t.shape[1:]).reshape(-1, *t.shape[1:])
@@ -209,7 +218,10 @@ def point_forward(sd, cam, latents, xyz, viewdirs, NS, use_code_viewdirs=False,
     if rnd is not None:
         lat = rnd(lat, "latent")
     zx = torch.cat((lat, zf), dim=-1)
-    o = resnetfc(sd, zx, L, NS, P, n_blocks, combine_layer, combine_type, **hook).reshape(-1, P, 4)
+    net_hook = hook if rec is None else dict(hook, rec=rec)
+    o = resnetfc(sd, zx, L, NS, P, n_blocks, combine_layer, combine_type, **net_hook).reshape(-1, P, 4)
+    if rec is not None:
+        rec(o[..., 3:4].reshape(-1, 1), "sigma")
     out = torch.cat([torch.sigmoid(o[..., :3]), torch.relu(o[..., 3:4])], dim=-1).reshape(SB, P, 4)
     if return_stages:
         return out, dict(uv=uv, index_out=lat, mlp_in=zx, mlp_out=o.reshape(-1, 4))

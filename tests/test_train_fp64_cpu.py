@@ -1,6 +1,8 @@
 """CPU self-checks of tests/train_fp64_util.py, the fp64 truth test_gpu_train_fp64.py holds the training backward to: the
 exact-geometry lattice lands where it is planned, the oracle's lookup follows ATen's grid_sampler_2d at the borders, the ray
 mask catches what it is for, and the comparison rules at the bounds used reject planted kernel defects."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -181,6 +183,182 @@ def test_full_compare_rejects_the_clamp_gradient_at_a_border(monkeypatch):
     assert np.abs(wrong["xyz"][0, border] - truth["xyz"][0, border]).max() > 0
     with pytest.raises(AssertionError, match="xyz"):
         tu.full_compare(wrong, truth, 5e-4)
+
+
+# ----------------------------------------------------------------------------- the ReLU-margin mask
+@pytest.mark.parametrize("name", list(tu.MARGIN_CASES))
+def test_relu_margin_mask_stays_under_the_cap_and_removes_the_events(name):
+    """Every case of test_several_views_match_fp64_at_every_entry, oracle in fp64 and fp32 only: at most 5 % of the points
+    masked, and the masked fp32 restatement within 1e-5 of fp64 at every entry of every gradient (with 5e-4 to spend, a
+    kernel's own error is what is left to see)."""
+    for P in tu.MARGIN_POINTS:
+        c = tu.margin_case(name, P)
+        args = (c["spec"], c["poses"], c["maps"], c["xyz"], c["dirs"])
+        keep = tu.relu_margin_mask(*args, uv_scale=c["uvs"])
+        assert keep.shape == c["cot"].shape[:2]
+        assert int((~keep).sum()) <= tu.MASK_MAX_FRACTION * keep.size, (name, P, int((~keep).sum()))
+        cot = tu.mask_points(c["cot"], keep)
+        _, truth = tu.point_grads_fp64(*args, cot, uv_scale=c["uvs"])
+        _, ref32 = tu.point_grads_fp64(*args, cot, uv_scale=c["uvs"], dtype=torch.float32)
+        tu.full_compare(ref32, truth, 1e-5, f"{name} P {P}")
+
+
+@functools.lru_cache(maxsize=None)
+def _four_views():
+    """(256, 8, 9), four views, 1001 points per object: (case, args, keep, masked cotangent, fp64 (out, grads, d(zx))); shared,
+    so read-only."""
+    c = tu.margin_case("fix_ns4", 1001)
+    args = (c["spec"], c["poses"], c["maps"], c["xyz"], c["dirs"])
+    keep = tu.relu_margin_mask(*args)
+    cot = tu.mask_points(c["cot"], keep)
+    return c, args, keep, cot, tu.point_grads_fp64(*args, cot, stages=True)
+
+
+def test_without_the_mask_the_fp32_restatement_is_not_within_1e_5():
+    """The mask is what removes the events: the same four-view run with every cotangent row fails the 1e-5 rule."""
+    c = tu.margin_case("fix_ns4", 1001)
+    args = (c["spec"], c["poses"], c["maps"], c["xyz"], c["dirs"])
+    _, truth = tu.point_grads_fp64(*args, c["cot"])
+    _, ref32 = tu.point_grads_fp64(*args, c["cot"], dtype=torch.float32)
+    with pytest.raises(AssertionError):
+        tu.full_compare(ref32, truth, 1e-5)
+
+
+def test_argmax_rule_masks_a_near_tie_of_the_view_maximum():
+    """combine_type "max" with views 0 and 2 sharing pose and map: every unit of the parked stream ties, so every point is
+    masked by the argmax rule; the same inputs under "average" keep nearly all."""
+    spec, poses, maps, xyz, dirs, _ = _small_points(NS=3, P=50, combine="max")
+    poses[:, 2] = poses[:, 0]
+    maps[0][2] = maps[0][0]
+    info = {}
+    keep = tu.relu_margin_mask(spec, poses, maps, xyz, dirs, info=info)
+    assert not keep.any() and info["argmax"] > 0
+    assert tu.relu_margin_mask(dict(spec, combine_type="average"), poses, maps, xyz, dirs).sum() > 40
+
+
+def test_latent_scatter_is_the_lookups_adjoint_on_absolute_values():
+    """latent_scatter's sum |g w| against autograd through the oracle's lookup with |g| as cotangent, and its counts
+    where it is zero; three levels with uv_scale, points on and beyond the borders."""
+    rng = np.random.default_rng(6)
+    lat, B, P = [(3, 16, 16), (2, 8, 8), (4, 5, 9)], 2, 200
+    uv = rng.random((B, P, 2)) * 40 - 4
+    uvs = [(0.5, 0.5), (0.25, 0.25), (0.25, 0.125)]
+    g = rng.standard_normal((B * P, 9 + 5))
+    got = tu.latent_scatter(g, uv, lat, uvs)
+    c0 = 0
+    for (C, H, W), s, (tot, cnt) in zip(lat, uvs, got):
+        m = torch.zeros(B, C, H, W, dtype=tu.F64, requires_grad=True)
+        o = orc.index_latent(torch.from_numpy(uv) * torch.tensor(s, dtype=tu.F64), [m])              # (B, C, P)
+        (o * torch.from_numpy(np.abs(g[:, c0:c0 + C])).reshape(B, P, C).transpose(1, 2)).sum().backward()
+        assert np.allclose(tot, m.grad.numpy(), rtol=0, atol=1e-12)
+        assert cnt.sum() <= 4 * B * P and cnt.min() >= 0 and ((cnt[:, 0] > 0) == (tot.max(axis=1) > 0)).all()
+        c0 += C
+
+
+def _view_mean_scaled(rows, NS_scale):
+    """orc.resnetfc with the view mean's backward multiplied by NS_scale on the given rows of the reduced stream (the
+    forward unchanged): k_combine_bwd leaving out 1 / NS there."""
+    def net(sd, zx, d_latent, NS, P, n_blocks=5, combine_layer=3, combine_type="average"):
+        lin = lambda x, k: torch.addmm(sd[k + ".bias"], x, sd[k + ".weight"].t())
+        z, x = zx[:, :d_latent], zx[:, d_latent:]
+        x = lin(x, "lin_in")
+        for b in range(n_blocks):
+            if b == combine_layer and NS > 1:
+                x = x.reshape(-1, NS, P, x.shape[-1]).mean(dim=1).reshape(-1, x.shape[-1])
+                extra = torch.zeros(x.shape[0], 1, dtype=x.dtype)
+                extra[rows] = NS_scale - 1.0
+                x = x + (x - x.detach()) * extra         # + 0 exactly; the gradient times 1 + extra
+            if b < combine_layer:
+                x = x + lin(z, f"lin_z.{b}")
+            x = x + lin(torch.relu(lin(torch.relu(x), f"blocks.{b}.fc_0")), f"blocks.{b}.fc_1")
+        return lin(torch.relu(x), "lin_out")
+    return net
+
+
+def test_every_entry_rule_under_the_mask_rejects_view_and_block_mutants(monkeypatch):
+    """full_compare at 5e-4 on the masked four-view case, truth against truth with one planted defect each (applied to the
+    fp64 gradients on the CPU): one view's scatter landing in the next view's map; one view's contributions dropped; the view
+    mean's 1 / NS missing on one 256-thread block of k_combine_bwd (4 points at d_hidden 64); the last 4 points of an object
+    (the last block of k_features_bwd's (P + 3) / 4 grid) dropped."""
+    c, args, keep, cot, (_, truth, dzx) = _four_views()
+    SB, NS, P = c["spec"]["SB"], c["spec"]["NS"], 1001
+    assert tu.full_compare(truth, truth, 5e-4)["latent.0"] == 0
+    g = truth["latent.0"].reshape(SB, NS, *truth["latent.0"].shape[1:])
+    moved = g.copy()
+    moved[1, 3] += moved[1, 2]
+    moved[1, 2] = 0
+    dropped = g.copy()
+    dropped[2, 1] = 0
+    for what, bad in (("moved", moved), ("dropped", dropped)):
+        with pytest.raises(AssertionError, match="latent.0"):
+            tu.full_compare({**truth, "latent.0": bad.reshape(truth["latent.0"].shape)}, truth, 5e-4, what)
+    # the last 4 points of object 1 that carry a cotangent: every gradient that sums over points notices, d(xyz) has the rows themselves
+    live = np.flatnonzero(keep[1])[-4:]
+    c2 = cot.copy()
+    c2[1, live] = 0
+    _, short = tu.point_grads_fp64(*args, c2)
+    with pytest.raises(AssertionError) as e:
+        tu.full_compare(short, truth, 5e-4)
+    assert "latent.0" in str(e.value) and "xyz" in str(e.value) and "lin_z.0.weight" in str(e.value)
+    # 1 / NS missing on the block of points 1001 + 4 .. 1001 + 7 of the reduced stream (kept ones)
+    rows = P + np.flatnonzero(keep[1])[4:8]
+    monkeypatch.setattr(orc, "resnetfc", _view_mean_scaled(torch.from_numpy(rows), float(NS)))
+    _, unscaled = tu.point_grads_fp64(*args, cot)
+    monkeypatch.undo()
+    for k in ("coarse.blocks.3.fc_0.weight", "coarse.lin_out.weight"):        # behind the reduction: untouched
+        assert np.array_equal(unscaled[k], truth[k])
+    with pytest.raises(AssertionError) as e:
+        tu.full_compare(unscaled, truth, 5e-4)
+    assert "latent.0" in str(e.value) and "lin_z.0.weight" in str(e.value)
+
+
+def test_every_entry_rule_rejects_a_fixed_point_sum_that_wraps():
+    """The four-view case's own contributions g w (fp32 d(zx) rows times the fp64 taps' weights) through fixed_point_sum.
+    k_latq_scale's s = 61 - ex - ceil(log2 n_terms) keeps two bits of headroom, so with at most n_terms contributions of
+    |g w| < 2^ex per entry a scale two bits larger is the last that cannot wrap: it must still pass.  What n_terms guards is
+    the case of every contribution to an entry having one sign and the largest magnitude; with that entry planted (n_terms
+    contributions of max |g|), a scale two bits beyond what n_terms allows (s + 4) wraps the entry and is rejected, and so
+    is n_terms understated 16-fold (MV / 4 for 4 MV)."""
+    c, args, keep, cot, (_, truth, dzx) = _four_views()
+    spec = c["spec"]
+    C, H, W = spec["lat"][0]
+    with torch.no_grad():
+        uv = tu.point_forward_oracle(*args)[1]["uv"].numpy()
+    B, P = uv.shape[:2]
+    ix, iy = np.clip(uv[..., 0], 0, W - 1), np.clip(uv[..., 1], 0, H - 1)
+    x0, y0 = np.floor(ix), np.floor(iy)
+    g32 = dzx[:, :C].astype(np.float32).reshape(B, P, C)
+    contrib, index = [], []
+    for xx, yy, ww in ((x0, y0, (x0 + 1 - ix) * (y0 + 1 - iy)), (x0 + 1, y0, (ix - x0) * (y0 + 1 - iy)),
+                       (x0, y0 + 1, (x0 + 1 - ix) * (iy - y0)), (x0 + 1, y0 + 1, (ix - x0) * (iy - y0))):
+        live = (xx <= W - 1) & (yy <= H - 1) & (ww != 0)
+        b, p = np.nonzero(live)
+        tex = (yy[b, p] * W + xx[b, p]).astype(np.int64)
+        contrib.append((g32[b, p] * ww[b, p].astype(np.float32)[:, None]).reshape(-1))
+        index.append(((b[:, None] * C + np.arange(C)[None]) * (H * W) + tex[:, None]).reshape(-1))
+    contrib, index = np.concatenate(contrib), np.concatenate(index)
+    n_terms = 4 * B * P
+    gmax = float(np.abs(g32).max())
+    s = tu.latq_scale_bits(gmax, n_terms)
+    t = truth["latent.0"].reshape(-1)
+    for bits in (0, 2):
+        got = tu.fixed_point_sum(contrib, index, t.size, s + bits)
+        assert tu.full_compare({"m": got}, {"m": t}, 5e-4)["m"] < 1e-5
+    # the guarded case: entry 0 receives n_terms contributions of + max |g|
+    free = index != 0
+    contrib = np.concatenate([contrib[free], np.full(n_terms, gmax, np.float32)])
+    index = np.concatenate([index[free], np.zeros(n_terms, np.int64)])
+    t = np.zeros_like(t)
+    np.add.at(t, index, contrib.astype(np.float64))
+    rest = np.arange(t.size) != 0
+    for bits, n in ((0, n_terms), (2, n_terms)):
+        got = tu.fixed_point_sum(contrib, index, t.size, tu.latq_scale_bits(gmax, n) + bits)
+        assert abs(got[0] - t[0]) <= 1e-6 * t[0]
+        assert tu.full_compare({"m": got[rest]}, {"m": t[rest]}, 5e-4)["m"] < 1e-5
+    for bits, n in ((4, n_terms), (0, n_terms // 16)):
+        got = tu.fixed_point_sum(contrib, index, t.size, tu.latq_scale_bits(gmax, n) + bits)
+        with pytest.raises(AssertionError):
+            tu.full_compare({"m": got}, {"m": t}, 5e-4)
 
 
 def test_depth_bound_rejects_the_neighbouring_slot_of_a_tie():

@@ -103,10 +103,10 @@ def fp64_step(spec, noise, poses, maps, cot, mask, rays, sds=None, dtype=F64):
     return dict(out=out, z=z, keep=keep, grads=grads)
 
 
-def point_grads_fp64(spec, poses, maps_np, xyz, dirs, cot, uv_scale=None, sd=None, stages=False, dtype=F64):
-    """The oracle's point_forward at explicit points (SB,P,3) in float64 under autograd with cotangent cot (SB,P,4):
-    (out, {coarse.*, latent.*, xyz}) [, d(zx) (SB*NS*P, L + d_in)].  uv_scale: per level (sx, sy) applied to the pixel
-    coordinates, as encoder.uv_scale = "image" makes the kernels do."""
+def point_forward_oracle(spec, poses, maps_np, xyz, dirs, uv_scale=None, sd=None, dtype=F64, rec=None):
+    """The oracle's point_forward at explicit points (SB,P,3) on fresh leaves: (out (SB,P,4), stages, (sd, maps, xyz) leaves).
+    uv_scale: per level (sx, sy) applied to the pixel coordinates, as encoder.uv_scale = "image" makes the kernels do.
+    rec: the oracle's ReLU-input recorder."""
     sd = sd if sd is not None else gu.make_mlp_state(spec, "coarse")
     sdo = {k: torch.from_numpy(np.asarray(v)).to(dtype).requires_grad_(True) for k, v in sd.items()}
     lo = [torch.from_numpy(np.asarray(m)).to(dtype).requires_grad_(True) for m in maps_np]
@@ -116,12 +116,21 @@ def point_grads_fp64(spec, poses, maps_np, xyz, dirs, cot, uv_scale=None, sd=Non
         def scaled(uv, latents):
             return torch.cat([orig(uv * torch.tensor(s, dtype=uv.dtype), [m]) for s, m in zip(uv_scale, latents)], dim=1)
         orc.index_latent = scaled
+    hook = {} if rec is None else dict(rec=rec)
     try:
         o, st = orc.point_forward(sdo, fp64_camera(spec, poses, dtype), lo, xo, torch.from_numpy(np.asarray(dirs)).to(dtype), spec["NS"],
                                   use_code_viewdirs=spec["use_code_viewdirs"], n_blocks=spec["n_blocks"],
-                                  combine_layer=spec["combine_layer"], combine_type=spec["combine_type"], return_stages=True)
+                                  combine_layer=spec["combine_layer"], combine_type=spec["combine_type"], return_stages=True,
+                                  **hook)
     finally:
         orc.index_latent = orig
+    return o, st, (sdo, lo, xo)
+
+
+def point_grads_fp64(spec, poses, maps_np, xyz, dirs, cot, uv_scale=None, sd=None, stages=False, dtype=F64):
+    """point_forward_oracle in float64 under autograd with cotangent cot (SB,P,4):
+    (out, {coarse.*, latent.*, xyz}) [, d(zx) (SB*NS*P, L + d_in)]."""
+    o, st, (sdo, lo, xo) = point_forward_oracle(spec, poses, maps_np, xyz, dirs, uv_scale, sd, dtype)
     zx = st["mlp_in"]
     zx.retain_grad()
     (o * torch.from_numpy(np.asarray(cot)).to(dtype)).sum().backward()
@@ -131,6 +140,135 @@ def point_grads_fp64(spec, poses, maps_np, xyz, dirs, cot, uv_scale=None, sd=Non
     if stages:
         return o.detach().numpy(), g, zx.grad.numpy()
     return o.detach().numpy(), g
+
+
+# ----------------------------------------------------------------------------- explicit-point cases and the ReLU-margin mask
+def point_spec(lat, NS=1, SB=1, d_hidden=64, combine_type="average", image=(8, 4), focal=2.0, seed=201, **kw):
+    return gu._case(seed=seed, d_hidden=d_hidden, lat=lat, image=image, focal=focal, NS=NS, SB=SB, combine_type=combine_type, **kw)
+
+
+def random_points(spec, P, seed):
+    """P points per object inside the source frusta (what the renderer feeds the MLP), and their view directions."""
+    rng = np.random.default_rng(seed)
+    rays, _ = gu.make_inputs(dict(spec, N=max(P, 1), edge=False))
+    xyz = np.zeros((spec["SB"], P, 3), np.float32)
+    dirs = np.zeros_like(xyz)
+    for sb in range(spec["SB"]):
+        r = rays[sb, :P]
+        t = spec["z_near"] + (spec["z_far"] - spec["z_near"]) * rng.random((P, 1))
+        xyz[sb] = r[:, :3] + t * r[:, 3:6]
+        dirs[sb] = r[:, 3:6]
+    return xyz, dirs
+
+
+# A unit is at risk when its fp64 ReLU input lies within RELU_MARGIN_FACTOR row deviations of 0 (relu_margin_mask).  Measured
+# on the CPU with the oracle in fp64 and in fp32 alone, over every (case, P) of MARGIN_CASES x MARGIN_POINTS: the smallest
+# power of two at which the fp32 restatement's worst entry error / scale over every gradient is <= 1e-5 is 1/2 (worst
+# 7.6e-6, as at 1, 2 and 8; with no mask and at 1/4 up to 1.1e-2); times 4 for a correct fp32 implementation that sums
+# in another order than torch.  Masked points at 2, of SB * P, P = 1001: lds_ns4 14 / 3003 (0.5 %), fix_ns2 5 (0.2 %),
+# fix_ns3 12 (0.4 %), fix_ns4 9 (0.3 %), fix_ns4_max 10 (0.3 %), c512_ns3 8 (0.3 %), ms4_ns3 15 / 2002 (0.7 %),
+# ms4_ns3_uv 5 / 2002 (0.2 %); at most 1.2 % at 255 .. 257 points per object (ms4_ns3, 6 / 510) and none at P = 1.  The
+# argmax rule of fix_ns4_max adds no point at 2 (1 of 771 at 4, up to 3 of 3003 at 8).  At 8 the largest share is 4.1 %.
+RELU_MARGIN_FACTOR = 2.0
+MS4 = [(64, 16, 16), (64, 16, 16), (128, 8, 8), (256, 4, 4)]
+# name -> (lat, route of the latent gradient, NS, SB, d_hidden, combine_type, uv_scale = "image")
+MARGIN_CASES = {
+    "lds_ns4": ([(256, 8, 8)], 1, 4, 3, 64, "average", False),
+    "fix_ns2": ([(256, 8, 9)], 2, 2, 3, 64, "average", False),
+    "fix_ns3": ([(256, 8, 9)], 2, 3, 3, 64, "average", False),
+    "fix_ns4": ([(256, 8, 9)], 2, 4, 3, 64, "average", False),
+    "fix_ns4_max": ([(256, 8, 9)], 2, 4, 3, 64, "max", False),
+    "c512_ns3": ([(512, 5, 9)], 2, 3, 3, 64, "average", False),
+    "ms4_ns3": (MS4, 2, 3, 2, 128, "average", False),
+    "ms4_ns3_uv": (MS4, 2, 3, 2, 128, "average", True),
+}
+MARGIN_POINTS = (1, 255, 256, 257, 1001)
+
+
+def margin_case(name, P, lat=None):
+    """Inputs of one (case, points per object): dict(spec, poses, maps, xyz, dirs, cot, uvs, route).  The spec, the points
+    and the cotangent are test_route_and_block_boundaries_match_fp64's (seed 211 + P, default_rng(P)).  lat: other levels
+    for the same points (the route-equivalence test cuts a map along its channels)."""
+    lat0, route, NS, SB, d_hidden, combine, uv_image = MARGIN_CASES[name]
+    spec = point_spec(lat or lat0, NS=NS, SB=SB, d_hidden=d_hidden, combine_type=combine, image=(128, 128), focal=131.25,
+                      seed=211 + P)
+    _, poses = gu.make_inputs(dict(spec, N=1))
+    xyz, dirs = random_points(spec, P, P)
+    cot = np.random.default_rng(P).standard_normal((SB, P, 4)).astype(np.float32)
+    uvs = [(w / spec["image"][0], h / spec["image"][1]) for _, h, w in spec["lat"]] if uv_image else None
+    return dict(spec=spec, poses=poses, maps=gu.make_latents(spec), xyz=xyz, dirs=dirs, cot=cot, uvs=uvs, route=route)
+
+
+def _relu_inputs(spec, poses, maps, xyz, dirs, uv_scale, sd, dtype):
+    recs = {}
+    with torch.no_grad():
+        point_forward_oracle(spec, poses, maps, xyz, dirs, uv_scale, sd, dtype,
+                             rec=lambda t, name: recs.__setitem__(name, t.detach().to(F64).numpy()))
+    return recs
+
+
+def relu_margin_mask(spec, poses, maps, xyz, dirs, uv_scale=None, sd=None, factor=RELU_MARGIN_FACTOR, info=None):
+    """The points whose gradient term is a property of the backward and not of forward rounding, as a (SB, P) bool array of
+    points to KEEP; computed from the oracle in fp64 and in fp32 alone, never from a kernel's output.
+    Every ReLU input is recorded in both precisions: per block the block input and the fc_0 output, the lin_out input, the
+    sigma head.  Row r of a tensor deviates by d_r = max_j |x32_rj - x64_rj|; a unit is at risk when |x64_rj| < factor d_r
+    (the one-column sigma head takes d_r from the same row of the lin_out input): an fp32 forward may decide it the other way,
+    which moves that point's term of every gradient sum by O(1).  With combine_type "max" a unit of the parked per-view stream
+    is at risk as well when its largest and second-largest view lie within factor d_r (the largest d_r of the point's views):
+    the argmax may flip and send the gradient to another view.  Rows in front of the view reduction are (object, view, point);
+    a point is masked through any of its views.  The caller zeroes a masked point's cotangent row on both sides.
+    info: a dict that receives the counts {"relu": points by the ReLU rule, "argmax": points the argmax rule adds}."""
+    SB, P, NS = spec["SB"], np.asarray(xyz).shape[1], spec["NS"]
+    x64 = _relu_inputs(spec, poses, maps, xyz, dirs, uv_scale, sd, F64)
+    x32 = _relu_inputs(spec, poses, maps, xyz, dirs, uv_scale, sd, torch.float32)
+    dev = {k: np.abs(x32[k] - x64[k]).max(axis=1) for k in x64}
+    bad = np.zeros((SB, P), bool)
+    for k, a in x64.items():
+        if k == "park":
+            continue
+        d = dev["lin_out.in"] if k == "sigma" else dev[k]
+        risk = (np.abs(a) < factor * d[:, None]).any(axis=1)
+        bad |= risk.reshape(SB, NS, P).any(axis=1) if risk.size == SB * NS * P and NS > 1 else risk.reshape(SB, P)
+    n_relu = int(bad.sum())
+    if spec["combine_type"] == "max" and NS > 1:
+        a = np.sort(x64["park"].reshape(SB, NS, P, -1), axis=1)
+        d = dev["park"].reshape(SB, NS, P).max(axis=1)
+        bad |= ((a[:, -1] - a[:, -2]) < factor * d[..., None]).any(axis=-1)
+    if info is not None:
+        info.update(relu=n_relu, argmax=int(bad.sum()) - n_relu)
+    return ~bad
+
+
+def mask_points(cot, keep):
+    """cot (SB,P,4) with the rows of masked points zeroed (a copy)."""
+    out = np.array(cot, dtype=np.float32, copy=True)
+    out[~keep] = 0.0
+    return out
+
+
+def latent_scatter(dzx, uv, lat, uv_scale=None):
+    """What reaches every latent-map entry, from the d(zx) rows (SB*NS*P, >= L) and the pixel coordinates uv (SB*NS, P, 2)
+    of point_grads_fp64(stages=True) / point_forward_oracle's stages, with index_latent's taps in float64: per level
+    (sum |g w| (SB*NS, C, H, W), number of contributions with w != 0 (SB*NS, 1, H, W))."""
+    uv = np.asarray(uv, np.float64)
+    B, P = uv.shape[:2]
+    out, c0 = [], 0
+    for lvl, (C, H, W) in enumerate(lat):
+        s = uv_scale[lvl] if uv_scale else (1.0, 1.0)
+        ix, iy = np.clip(uv[..., 0] * s[0], 0, W - 1), np.clip(uv[..., 1] * s[1], 0, H - 1)
+        x0, y0 = np.floor(ix), np.floor(iy)
+        g = np.abs(np.asarray(dzx, np.float64)[:, c0:c0 + C]).reshape(B, P, C)
+        tot, cnt = np.zeros((B, H * W, C)), np.zeros((B, H * W))
+        for xx, yy, ww in ((x0, y0, (x0 + 1 - ix) * (y0 + 1 - iy)), (x0 + 1, y0, (ix - x0) * (y0 + 1 - iy)),
+                           (x0, y0 + 1, (x0 + 1 - ix) * (iy - y0)), (x0 + 1, y0 + 1, (ix - x0) * (iy - y0))):
+            live = (xx <= W - 1) & (yy <= H - 1) & (ww != 0)
+            idx = np.where(live, yy * W + xx, 0).astype(np.int64)
+            for b in range(B):
+                np.add.at(tot[b], idx[b][live[b]], g[b][live[b]] * ww[b][live[b]][:, None])
+                np.add.at(cnt[b], idx[b][live[b]], 1.0)
+        out.append((tot.transpose(0, 2, 1).reshape(B, C, H, W), cnt.reshape(B, 1, H, W)))
+        c0 += C
+    return out
 
 
 # ----------------------------------------------------------------------------- comparison
