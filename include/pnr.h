@@ -36,7 +36,9 @@ extern "C" {
                                   * pnr_views_to_tensor_u8; the training draws, pnr_train_draw; the fused launch's work split as a
                                   * host diagnostic, pnr_debug_point_split; the colour-jitter augmentation of 8-bit batches,
                                   * pnr_color_jitter_workspace_bytes / pnr_color_jitter_plan / pnr_train_batch_u8_jitter /
-                                  * pnr_views_to_tensor_u8_jitter */
+                                  * pnr_views_to_tensor_u8_jitter; the data-parallel training step — an object base in the keyed
+                                  * draws and a divisor folded into the optimiser, pnr_train_draw_at / pnr_color_jitter_plan_at /
+                                  * pnr_adam_step_div */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -682,6 +684,15 @@ int32_t pnr_train_batch_u8_jitter(const uint8_t* images_u8, const float* poses, 
 int32_t pnr_views_to_tensor_u8_jitter(const uint8_t* images_u8, const int64_t* view_ord, int32_t SB, int32_t NV, int32_t NS,
                                       int32_t W, int32_t H, int32_t C, int32_t balanced, float* out,
                                       const float* jitter /* (SB, 8) */, void* stream);
+/* pnr_color_jitter_plan_at: the plan of a SLICE of a step's batch.  The call's object o is object obj_base + o of the step: its
+ * record is drawn with the counter (lo32(obj_base + o), hi32(obj_base + o), 10, block), everything else — the bytes read, the
+ * grey mean (which depends on the object's bytes and its record alone), the row written — is the call's own object o.  The
+ * records of objects [k, k + m) under obj_base = k are therefore rows k .. k + m - 1 of the whole batch's plan, bit for bit.
+ * pnr_color_jitter_plan is this call with obj_base 0.  Checks and codes as above, and
+ *   PNR_E_SHAPE  obj_base < 0 or obj_base + SB past int64 */
+int32_t pnr_color_jitter_plan_at(const uint8_t* images_u8, int32_t SB, int32_t NV, int32_t W, int32_t H, int32_t C,
+                                 const float* ranges /* HOST, 4 */, uint64_t seed, int64_t obj_base, float* record_out /* (SB, 8) */,
+                                 void* workspace, uint64_t ws_bytes, void* stream);
 
 /* ---- training draws on the device, csrc/train_draw.hip ---------------------------------------------------------------------------
  * pnr_train_draw: the pixels a training step samples and the source views it encodes (train/train.py:268-300: per object
@@ -713,6 +724,15 @@ int32_t pnr_views_to_tensor_u8_jitter(const uint8_t* images_u8, const int64_t* v
 int32_t pnr_train_draw(const float* bbox /* (SB, NV, 4) cmin rmin cmax rmax, or NULL */, int32_t SB, int32_t NV, int32_t W,
                        int32_t H, int64_t B, int32_t NS, uint64_t seed, int64_t* pix_inds_out /* (SB, B) */,
                        int64_t* view_ord_out /* (SB, NS), NULL iff NS == 0 */, void* stream);
+/* pnr_train_draw_at: the draws of a SLICE of a step's batch, for a step whose objects are split over several callers (the ranks
+ * of a data-parallel run).  The call's object o is object obj_base + o of the step and only the counters see it:
+ *   pixel (o, j)        r = (obj_base + o) * B + j, an int64, in place of o * B + j
+ *   views of object o   counter index obj_base + o in place of o
+ * bbox, pix_inds_out and view_ord_out are the call's own SB rows.  The outputs of objects [k, k + m) under obj_base = k are rows
+ * k .. k + m - 1 of the whole batch's call, bit for bit; pnr_train_draw is this call with obj_base 0.  Checks and codes as above, and
+ *   PNR_E_SHAPE  obj_base < 0, or obj_base + SB or (obj_base + SB) * B past int64 */
+int32_t pnr_train_draw_at(const float* bbox, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B, int32_t NS, uint64_t seed,
+                          int64_t obj_base, int64_t* pix_inds_out, int64_t* view_ord_out, void* stream);
 
 /* Mesh extraction (util/recon.py: marching_cubes, with util.gen_grid util.py:98-115 and PyMCubes behind it), csrc/mesh.hip.
  *
@@ -826,6 +846,20 @@ int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_segments, con
                       double lr, double beta1, double beta2, double eps, double max_norm,
                       const pnr_optim_scaler* scaler /* host, or NULL */, pnr_optim_state* state,
                       void* workspace, uint64_t workspace_bytes, void* stream);
+/* pnr_adam_step_div: the step of a gradient buffer that holds the SUM over grad_div ranks (one all-reduce over the flat buffer)
+ * where the mean is meant.  With inv_div = 1.0f / (float)grad_div, rounded once on the host, the gradient enters everything as
+ *     u = (grad * inv_scale) * inv_div            two separately rounded fp32 products
+ * the norm is sqrt(sum u^2), found_inf is set by a non-finite u, and g = u * clip_coef in the element's arithmetic above: the
+ * norm, the clip, the skip and the scaler see the divided gradient, and no pass over the buffer is added.  A power-of-two
+ * grad_div is exact (short of underflow): the step on 2 g with grad_div 2 is the step on g, bit for bit.  grad_div == 1 runs the
+ * kernels WITHOUT the second product — pnr_adam_step is this call with grad_div 1 and keeps its bits.  Checks and codes as
+ * above, and
+ *   PNR_E_SHAPE  grad_div < 1 */
+int32_t pnr_adam_step_div(const pnr_optim_segment* segments, int32_t n_segments, const pnr_optim_chunk* chunks, int64_t n_chunks,
+                          const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n_flat,
+                          double lr, double beta1, double beta2, double eps, double max_norm,
+                          const pnr_optim_scaler* scaler /* host, or NULL */, int32_t grad_div, pnr_optim_state* state,
+                          void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* ---- upstream pixelNeRF's latent map: the tail of its SpatialEncoder.forward, csrc/upsample.hip -------------------------------
  *

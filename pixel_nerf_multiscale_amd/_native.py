@@ -176,10 +176,12 @@ PROTOTYPES = {
     "pnr_views_to_tensor_u8": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp]),
     "pnr_color_jitter_workspace_bytes": (_u64, [_i32, _i32, _i32, _i32]),
     "pnr_color_jitter_plan": (_i32, [_fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float), _u64, _fp, _fp, _u64, _fp]),  # ranges: HOST
+    "pnr_color_jitter_plan_at": (_i32, [_fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float), _u64, _i64, _fp, _fp, _u64, _fp]),
     "pnr_train_batch_u8_jitter": (_i32, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _f, _f, _fp, _i64, _fp, _fp, _i32, _i32, _fp,
                                          _fp]),
     "pnr_views_to_tensor_u8_jitter": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
     "pnr_train_draw": (_i32, [_fp, _i32, _i32, _i32, _i32, _i64, _i32, _u64, _fp, _fp, _fp]),
+    "pnr_train_draw_at": (_i32, [_fp, _i32, _i32, _i32, _i32, _i64, _i32, _u64, _i64, _fp, _fp, _fp]),
     "pnr_grid_points": (_i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _i64, _i64, _i32, _fp, _fp, _fp]),
     "pnr_mc_workspace_bytes": (_u64, [_i32, _i32, _i32]),
     "pnr_mc_count": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, _fp, _u64, _fp, _fp]),
@@ -190,6 +192,8 @@ PROTOTYPES = {
     "pnr_optim_workspace_bytes": (_u64, [_i64]),
     "pnr_adam_step": (_i32, [_fp, _i32, _fp, _i64, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double,
                              C.c_double, C.POINTER(pnr_optim_scaler), _fp, _fp, _u64, _fp]),
+    "pnr_adam_step_div": (_i32, [_fp, _i32, _fp, _i64, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 C.c_double, C.POINTER(pnr_optim_scaler), _i32, _fp, _fp, _u64, _fp]),
     "pnr_upsample_concat": (_i32, [C.POINTER(C.c_void_p), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _fp,
                                    _fp, _i32, _fp]),                       # levels and the size arrays: HOST addresses
     "pnr_upsample_concat_bwd": (_i32, [_fp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32,

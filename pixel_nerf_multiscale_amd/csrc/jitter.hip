@@ -35,14 +35,16 @@ __device__ __forceinline__ JitterRec jitter_draw(uint64_t seed, int64_t o, const
 // Workgroup b: object b / nblk, pixels [PNR_JITTER_BLOCK c, PNR_JITTER_BLOCK (c + 1)) of its NV H W, c = b % nblk.  Round `it`
 // gives thread t the pixels [4 g, 4 g + 4), g = 256 it + t; the loads are load_pixels_u8's (whole dwords when the object's first
 // byte is dword-aligned and the group is whole, else byte by byte: only bytes of this object are touched).  An object whose
-// contrast factor is exactly 1 needs no mean: its workgroups leave at once and their partials are never read.
+// contrast factor is exactly 1 needs no mean: its workgroups leave at once and their partials are never read.  obj_base: the
+// call's object o draws with the counter of object obj_base + o of the step; bytes, partials and records stay the call's rows.
 __global__ void __launch_bounds__(JB_THREADS) k_jitter_partials(const uint8_t* __restrict__ images, int64_t npix, int C, int nblk,
-                                                                JitterRanges rg, uint64_t seed, double* __restrict__ partials) {
+                                                                JitterRanges rg, uint64_t seed, int64_t obj_base,
+                                                                double* __restrict__ partials) {
     __shared__ double s[JB_THREADS];
     const int64_t o = blockIdx.x / (unsigned)nblk;
     const int64_t first = (int64_t)(blockIdx.x - (unsigned)o * (unsigned)nblk) * PNR_JITTER_BLOCK;
     uint32_t code;
-    const JitterRec rec = jitter_draw(seed, o, rg, code);
+    const JitterRec rec = jitter_draw(seed, obj_base + o, rg, code);
     if (rec.contrast == 1.0f) return;                   // the whole workgroup: the draw depends on o alone
     const uint8_t* obj = images + o * npix * C;
     const bool aligned = (((uintptr_t)obj) & 3) == 0;
@@ -71,12 +73,13 @@ __global__ void __launch_bounds__(JB_THREADS) k_jitter_partials(const uint8_t* _
 
 // Workgroup o writes object o's record; with partials it folds the object's nblk of them first (thread t adds partials t,
 // t + 256, .. in that order, then the LDS tree), divides by the pixel count in fp64 and rounds ONCE to fp32.
-__global__ void __launch_bounds__(JB_THREADS) k_jitter_record(JitterRanges rg, uint64_t seed, const double* __restrict__ partials,
-                                                              int nblk, int64_t npix, float* __restrict__ record_out) {
+__global__ void __launch_bounds__(JB_THREADS) k_jitter_record(JitterRanges rg, uint64_t seed, int64_t obj_base,
+                                                              const double* __restrict__ partials, int nblk, int64_t npix,
+                                                              float* __restrict__ record_out) {
     __shared__ double s[JB_THREADS];
     const int64_t o = blockIdx.x;
     uint32_t code;
-    JitterRec rec = jitter_draw(seed, o, rg, code);
+    JitterRec rec = jitter_draw(seed, obj_base + o, rg, code);
     if (partials && rec.contrast != 1.0f) {             // the whole workgroup
         double acc = 0.0;
         for (int k = threadIdx.x; k < nblk; k += JB_THREADS) acc += partials[o * nblk + k];
@@ -108,9 +111,9 @@ extern "C" uint64_t pnr_color_jitter_workspace_bytes(int32_t SB, int32_t NV, int
     return bytes_of([&](Bump& b) { jitter_carve(b, SB, NV, W, H); });
 }
 
-extern "C" int32_t pnr_color_jitter_plan(const uint8_t* images_u8, int32_t SB, int32_t NV, int32_t W, int32_t H, int32_t C,
-                                         const float* ranges, uint64_t seed, float* record_out, void* workspace, uint64_t ws_bytes,
-                                         void* stream) {
+extern "C" int32_t pnr_color_jitter_plan_at(const uint8_t* images_u8, int32_t SB, int32_t NV, int32_t W, int32_t H, int32_t C,
+                                            const float* ranges, uint64_t seed, int64_t obj_base, float* record_out, void* workspace,
+                                            uint64_t ws_bytes, void* stream) {
     if (!ranges || !record_out) return PNR_E_NULL;
     JitterRanges rg;
     for (int k = 0; k < 4; ++k) {
@@ -118,6 +121,7 @@ extern "C" int32_t pnr_color_jitter_plan(const uint8_t* images_u8, int32_t SB, i
         if (!(rg.v[k] >= 0.0f && rg.v[k] <= (k == 3 ? 0.5f : 1.0f))) return PNR_E_SHAPE;      // NaN fails too
     }
     if ((C != 3 && C != 4) || !batch_shape_ok(SB, NV, W, H, 0)) return PNR_E_SHAPE;
+    if (obj_base < 0 || obj_base > 0x7fffffffffffffffLL - SB) return PNR_E_SHAPE;           // the last counter stays inside int64
     const bool reduce = rg.v[1] != 0.0f;                // a contrast range of 0: every factor is exactly 1, no mean is needed
     const int64_t nblk = jitter_blocks(NV, W, H), npix = (int64_t)NV * H * W;
     double* partials = nullptr;
@@ -129,13 +133,19 @@ extern "C" int32_t pnr_color_jitter_plan(const uint8_t* images_u8, int32_t SB, i
         Bump ws(workspace);
         partials = jitter_carve(ws, SB, NV, W, H);
         hipLaunchKernelGGL(k_jitter_partials, dim3((unsigned)(SB * nblk)), dim3(JB_THREADS), 0, (hipStream_t)stream, images_u8, npix, C,
-                           (int)nblk, rg, seed, partials);
+                           (int)nblk, rg, seed, obj_base, partials);
         PNR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_jitter_record, dim3((unsigned)SB), dim3(JB_THREADS), 0, (hipStream_t)stream, rg, seed,
+    hipLaunchKernelGGL(k_jitter_record, dim3((unsigned)SB), dim3(JB_THREADS), 0, (hipStream_t)stream, rg, seed, obj_base,
                        (const double*)partials, (int)nblk, npix, record_out);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
+}
+
+extern "C" int32_t pnr_color_jitter_plan(const uint8_t* images_u8, int32_t SB, int32_t NV, int32_t W, int32_t H, int32_t C,
+                                         const float* ranges, uint64_t seed, float* record_out, void* workspace, uint64_t ws_bytes,
+                                         void* stream) {
+    return pnr_color_jitter_plan_at(images_u8, SB, NV, W, H, C, ranges, seed, 0, record_out, workspace, ws_bytes, stream);
 }
 
 extern "C" int32_t pnr_train_batch_u8_jitter(const uint8_t* images_u8, const float* poses, const float* focal, const float* c,

@@ -60,11 +60,13 @@ __device__ __forceinline__ float inv_scale_of(const pnr_optim_state* st, int use
 
 // Element e of a chunk belongs to thread (e / 4) % 256, which visits its elements in ascending order: 16 fp64 additions per
 // thread, then the 8 levels of block_sum_or.  The order depends on the element's place in its chunk alone — the 16-byte and
-// the scalar loads feed the same additions.
+// the scalar loads feed the same additions.  DIV (pnr_adam_step_div with grad_div > 1): the gradient is a SUM over grad_div ranks
+// and every use of it is ((grad * inv_scale) * inv_div); without DIV the multiply is not compiled in.
+template <bool DIV>
 __global__ void __launch_bounds__(OPT_THREADS) k_grad_sumsq(const pnr_optim_segment* __restrict__ segs, int n_segs,
                                                             const pnr_optim_chunk* __restrict__ chunks, int64_t n_chunks,
                                                             const float* __restrict__ grad, int64_t n_flat,
-                                                            const pnr_optim_state* __restrict__ st, int use_scaler,
+                                                            const pnr_optim_state* __restrict__ st, int use_scaler, float inv_div,
                                                             double* __restrict__ part, int32_t* __restrict__ flag) {
     __shared__ double red[OPT_THREADS];
     __shared__ int redb[OPT_THREADS];
@@ -90,7 +92,8 @@ __global__ void __launch_bounds__(OPT_THREADS) k_grad_sumsq(const pnr_optim_segm
             }
 #pragma unroll
             for (int k = 0; k < OPT_VEC; ++k) {
-                const float u = x[k] * inv;               // rounded to fp32, as unscale_ leaves it
+                float u = x[k] * inv;                     // rounded to fp32, as unscale_ leaves it
+                if (DIV) u = u * inv_div;
                 bad |= finite_f(u) ? 0 : 1;
                 const double d = (double)u;
                 acc += d * d;                             // the square of an fp32 value is exact in fp64
@@ -157,10 +160,13 @@ __global__ void __launch_bounds__(OPT_THREADS) k_optim_reduce(const double* __re
     }
 }
 
-struct AdamConsts { float beta1, one_minus_beta1, beta2, one_minus_beta2, eps, inv_scale, clip_coef, step_size, rsqrt_bc2; };
+struct AdamConsts { float beta1, one_minus_beta1, beta2, one_minus_beta2, eps, inv_scale, clip_coef, step_size, rsqrt_bc2, inv_div; };
 
+template <bool DIV>
 __device__ __forceinline__ void adam_elem(float grad, float& m, float& v, float& p, const AdamConsts& k) {
-    const float g = (grad * k.inv_scale) * k.clip_coef;
+    float g = grad * k.inv_scale;
+    if (DIV) g = g * k.inv_div;
+    g = g * k.clip_coef;
     m = k.beta1 * m + k.one_minus_beta1 * g;
     v = k.beta2 * v + (k.one_minus_beta2 * g) * g;
     const float denom = __fsqrt_rn(v) * k.rsqrt_bc2 + k.eps;
@@ -171,6 +177,7 @@ __device__ __forceinline__ void adam_elem(float grad, float& m, float& v, float&
 // 16-byte aligned (every chunk of a tensor torch allocated); a view that starts inside its storage takes the scalar body, and
 // so does the last, partial quad of a segment.  Plain stores: m, v and p are read again next step and nothing else is
 // between, so there is no reason to steer them past the L2.
+template <bool DIV>
 __global__ void __launch_bounds__(OPT_THREADS) k_adam_apply(const pnr_optim_segment* __restrict__ segs, int n_segs,
                                                             const pnr_optim_chunk* __restrict__ chunks, int64_t n_chunks,
                                                             const float* __restrict__ grad, float* __restrict__ exp_avg,
@@ -197,10 +204,10 @@ __global__ void __launch_bounds__(OPT_THREADS) k_adam_apply(const pnr_optim_segm
                 float4 mq = *reinterpret_cast<const float4*>(m + e);
                 float4 vq = *reinterpret_cast<const float4*>(v + e);
                 float4 pq = *reinterpret_cast<const float4*>(p + e);
-                adam_elem(gq.x, mq.x, vq.x, pq.x, k);
-                adam_elem(gq.y, mq.y, vq.y, pq.y, k);
-                adam_elem(gq.z, mq.z, vq.z, pq.z, k);
-                adam_elem(gq.w, mq.w, vq.w, pq.w, k);
+                adam_elem<DIV>(gq.x, mq.x, vq.x, pq.x, k);
+                adam_elem<DIV>(gq.y, mq.y, vq.y, pq.y, k);
+                adam_elem<DIV>(gq.z, mq.z, vq.z, pq.z, k);
+                adam_elem<DIV>(gq.w, mq.w, vq.w, pq.w, k);
                 *reinterpret_cast<float4*>(m + e) = mq;
                 *reinterpret_cast<float4*>(v + e) = vq;
                 *reinterpret_cast<float4*>(p + e) = pq;
@@ -209,7 +216,7 @@ __global__ void __launch_bounds__(OPT_THREADS) k_adam_apply(const pnr_optim_segm
                 for (int q = 0; q < OPT_VEC; ++q)
                     if (e + q < cv.n) {
                         float mm = m[e + q], vv = v[e + q], pp = p[e + q];
-                        adam_elem(g[e + q], mm, vv, pp, k);
+                        adam_elem<DIV>(g[e + q], mm, vv, pp, k);
                         m[e + q] = mm; v[e + q] = vv; p[e + q] = pp;
                     }
             }
@@ -257,11 +264,12 @@ extern "C" uint64_t pnr_optim_workspace_bytes(int64_t n_chunks) {
     return bytes_of([&](Bump& b) { carve_optim(b, n_chunks); });
 }
 
-extern "C" int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_segments, const pnr_optim_chunk* chunks,
-                                 int64_t n_chunks, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n_flat,
-                                 double lr, double beta1, double beta2, double eps, double max_norm,
-                                 const pnr_optim_scaler* scaler, pnr_optim_state* state, void* workspace,
-                                 uint64_t workspace_bytes, void* stream) {
+extern "C" int32_t pnr_adam_step_div(const pnr_optim_segment* segments, int32_t n_segments, const pnr_optim_chunk* chunks,
+                                     int64_t n_chunks, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n_flat,
+                                     double lr, double beta1, double beta2, double eps, double max_norm,
+                                     const pnr_optim_scaler* scaler, int32_t grad_div, pnr_optim_state* state, void* workspace,
+                                     uint64_t workspace_bytes, void* stream) {
+    if (grad_div < 1) return PNR_E_SHAPE;
     if (n_segments < 0 || n_chunks < 0 || n_flat < 0 || n_chunks >= OPT_MAX_CHUNKS) return PNR_E_SHAPE;
     if (!state) return PNR_E_NULL;
     if (n_chunks > 0 && (!segments || !chunks || !grad || !exp_avg || !exp_avg_sq || !workspace)) return PNR_E_NULL;
@@ -282,9 +290,11 @@ extern "C" int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_se
     const int64_t rounds = (n_chunks + OPT_MAX_GRID - 1) / OPT_MAX_GRID;
     const unsigned grid = (unsigned)((n_chunks + rounds - 1) / rounds);
     hipStream_t s = (hipStream_t)stream;
+    const bool div = grad_div > 1;
+    const float inv_div = 1.0f / (float)grad_div;         // rounded once, here
 
-    hipLaunchKernelGGL(k_grad_sumsq, dim3(grid), dim3(OPT_THREADS), 0, s, segments, (int)n_segments, chunks, n_chunks, grad, n_flat,
-                       (const pnr_optim_state*)state, use_scaler, part, flag);
+    hipLaunchKernelGGL((div ? k_grad_sumsq<true> : k_grad_sumsq<false>), dim3(grid), dim3(OPT_THREADS), 0, s, segments, (int)n_segments,
+                       chunks, n_chunks, grad, n_flat, (const pnr_optim_state*)state, use_scaler, inv_div, part, flag);
     PNR_LAUNCH_CHECK();
 
     ReduceArgs ra;
@@ -301,8 +311,18 @@ extern "C" int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_se
     k.beta2 = (float)beta2; k.one_minus_beta2 = (float)(1.0 - beta2);
     k.eps = (float)eps;
     k.inv_scale = 1.0f; k.clip_coef = 1.0f; k.step_size = 0.0f; k.rsqrt_bc2 = 1.0f;      // read from `state` on the device
-    hipLaunchKernelGGL(k_adam_apply, dim3(grid), dim3(OPT_THREADS), 0, s, segments, (int)n_segments, chunks, n_chunks, grad, exp_avg,
-                       exp_avg_sq, n_flat, (const pnr_optim_state*)state, k);
+    k.inv_div = inv_div;
+    hipLaunchKernelGGL((div ? k_adam_apply<true> : k_adam_apply<false>), dim3(grid), dim3(OPT_THREADS), 0, s, segments, (int)n_segments,
+                       chunks, n_chunks, grad, exp_avg, exp_avg_sq, n_flat, (const pnr_optim_state*)state, k);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
+}
+
+extern "C" int32_t pnr_adam_step(const pnr_optim_segment* segments, int32_t n_segments, const pnr_optim_chunk* chunks,
+                                 int64_t n_chunks, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n_flat,
+                                 double lr, double beta1, double beta2, double eps, double max_norm,
+                                 const pnr_optim_scaler* scaler, pnr_optim_state* state, void* workspace,
+                                 uint64_t workspace_bytes, void* stream) {
+    return pnr_adam_step_div(segments, n_segments, chunks, n_chunks, grad, exp_avg, exp_avg_sq, n_flat, lr, beta1, beta2, eps, max_norm,
+                             scaler, 1, state, workspace, workspace_bytes, stream);
 }

@@ -19,13 +19,15 @@ __device__ __forceinline__ int box_coord(float f) {
 
 // Work items [0, n_pix): pixel (o, j) = i / B, i % B.  Work items [n_pix, n_pix + SB): the NS source views of object i - n_pix
 // (when NS > 0).  The view walk keeps its chosen views ascending in a 64-entry private array (insertion, NS^2 / 4 moves): NS
-// is a handful in training.
+// is a handful in training.  obj_base: the call's object o is object obj_base + o of the step — it enters the two counters and
+// nothing else (boxes and outputs are the call's own rows), so a call over a slice of a batch writes that slice's rows.
 __global__ void __launch_bounds__(256) k_train_draw(const float* __restrict__ bbox, int SB, int NV, int W, int H, int64_t B, int NS,
-                                                    uint64_t seed, int64_t n_pix, int64_t* __restrict__ pix_out,
+                                                    uint64_t seed, int64_t obj_base, int64_t n_pix, int64_t* __restrict__ pix_out,
                                                     int64_t* __restrict__ view_out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_pix) {
-        const u32x4 r = philox4x32(seed, (uint32_t)i, (uint32_t)((uint64_t)i >> 32), DRAW_PIX, 0u);
+        const uint64_t ctr = (uint64_t)(obj_base * B + i);
+        const u32x4 r = philox4x32(seed, (uint32_t)ctr, (uint32_t)(ctr >> 32), DRAW_PIX, 0u);
         const int64_t o = i / B;
         const int view = (int)mulhi(r.x, (uint32_t)NV);
         int cmin = 0, rmin = 0, cmax = W - 1, rmax = H - 1;
@@ -46,8 +48,9 @@ __global__ void __launch_bounds__(256) k_train_draw(const float* __restrict__ bb
     if (NS <= 0 || o >= SB) return;
     int chosen[DRAW_MAX_NS];                             // ascending
     u32x4 r = {0u, 0u, 0u, 0u};
+    const uint64_t ctr = (uint64_t)(obj_base + o);
     for (int s = 0; s < NS; ++s) {
-        if ((s & 3) == 0) r = philox4x32(seed, (uint32_t)o, (uint32_t)((uint64_t)o >> 32), DRAW_VIEWS, (uint32_t)(s >> 2));
+        if ((s & 3) == 0) r = philox4x32(seed, (uint32_t)ctr, (uint32_t)(ctr >> 32), DRAW_VIEWS, (uint32_t)(s >> 2));
         const int w = s & 3;
         const uint32_t word = w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w;
         int t = (int)mulhi(word, (uint32_t)(NV - s));    // the t-th view not chosen yet
@@ -63,16 +66,24 @@ __global__ void __launch_bounds__(256) k_train_draw(const float* __restrict__ bb
 
 using namespace pnr;
 
-extern "C" int32_t pnr_train_draw(const float* bbox, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B, int32_t NS, uint64_t seed,
-                                  int64_t* pix_inds_out, int64_t* view_ord_out, void* stream) {
+extern "C" int32_t pnr_train_draw_at(const float* bbox, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B, int32_t NS,
+                                     uint64_t seed, int64_t obj_base, int64_t* pix_inds_out, int64_t* view_ord_out, void* stream) {
     if (NS < 0 || NS > DRAW_MAX_NS || !batch_shape_ok(SB, NV, W, H, B) || NS > NV) return PNR_E_SHAPE;
     if ((B > 0 && !pix_inds_out) || (NS > 0 && !view_ord_out)) return PNR_E_NULL;
+    // the last pixel counter, (obj_base + SB) * B - 1, and the last view counter stay inside int64
+    constexpr int64_t I64_MAX = 0x7fffffffffffffffLL;
+    if (obj_base < 0 || obj_base > I64_MAX - SB || (B > 0 && obj_base + SB > I64_MAX / B)) return PNR_E_SHAPE;
     if (B == 0 && NS == 0) return PNR_OK;
     const int64_t n_pix = (int64_t)SB * B;
     const int64_t total = n_pix + SB;
     if ((total + 255) / 256 > (((int64_t)1 << 31) - 1)) return PNR_E_SHAPE;                    // one launch: the grid's x extent
     hipLaunchKernelGGL(k_train_draw, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bbox, SB, NV, W, H, B, NS,
-                       seed, n_pix, pix_inds_out, view_ord_out);
+                       seed, obj_base, n_pix, pix_inds_out, view_ord_out);
     PNR_LAUNCH_CHECK();
     return PNR_OK;
+}
+
+extern "C" int32_t pnr_train_draw(const float* bbox, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B, int32_t NS, uint64_t seed,
+                                  int64_t* pix_inds_out, int64_t* view_ord_out, void* stream) {
+    return pnr_train_draw_at(bbox, SB, NV, W, H, B, NS, seed, 0, pix_inds_out, view_ord_out, stream);
 }

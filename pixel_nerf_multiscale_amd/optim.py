@@ -56,7 +56,10 @@ class DeviceAdam(torch.optim.Optimizer):
     step count for all parameters (torch keeps one per parameter, which differ only when a gradient was None for some steps).
 
     grad_norm (fp64), found_inf, scale_value, step_count, skipped are 0-dim device views of the state record: reading one
-    (.item()) is the only wait, and the caller chooses when."""
+    (.item()) is the only wait, and the caller chooses when.
+
+    Data-parallel steps: allreduce(group), in train_step's grad_hook slot, sums the flat gradient buffer over the ranks with
+    ONE collective and arms the next step() to divide by the world size inside its kernels (pnr_adam_step_div)."""
 
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=None, scaler=None):
         params = list(params)
@@ -129,6 +132,7 @@ class DeviceAdam(torch.optim.Optimizer):
         self._seg_n = None                      # what the device tables hold: lengths and parameter addresses
         self._seg_param = None
         self._n_chunks = 0
+        self._grad_div = 1                      # armed by allreduce() for ONE step()
 
         self._scaler_conf = scaler
         self._scaler_arg = None
@@ -227,11 +231,49 @@ class DeviceAdam(torch.optim.Optimizer):
         self._seg_n, self._seg_param = seg_n, seg_param
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def allreduce(self, group=None):
+        """The gradient exchange of a data-parallel step, for train_step's grad_hook slot: every rank holds the gradient of
+        its share of the batch (each a mean over its own rays) and leaves with their sum; the step that follows divides by the
+        world size inside its kernels, so the mean costs no pass of its own.
+          * a gradient that was replaced (p.grad = other) is copied into its slice and p.grad pointed back, as step() does;
+          * a parameter whose .grad is None gets its slice, zeroed: every rank then steps the same segments, whichever of them
+            reached the parameter in its backward;
+          * ONE dist.all_reduce(SUM) over the whole flat gradient buffer (SUM, not AVG: every backend has it);
+          * the next step() — that one only — runs with grad_div = the group's size.  Norm, clip, found_inf and the scaler read
+            the same reduced buffer on every rank, so they agree with no further collective.
+        group: a ProcessGroup, or None for the default group.  With no initialised group, or a group of one rank, no collective
+        is issued and the divisor stays 1: the step's bits are those of a plain step."""
+        import torch.distributed as dist
+        world = 1
+        if dist.is_available() and dist.is_initialized():
+            world = dist.get_world_size(group)
+        for i, p in enumerate(self._params):
+            g = p.grad
+            if g is None:
+                if world > 1:
+                    self._slices[i].zero_()
+                    p.grad = self._slices[i]
+            elif g.data_ptr() != self._slice_ptr[i] or g.dtype != torch.float32 or not g.is_contiguous():
+                if g.shape != p.shape or g.device != self._dev:
+                    raise ValueError(f"parameter {i}: replaced .grad has shape {tuple(g.shape)} on {g.device}")
+                self._slices[i].copy_(g)
+                p.grad = self._slices[i]
+        if world > 1:
+            dist.all_reduce(self._grad, op=dist.ReduceOp.SUM, group=group)
+        self._grad_div = world
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_div=None):
+        """grad_div: the gradient buffer holds a sum over that many ranks (pnr_adam_step_div); None: what allreduce() armed
+        for this step, 1 otherwise."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        armed, self._grad_div = self._grad_div, 1
+        grad_div = armed if grad_div is None else int(grad_div)
+        if grad_div < 1:
+            raise ValueError(f"grad_div must be >= 1, got {grad_div}")
         seg_n = np.empty(len(self._params), dtype=np.int64)
         seg_param = np.empty(len(self._params), dtype=np.uint64)
         for i, p in enumerate(self._params):
@@ -254,14 +296,14 @@ class DeviceAdam(torch.optim.Optimizer):
         g = self.param_groups[0]
         N = self._N
         max_norm = g.get("max_norm")
-        rc = N.lib.pnr_adam_step(self._tables.data_ptr(), len(self._params), self._tables.data_ptr() + self._seg_bytes,
-                                 self._n_chunks, self._grad.data_ptr(), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
-                                 self._n_flat, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                 0.0 if max_norm is None else float(max_norm),
-                                 None if self._scaler_arg is None else C.byref(self._scaler_arg),
-                                 self._state_buf.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(),
-                                 N.current_stream(self._dev))
-        N.check(rc, "pnr_adam_step")
+        rc = N.lib.pnr_adam_step_div(self._tables.data_ptr(), len(self._params), self._tables.data_ptr() + self._seg_bytes,
+                                     self._n_chunks, self._grad.data_ptr(), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
+                                     self._n_flat, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                     0.0 if max_norm is None else float(max_norm),
+                                     None if self._scaler_arg is None else C.byref(self._scaler_arg), int(grad_div),
+                                     self._state_buf.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(),
+                                     N.current_stream(self._dev))
+        N.check(rc, "pnr_adam_step_div")
         return loss
 
     # ------------------------------------------------------------------------------------------------ checkpoints

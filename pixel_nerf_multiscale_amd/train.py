@@ -17,7 +17,7 @@ def curr_nviews_for(nviews, seed):
 
 
 def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=True, is_train=True, balanced=True,
-               draws="host", seed=None, jitter=None):
+               draws="host", seed=None, jitter=None, obj_base=0):
     """The front end of calc_losses (train/train.py:243-317): host draws, ONE upload of the (SB, ray_batch_size) pixel
     indices (the source-view choice rides in the same buffer) and one of the intrinsics, both from pinned memory, one launch
     for the rays and colours, and the source views picked on the device.
@@ -42,9 +42,19 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
     the operations, the object's grey mean over all its views), and the two gathers apply it to the sampled pixels and the
     chosen source views only: no host read and no further upload.  The record depends on (seed) and the bytes alone, so
     checkpoints need nothing new.  A float batch or draws="host" with jitter raises ValueError; is_train=False ignores it;
-    None makes the calls made without it."""
+    None makes the calls made without it.
+
+    obj_base (draws="device" only; ValueError with host draws): `data` holds objects obj_base .. obj_base + SB - 1 of the
+    step's batch — a rank's share of a data-parallel step.  The pixel draw, the view draw and the jitter record of its object
+    o are keyed as object obj_base + o (pnr_train_draw_at, pnr_color_jitter_plan_at), so the six outputs are rows
+    obj_base .. obj_base + SB - 1 of the whole batch's outputs, bit for bit."""
     if draws not in ("host", "device"):
         raise ValueError(f"draws must be 'host' or 'device', got {draws!r}")
+    obj_base = int(obj_base)
+    if obj_base != 0 and draws != "device":
+        raise ValueError("obj_base needs draws='device': only the keyed draws can place a slice inside its step's batch")
+    if obj_base < 0:
+        raise ValueError(f"obj_base must be >= 0, got {obj_base}")
     if draws == "device" and seed is None:
         raise ValueError("draws='device' needs seed, the per-step key: parallel.frame_seed(base_seed, global_step)")
     as_bytes = data["images"].dtype == torch.uint8
@@ -71,8 +81,8 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
         if boxes is not None:
             boxes = boxes.to(device=device, dtype=torch.float32)
         pix_inds, image_ord = util.train_draw(boxes, SB, NV, W, H, B, curr_nviews_for(nviews, seed), seed,
-                                              out_pix=torch.empty(SB, B, dtype=torch.long, device=device))
-        record = None if jitter is None else util.color_jitter_plan(all_images, jitter, seed)
+                                              out_pix=torch.empty(SB, B, dtype=torch.long, device=device), obj_base=obj_base)
+        record = None if jitter is None else util.color_jitter_plan(all_images, jitter, seed, obj_base=obj_base)
         return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced, record)
 
     all_bboxes = data.get("bbox") if (is_train and use_bbox) else None
@@ -129,7 +139,7 @@ def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_ne
 
 
 def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far, loss, use_bbox=True, is_train=True,
-                balanced=True, draws="host", seed=None, jitter=None):
+                balanced=True, draws="host", seed=None, jitter=None, obj_base=0):
     """One batch of the data loader -> (loss, loss_dict), ready for loss.backward().
 
     net          PixelNeRFNet (on the device)
@@ -148,6 +158,9 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
                  the device, which consume neither global generator
     jitter       None, or a data.ColorJitter: the colour augmentation of make_batch (8-bit batch, draws="device", training
                  only — is_train=False ignores it)
+    obj_base     draws="device" only: `data` is the slice [obj_base, obj_base + SB) of the step's batch (make_batch), and the
+                 render runs with the renderer's ray_index_base = obj_base * ray_batch_size, so its keyed noise is that of
+                 those rays of the whole batch's render.  The loss is the mean over the slice's own rays.
 
     loss_dict has "rc", "rf" (only with a fine pass) and "t".  Unlike the reference, which returns Python floats (three
     .item() calls, i.e. three host synchronisations per step), each value is a 0-dim view of ONE 3-float device buffer:
@@ -163,10 +176,15 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     dev = net.poses.device
     all_rays, all_rgb_gt, src_images, src_poses, focal, c = make_batch(
         data, dev, ray_batch_size=ray_batch_size, nviews=nviews, z_near=z_near, z_far=z_far, use_bbox=use_bbox, is_train=is_train,
-        balanced=balanced, draws=draws, seed=seed, jitter=jitter)
+        balanced=balanced, draws=draws, seed=seed, jitter=jitter, obj_base=obj_base)
     net.encode(src_images, src_poses, focal, c=c)
 
-    render_dict = render_par(all_rays, want_weights=True)
+    if obj_base:
+        rend = render_par.renderer
+        with rend.keyed(rend.forced_seed, base=int(obj_base) * int(ray_batch_size)):
+            render_dict = render_par(all_rays, want_weights=True)
+    else:
+        render_dict = render_par(all_rays, want_weights=True)
     total, stats = loss(render_dict, all_rgb_gt)
     loss_dict = {"rc": stats[0]}
     fine = render_dict.get("fine")
@@ -183,7 +201,9 @@ def train_step(net, render_par, data, optim, *, grad_hook=None, **calc_losses_kw
     optim        optim.DeviceAdam: unscale, clip_grad_norm_, the found-inf skip, Adam and the scaler's update are its step()
     grad_hook    called with no arguments between backward and the step — the place for
                  parallel.allreduce_gradients(params); a gradient it replaces is re-adopted by optim.step()
-    the rest     calc_losses' keywords (ray_batch_size, nviews, z_near, z_far, loss, use_bbox, is_train, jitter)
+                 — and for optim.allreduce, DeviceAdam's own all-reduce of its flat gradient buffer (one collective; the
+                 mean's divide is folded into the step)
+    the rest     calc_losses' keywords (ray_batch_size, nviews, z_near, z_far, loss, use_bbox, is_train, jitter, obj_base)
 
     -> calc_losses' loss_dict with "grad_norm" added (the fp64 norm of the unscaled gradients before clipping, what
     clip_grad_norm_ returns): 0-dim device views, like the others.  Nothing in here waits for the device; whether the step

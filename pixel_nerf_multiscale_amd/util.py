@@ -326,18 +326,28 @@ def _jitter_record(jitter, SB):
     return jitter.contiguous()
 
 
-def color_jitter_plan(images_u8, ranges, seed, out=None):
+def _obj_base(obj_base):
+    """The first object of a call over a slice of a step's batch, as the keyed kernels take it."""
+    obj_base = int(obj_base)
+    if not 0 <= obj_base < 1 << 63:
+        raise ValueError(f"obj_base must be a non-negative int64, got {obj_base}")
+    return obj_base
+
+
+def color_jitter_plan(images_u8, ranges, seed, out=None, obj_base=0):
     """The colour-jitter records of one step (pnr_color_jitter_plan; include/pnr.h writes the arithmetic down): per object of
     the uint8 batch images_u8 (SB, NV, H, W, 3 | 4) on the device, one brightness / contrast / saturation factor and hue shift
     inside `ranges` (four host floats, or a data.ColorJitter), the order of the four operations, and — where contrast takes
     part — the object's grey mean over ALL its views, all keyed by `seed` alone (the per-step key).  -> float32 (SB, 8) on the
     device: [brightness, contrast, saturation, hue, mean, order code, 0, 0], what train_batch_u8 / views_to_tensor_u8 take as
-    `jitter`.  Reads nothing back; `out` (SB, 8) float32 contiguous is filled when given."""
+    `jitter`.  Reads nothing back; `out` (SB, 8) float32 contiguous is filled when given.
+    obj_base: images_u8 holds objects obj_base .. obj_base + SB - 1 of the step's batch (pnr_color_jitter_plan_at): the records
+    are those rows of the whole batch's plan, bit for bit."""
     from . import _native as N
     import ctypes
     images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
     ranges = tuple(float(r) for r in getattr(ranges, "ranges", ranges))
-    seed = int(seed)
+    seed, obj_base = int(seed), _obj_base(obj_base)
     if len(ranges) != 4:
         raise ValueError(f"ranges must be (brightness, contrast, saturation, hue), got {ranges}")
     if not 0 <= seed < 1 << 64:
@@ -348,8 +358,8 @@ def color_jitter_plan(images_u8, ranges, seed, out=None):
         raise ValueError("out must be contiguous")
     nbytes = int(N.lib.pnr_color_jitter_workspace_bytes(SB, NV, W, H)) if ranges[1] != 0.0 else 0
     ws = N.scratch(nbytes, dev)
-    N.check(N.lib.pnr_color_jitter_plan(N.ptr(images_u8), SB, NV, W, H, C, (ctypes.c_float * 4)(*ranges), seed, N.ptr(rec),
-                                        ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_color_jitter_plan")
+    N.check(N.lib.pnr_color_jitter_plan_at(N.ptr(images_u8), SB, NV, W, H, C, (ctypes.c_float * 4)(*ranges), seed, obj_base,
+                                           N.ptr(rec), ws.data_ptr(), nbytes, N.current_stream(dev)), "pnr_color_jitter_plan_at")
     return rec
 
 
@@ -412,16 +422,19 @@ def views_to_tensor_u8(images_u8, view_ord, balanced=True, jitter=None):
     return out
 
 
-def train_draw(bbox, SB, NV, W, H, B, NS, seed, out_pix=None, out_views=None):
+def train_draw(bbox, SB, NV, W, H, B, NS, seed, out_pix=None, out_views=None, obj_base=0):
     """The draws of one training step on the device (pnr_train_draw; include/pnr.h writes the arithmetic down): B pixels per
     object — a uniform view, then a uniform cell of its box, or of the whole image when bbox is None — and an ordered
     subset of NS of its NV views, all keyed by `seed` alone (the caller's per-step key, parallel.frame_seed(base, step)).
     bbox (SB, NV, 4) = cmin, rmin, cmax, rmax float32 on the device, or None; out_pix (SB, B) / out_views (SB, NS) int64 on
     the device are filled when given (out_pix names the device when there are no boxes), else allocated on bbox's device or
     the current one.  -> (pix_inds, view_ord) for train_batch / train_batch_u8 / views_to_tensor_u8 / batched_index_select_nd.
-    An invalid box (NaN, inverted, outside the image) gives index -1, a NaN row downstream.  Reads nothing back."""
+    An invalid box (NaN, inverted, outside the image) gives index -1, a NaN row downstream.  Reads nothing back.
+    obj_base: the call draws objects obj_base .. obj_base + SB - 1 of the step's batch (pnr_train_draw_at; bbox and the outputs
+    are those SB objects' rows): what it writes are those rows of the whole batch's draw, bit for bit."""
     from . import _native as N
     SB, NV, W, H, B, NS, seed = int(SB), int(NV), int(W), int(H), int(B), int(NS), int(seed)
+    obj_base = _obj_base(obj_base)
     if not 0 <= seed < 1 << 64:
         raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
     if SB < 1 or NV < 1 or W < 1 or H < 1 or B < 0:
@@ -441,8 +454,8 @@ def train_draw(bbox, SB, NV, W, H, B, NS, seed, out_pix=None, out_views=None):
     dev = N.same_device(*given) if given else torch.device("cuda", torch.cuda.current_device())
     pix = torch.empty(SB, B, dtype=torch.long, device=dev) if out_pix is None else out_pix
     views = torch.empty(SB, NS, dtype=torch.long, device=dev) if out_views is None else out_views
-    N.check(N.lib.pnr_train_draw(N.dptr(bbox), SB, NV, W, H, B, NS, seed, pix.data_ptr() if B else None,
-                                 views.data_ptr() if NS else None, N.current_stream(dev)), "pnr_train_draw")
+    N.check(N.lib.pnr_train_draw_at(N.dptr(bbox), SB, NV, W, H, B, NS, seed, obj_base, pix.data_ptr() if B else None,
+                                    views.data_ptr() if NS else None, N.current_stream(dev)), "pnr_train_draw_at")
     return pix, views
 
 

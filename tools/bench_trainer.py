@@ -8,13 +8,20 @@ encoder), three ways, and train.make_batch alone to a synchronise under both kin
 The host-draw rows run make_batch as it was before the `draws` keyword, so they are the baseline.  Every configuration trains
 the same number of epochs after one warm-up epoch; no checkpoint, validation or picture falls into the timed part.  Prints one
 JSON line.
-    python tools/bench_trainer.py --epochs 3"""
+    python tools/bench_trainer.py --epochs 3
+
+--ranks N (at most 8) measures the data-parallel loop instead: the resident_device configuration under
+Trainer(data_parallel=True), once with 1 rank and once with N, each in a torch.distributed.run of its own that this script starts
+under a time limit of its own (one process per card; the global batch --sb must divide by N).  It needs N cards: on a machine that
+shows fewer it prints "not measured: one card" and measures nothing.
+    python tools/bench_trainer.py --ranks 8 --sb 8 --objects 32"""
 import argparse
 import contextlib
 import io
 import json
 import os
 import statistics
+import subprocess
 import sys
 import tempfile
 import time
@@ -40,6 +47,78 @@ def write_tree(root, n_obj, nv, size):
         dt.write_srn_object(os.path.join(root, "cars_train", "obj%03d" % o), images, poses, 131.25, size / 2, size / 2, stems)
 
 
+MAX_RANKS = 8
+RANK_RUN_SECONDS = 600         # the time limit of ONE torch.distributed.run of --ranks
+
+
+def rank_worker(a):
+    """One rank of --ranks (started by torch.distributed.run): resident_device under Trainer(data_parallel=True); rank 0 prints
+    the steps per second of the timed epochs as one JSON line."""
+    import torch.distributed as dist
+    from pixel_nerf_multiscale_amd import NeRFRenderer, PixelNeRFNet, train
+    from pixel_nerf_multiscale_amd.data import ResidentSplit, get_split_dataset
+    from pixel_nerf_multiscale_amd.model.loss import RenderLoss
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    dist.init_process_group("nccl", device_id=dev)
+    try:
+        dataset = get_split_dataset("srn", os.path.join(a.worker, "cars"), want_split="train", as_bytes=True)
+        torch.manual_seed(0)
+        net = PixelNeRFNet(model_conf(dict(gu.CASES["full_ns1"]), "fp32")).to(dev)
+        net.train_precision = a.precision
+        rend = NeRFRenderer(n_coarse=64, n_fine=32, n_fine_depth=16, white_bkgd=True).to(dev)
+        never = 10 ** 9
+        t = train.Trainer(net, rend, ResidentSplit(dataset, dev, device_boxes=True), None, name="ranks",
+                          checkpoints_path=os.path.join(a.worker, "ckpt"), logs_path=os.path.join(a.worker, "logs"), batch_size=a.sb,
+                          ray_batch_size=a.rays, nviews=a.views, loss=RenderLoss(1.0, 1.0), num_epochs=1 + a.epochs, draws="device",
+                          seed=3, print_interval=never, save_interval=never, eval_interval=never, vis_interval=never,
+                          data_parallel=True)
+        with contextlib.redirect_stdout(io.StringIO()):
+            t.train_epoch(0)
+            torch.cuda.synchronize()
+            dist.barrier()
+            t0 = time.perf_counter()
+            for epoch in range(1, 1 + a.epochs):
+                t.train_epoch(epoch)
+            torch.cuda.synchronize()
+            dist.barrier()
+        if dist.get_rank() == 0:
+            print(json.dumps({"ranks": dist.get_world_size(), "steps_per_s": round(a.epochs * t.batches_per_epoch / (time.perf_counter() - t0), 3)}),
+                  flush=True)
+    finally:
+        dist.destroy_process_group()
+
+
+def measure_ranks(a):
+    """--ranks: this process never opens a card; it counts them, writes the tree and starts one torch.distributed.run per world
+    size, each under its own time limit."""
+    n = min(int(a.ranks), MAX_RANKS)
+    cards = torch.cuda.device_count()
+    if cards < 2 or n < 2:
+        print("not measured: one card", flush=True)
+        return
+    if cards < n:
+        print(f"not measured: {n} ranks asked for, {cards} cards", flush=True)
+        return
+    if a.sb % n != 0:
+        raise SystemExit(f"--sb {a.sb} does not divide over {n} ranks")
+    res = {"what": "trainer_ranks", "sb": a.sb, "nv": a.nv, "objects": a.objects, "rays_per_obj": a.rays, "views": a.views,
+           "precision": a.precision, "epochs": a.epochs, "steps_per_epoch": a.objects // a.sb}
+    with tempfile.TemporaryDirectory() as tmp:
+        write_tree(tmp, a.objects, a.nv, 128)
+        for world in (1, n):
+            cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--nproc_per_node", str(world), os.path.abspath(__file__),
+                   "--worker", tmp, "--sb", str(a.sb), "--rays", str(a.rays), "--epochs", str(a.epochs), "--precision", a.precision,
+                   "--views", *[str(v) for v in a.views]]
+            done = subprocess.run(cmd, capture_output=True, text=True, timeout=RANK_RUN_SECONDS)
+            if done.returncode != 0:
+                raise SystemExit(f"{world} ranks: exit status {done.returncode}\n{done.stderr[-2000:]}")
+            line = next(l for l in reversed(done.stdout.splitlines()) if l.startswith("{"))
+            res[f"steps_per_s_{world}_ranks"] = json.loads(line)["steps_per_s"]
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sb", type=int, default=4)
@@ -50,7 +129,13 @@ def main():
     ap.add_argument("--epochs", type=int, default=3, help="timed epochs per configuration, after one warm-up epoch")
     ap.add_argument("--rounds", type=int, default=20, help="make_batch calls per kind of draw")
     ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16", "bf16x3"])
+    ap.add_argument("--ranks", type=int, default=0, help=f"measure the data-parallel loop at 1 and N <= {MAX_RANKS} ranks instead (needs N cards)")
+    ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)      # a rank of --ranks: the tree's folder
     a = ap.parse_args()
+    if a.worker:
+        return rank_worker(a)
+    if a.ranks:
+        return measure_ranks(a)
 
     from pixel_nerf_multiscale_amd import NeRFRenderer, PixelNeRFNet, train
     from pixel_nerf_multiscale_amd.data import ResidentSplit, get_split_dataset
