@@ -38,7 +38,7 @@ extern "C" {
                                   * pnr_color_jitter_workspace_bytes / pnr_color_jitter_plan / pnr_train_batch_u8_jitter /
                                   * pnr_views_to_tensor_u8_jitter; the data-parallel training step — an object base in the keyed
                                   * draws and a divisor folded into the optimiser, pnr_train_draw_at / pnr_color_jitter_plan_at /
-                                  * pnr_adam_step_div */
+                                  * pnr_adam_step_div; area resampling of images, pnr_resize_area_u8 / pnr_resize_area_f32 */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -904,6 +904,48 @@ int32_t pnr_upsample_concat_bwd(const float* d_out,           /* (N, sumC, H_0, 
                                 int32_t n_levels, int32_t n_maps,
                                 float* const* d_levels,       /* WRITTEN (=), not accumulated; a NULL entry is skipped */
                                 void* stream);
+
+/* ---- area resampling of images, csrc/resize.hip ---------------------------------------------------------------------------------
+ *
+ * Upstream pixelNeRF brings its float images to another image_size with F.interpolate(mode="area"), which is
+ * adaptive_avg_pool2d: a target sample is the mean of the source samples under its window.  This text is the specification.
+ *
+ * Window of target index i on an axis with n_in source and n_out target samples, ALL in integer arithmetic (64-bit products):
+ *     lo(i) = floor(i n_in / n_out),   hi(i) = ceil((i + 1) n_in / n_out),   source indices lo(i) .. hi(i) - 1
+ * A window is never empty and never leaves the axis.  Windows overlap when n_in / n_out is not an integer; n_out > n_in
+ * (upsampling: windows of one or two samples) and n_out == n_in (every window is its own sample: a copy) are ordinary cases,
+ * not special paths.  The window of a pixel is rows lo(y) .. hi(y) - 1 (H, Ht) by columns lo(x) .. hi(x) - 1 (W, Wt), n pixels.
+ *
+ * pnr_resize_area_u8: interleaved bytes (F, H, W, C) -> (F, Ht, Wt, C), C = 1..4, every channel kept and treated alike.
+ *     S = the exact integer sum of the window's n bytes of that channel;  out = (2 S + n) / (2 n), integer division:
+ *     the exact mean rounded to the nearest byte, a tie (fraction exactly .5) rounded UP.  An all-255 window gives 255.
+ *   Accumulator: 64 unsigned bits.  S <= 255 n < 2^39 and 2 S + n < 2^41 for every window the size checks admit (n <= H W <
+ *   2^31), so no admitted shape can overflow it.
+ *   Frame f of the input starts at in_u8 + f in_stride, of the output at out_u8 + f out_stride (BYTES; a dense stack has the
+ *   strides H W C and Ht Wt C), so a view is written straight into its slot of a pool; inside a frame both are dense.  Both
+ *   may start at ANY byte; loads and stores are byte-wide.  The bytes between two output frames are not touched.  Input and
+ *   output must not overlap.
+ *     PNR_E_NULL   in_u8 or out_u8 NULL
+ *     PNR_E_SHAPE  F, H, W, Ht or Wt < 1; H W >= 2^31 or Ht Wt >= 2^31; C outside 1..4; in_stride < H W C or out_stride <
+ *                  Ht Wt C; F frames of ceil(Ht Wt / 256) workgroups each that do not fit one launch (2^31 - 1 workgroups)
+ *
+ * pnr_resize_area_f32: fp32 planes (F, H, W) -> (F, Ht, Wt), both dense; F counts PLANES (the caller folds views x channels).
+ *     acc = 0.0 (fp64);  for every row of the window, top to bottom, for every column, left to right:  acc = acc + (double)v;
+ *     out = (float)(acc / (double)n): one IEEE fp64 division, then ONE rounding to fp32 (to nearest even).
+ *   A NaN or an Inf poisons exactly the windows that contain it (Inf and -Inf in one window give NaN), no other.
+ *     PNR_E_NULL   in or out NULL
+ *     PNR_E_SHAPE  F, H, W, Ht or Wt < 1; H W >= 2^31 or Ht Wt >= 2^31; planes x workgroups past one launch, as above
+ *     PNR_E_ALIGN  in or out not 4-byte aligned
+ *
+ * Both are asynchronous on `stream`, make every check before the launch (one launch each), need no workspace, use no atomics
+ * and read nothing back; a thread owns one target pixel and sums its window in the order above, so the same input gives the
+ * same bits.  Checked on the CPU against torch's fp64 F.interpolate(mode="area") (tests/test_resize_cpu.py).  NOT pinned:
+ * upstream's own loader end to end (its box and focal scaling differ on purpose: util.resize_bbox / util.resize_intrinsics). */
+int32_t pnr_resize_area_u8(const uint8_t* in_u8 /* (F, H, W, C), any byte alignment */, int64_t in_stride /* bytes per frame */,
+                           int32_t F, int32_t H, int32_t W, int32_t C, uint8_t* out_u8 /* (F, Ht, Wt, C), any byte alignment */,
+                           int64_t out_stride /* bytes per frame */, int32_t Ht, int32_t Wt, void* stream);
+int32_t pnr_resize_area_f32(const float* in /* (F, H, W) */, int32_t F, int32_t H, int32_t W, float* out /* (F, Ht, Wt) */,
+                            int32_t Ht, int32_t Wt, void* stream);
 
 /* Timing hook for bench.py: microseconds between the first and last point-MLP launch of the most recent
  * pnr_render on this thread is NOT kept (no global state); instead the caller brackets calls with

@@ -198,6 +198,8 @@ PROTOTYPES = {
                                    _fp, _i32, _fp]),                       # levels and the size arrays: HOST addresses
     "pnr_upsample_concat_bwd": (_i32, [_fp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32,
                                        C.POINTER(C.c_void_p), _fp]),
+    "pnr_resize_area_u8": (_i32, [_fp, _i64, _i32, _i32, _i32, _i32, _fp, _i64, _i32, _i32, _fp]),
+    "pnr_resize_area_f32": (_i32, [_fp, _i32, _i32, _i32, _fp, _i32, _i32, _fp]),
     "pnr_event_create": (_i32, [C.POINTER(C.c_void_p)]),
     "pnr_event_record": (_i32, [_fp, _fp]),
     "pnr_event_elapsed_ms": (_i32, [_fp, _fp, C.POINTER(C.c_float)]),

@@ -11,13 +11,19 @@ Items come in two modes.  as_bytes=False (the default) is what evaluate, evaluat
 float32 images (NV, 3, H, W).  as_bytes=True is for train.calc_losses: uint8 images (NV, H, W, 3), a quarter of the bytes,
 converted on the device only where a step needs them (util.train_batch_u8, util.views_to_tensor_u8) to the bits the float
 item holds.
+
+Another image_size.  The dataset classes read what the files hold and refuse a foreign image_size; the resampling
+(upstream's F.interpolate(mode="area")) is done on the device instead: ResidentSplit(image_size=...) builds its pool at the
+new size, and ResizedDataset wraps any dataset so that its items come at that size (util.resize_area_u8, util.resize_area,
+util.resize_bbox, util.resize_intrinsics).
 """
 from .dtu import ColorJitter, DTUDataset
 from .dvr import DVRDataset
 from .resident import ResidentSplit
+from .resized import ResizedDataset
 from .srn import SRNDataset
 
-__all__ = ["get_split_dataset", "SRNDataset", "DVRDataset", "DTUDataset", "ColorJitter", "ResidentSplit"]
+__all__ = ["get_split_dataset", "SRNDataset", "DVRDataset", "DTUDataset", "ColorJitter", "ResidentSplit", "ResizedDataset"]
 
 
 def get_split_dataset(dataset_type, datadir, want_split="all", training=True, **kwargs):

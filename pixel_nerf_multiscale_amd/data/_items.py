@@ -27,12 +27,14 @@ def mask_bbox(mask, path):
 
 
 def check_image_size(image_size, H, W, path):
-    """image_size None or the files' own (H, W); anything else would need area resampling, which is out of scope."""
+    """image_size None or the files' own (H, W): a dataset reads what the files hold.  Area resampling to another size is done
+    on the device, by ResidentSplit(image_size=...) and ResizedDataset."""
     if image_size is None:
         return
     want = (int(image_size), int(image_size)) if np.isscalar(image_size) else tuple(int(s) for s in image_size)
     if want != (H, W):
-        raise NotImplementedError(f"image_size {want} differs from the files' {(H, W)} ({path}): resampling is not implemented")
+        raise NotImplementedError(f"image_size {want} differs from the files' {(H, W)} ({path}): resampling is not implemented "
+                                  "in the dataset classes; use data.ResidentSplit(image_size=...) or data.ResizedDataset")
 
 
 def images_to_float(images_u8, balanced):

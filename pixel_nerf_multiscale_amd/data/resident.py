@@ -19,9 +19,16 @@ class ResidentSplit:
     unchanged.
 
     A dataset whose items carry no "bbox" (DTUDataset on scans without masks) is taken too: self.bbox is None and batch() has
-    no "bbox" key, so the draws cover the whole image; device_boxes=True on such a dataset raises ValueError."""
+    no "bbox" key, so the draws cover the whole image; device_boxes=True on such a dataset raises ValueError.
 
-    def __init__(self, dataset, device, max_bytes=None, device_boxes=False):
+    image_size=(Ht, Wt) (or an int) other than the items' own size builds the pool at that size, (N, NV, Ht, Wt, 3): each
+    object's bytes are uploaded to ONE reused staging buffer and util.resize_area_u8 (area resampling, the exact window mean
+    rounded to the nearest byte) writes them into the object's slot; max_bytes is judged on the resized pool; the boxes come
+    through util.resize_bbox and focal / c through util.resize_intrinsics (both differ from upstream's float scaling on
+    purpose: see there).  batch() and batches() keep their form.  With None or the items' own size nothing changes, not a
+    bit.  data.ResizedDataset gives evaluation and validation the same resolution."""
+
+    def __init__(self, dataset, device, max_bytes=None, device_boxes=False, image_size=None):
         if not getattr(dataset, "as_bytes", False):
             raise ValueError("ResidentSplit needs a dataset built with as_bytes=True")
         N = len(dataset)
@@ -37,29 +44,42 @@ class ResidentSplit:
             images = item["images"]
             if i == 0:
                 NV, H, W, C = (int(s) for s in images.shape)
-                nbytes = N * NV * H * W * C
+                Ht, Wt = (H, W) if image_size is None else util._target_size(image_size)
+                if min(Ht, Wt) < 1:
+                    raise ValueError(f"image_size must be positive, got {(Ht, Wt)}")
+                resized = (Ht, Wt) != (H, W)
+                nbytes = N * NV * Ht * Wt * C
                 if max_bytes is not None and nbytes > max_bytes:
                     raise ValueError(f"the split needs a pool of {nbytes} bytes, above max_bytes = {max_bytes}")
-                self.images = torch.empty(N, NV, H, W, C, dtype=torch.uint8, device=self.device)
+                self.images = torch.empty(N, NV, Ht, Wt, C, dtype=torch.uint8, device=self.device)
                 self.poses = torch.empty(N, NV, 4, 4, dtype=torch.float32, device=self.device)
+                staging = torch.empty(NV, H, W, C, dtype=torch.uint8, device=self.device) if resized else None
             elif tuple(images.shape) != (NV, H, W, C):
                 raise ValueError(f"{item['path']}: images {tuple(images.shape)}, the objects before it {(NV, H, W, C)}; "
                                  "a resident pool needs one shape")
-            self.images[i].copy_(images)
+            if resized:
+                staging.copy_(images)       # stream order: the resize of the object before it has read the buffer by then
+                util.resize_area_u8(staging, (Ht, Wt), out=self.images[i])
+            else:
+                self.images[i].copy_(images)
             self.poses[i].copy_(item["poses"])
             self.paths.append(item["path"])
             if i > 0 and ("bbox" in item) != bool(bbox):
                 raise ValueError(f"{item['path']}: {'' if 'bbox' in item else 'no '}boxes, unlike the objects before it")
+            item_focal, item_c = torch.as_tensor(item["focal"], dtype=torch.float32), item.get("c")
+            if resized:
+                item_focal, item_c = util.resize_intrinsics(item_focal, item_c, (H, W), (Ht, Wt))
             if "bbox" in item:
-                bbox.append(item["bbox"])
-            focal.append(torch.as_tensor(item["focal"], dtype=torch.float32))
-            c.append(item.get("c"))
+                bbox.append(util.resize_bbox(item["bbox"], (H, W), (Ht, Wt)) if resized else item["bbox"])
+            focal.append(item_focal)
+            c.append(item_c)
         if device_boxes and not bbox:
             raise ValueError("device_boxes=True needs a dataset whose items have a 'bbox'")
         self.bbox = torch.stack(bbox) if bbox else None
         self.focal = torch.stack(focal)
         self.c = None if c[0] is None else torch.stack(c)
         self.bbox_dev = util.upload(self.bbox.to(torch.float32).contiguous(), self.device) if device_boxes else None
+        self.image_size = (Ht, Wt)
 
     def __len__(self):
         return len(self.paths)

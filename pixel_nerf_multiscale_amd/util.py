@@ -854,3 +854,125 @@ def image_to_tensor(img_u8, balanced=False, device="cuda"):
     N.check(N.lib.pnr_image_to_tensor(img_u8.data_ptr(), W, H, int(bool(balanced)), out.data_ptr(), N.current_stream(dev)),
             "pnr_image_to_tensor")
     return out
+
+
+# ------------------------------------------------------------------------------------------- area resampling to an image_size
+def _target_size(size):
+    """(Ht, Wt) of a `size` argument: a pair, or one int for a square target."""
+    if isinstance(size, (int, np.integer)):
+        return int(size), int(size)
+    size = tuple(int(s) for s in size)
+    if len(size) != 2:
+        raise ValueError(f"size must be (Ht, Wt) or an int, got {size}")
+    return size
+
+
+def _resize_out(out, shape, dtype, dev):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {dtype} {tuple(shape)}, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def resize_area_u8(images_u8, size, out=None):
+    """8-bit images at another size, by area resampling on the GPU by libpnr_hip (pnr_resize_area_u8; include/pnr.h writes the
+    arithmetic down): images_u8 (..., H, W, C) uint8 on the device, C = 1..4 and any leading dimensions — (H, W, C),
+    (NV, H, W, C), (N, NV, H, W, C) — -> (..., Ht, Wt, C) uint8.  A target byte is the exact mean of the source bytes under its
+    window [floor(i n_in / n_out), ceil((i + 1) n_in / n_out)) per axis — the windows of F.interpolate(mode="area"), which
+    upstream pixelNeRF applies to its float images — rounded to the nearest byte, a tie up.  Every channel is kept; a mask is
+    the C = 1 case.  The target may be larger than the source, or equal to it (a copy).  size: (Ht, Wt), or an int for a square
+    target.  out: a contiguous uint8 tensor of the result's shape to write into, at any byte offset of a larger buffer (a
+    pool's slot).  Nothing here waits for the device."""
+    from . import _native as N
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() < 3 or not 1 <= images_u8.shape[-1] <= 4:
+        raise ValueError(f"images_u8 must be uint8 (..., H, W, 1..4), got {getattr(images_u8, 'dtype', None)} "
+                         f"{tuple(getattr(images_u8, 'shape', ()))}")
+    Ht, Wt = _target_size(size)
+    images_u8 = images_u8.contiguous()
+    lead = tuple(int(s) for s in images_u8.shape[:-3])
+    H, W, C = (int(s) for s in images_u8.shape[-3:])
+    F = math.prod(lead)
+    dev = N.same_device(images_u8, out)
+    out = _resize_out(out, lead + (Ht, Wt, C), torch.uint8, dev)
+    N.check(N.lib.pnr_resize_area_u8(images_u8.data_ptr(), H * W * C, F, H, W, C, out.data_ptr(), Ht * Wt * C, Ht, Wt,
+                                     N.current_stream(dev)), "pnr_resize_area_u8")
+    return out
+
+
+def resize_area(images, size, out=None):
+    """Float images at another size, by area resampling on the GPU by libpnr_hip (pnr_resize_area_f32): images (..., H, W)
+    float32 on the device, any leading dimensions (views, channels) -> (..., Ht, Wt) float32, each value the mean of its
+    window (resize_area_u8's windows) summed in fp64 and rounded to fp32 once — F.interpolate(mode="area") to within one fp32
+    rounding.  A NaN or Inf reaches exactly the windows that contain it.  size and out as for resize_area_u8 (out float32).
+    Nothing here waits for the device."""
+    from . import _native as N
+    if not torch.is_tensor(images) or images.dtype != torch.float32 or images.dim() < 2:
+        raise ValueError(f"images must be float32 (..., H, W), got {getattr(images, 'dtype', None)} "
+                         f"{tuple(getattr(images, 'shape', ()))}")
+    Ht, Wt = _target_size(size)
+    images = images.contiguous()
+    lead = tuple(int(s) for s in images.shape[:-2])
+    H, W = int(images.shape[-2]), int(images.shape[-1])
+    dev = N.same_device(images, out)
+    out = _resize_out(out, lead + (Ht, Wt), torch.float32, dev)
+    N.check(N.lib.pnr_resize_area_f32(images.data_ptr(), math.prod(lead), H, W, out.data_ptr(), Ht, Wt, N.current_stream(dev)),
+            "pnr_resize_area_f32")
+    return out
+
+
+def _sizes(src, dst):
+    (H, W), (Ht, Wt) = _target_size(src), _target_size(dst)
+    if min(H, W, Ht, Wt) < 1:
+        raise ValueError(f"image sizes must be positive, got {(H, W)} -> {(Ht, Wt)}")
+    return H, W, Ht, Wt
+
+
+def resize_bbox(bbox, src_size, dst_size):
+    """Boxes (..., 4) = cmin, rmin, cmax, rmax (whole numbers, corners included) of images (H, W) = src_size, at
+    (Ht, Wt) = dst_size after area resampling, on the host in integer arithmetic:
+        cmin' = floor(cmin Wt / W),   cmax' = ceil((cmax + 1) Wt / W) - 1,   the rows with H, Ht in the same way
+    — exactly the box of the mask "a target pixel is foreground when ANY source pixel under its window is".  -> float32, a
+    tensor for a tensor and an array for an array, like _items.mask_bbox.
+    A deliberate difference from upstream pixelNeRF, which multiplies the boxes by the ROW scale as floats (fractional corners,
+    and the wrong columns when the two scales differ)."""
+    H, W, Ht, Wt = _sizes(src_size, dst_size)
+    is_tensor = torch.is_tensor(bbox)
+    b = np.asarray(bbox.cpu() if is_tensor else bbox)
+    if b.shape[-1:] != (4,):
+        raise ValueError(f"bbox must be (..., 4), got {b.shape}")
+    q = b.astype(np.int64)
+    if not np.array_equal(q, b):
+        raise ValueError("bbox must hold whole numbers")
+    n_in = np.array([W, H, W, H], dtype=np.int64)
+    n_out = np.array([Wt, Ht, Wt, Ht], dtype=np.int64)
+    lo = (q * n_out) // n_in
+    hi = -((-(q + 1) * n_out) // n_in) - 1
+    res = np.where(np.array([True, True, False, False]), lo, hi).astype(np.float32)
+    return torch.from_numpy(res) if is_tensor else res
+
+
+def resize_intrinsics(focal, c, src_size, dst_size):
+    """The intrinsics of images (H, W) = src_size at (Ht, Wt) = dst_size: sx = Wt / W, sy = Ht / H.  focal — a float, or a
+    tensor that is one focal length per entry, or (..., 2) = (fx, fy) — keeps its form and is multiplied by sx when
+    sx == sy; otherwise it becomes (..., 2) = (fx sx, fy sy) float32.  c (..., 2) becomes (cx sx, cy sy); None stays None (the
+    default centre scales to the centre).  The products are made in fp64 and rounded once.  -> (focal, c).
+    A tensor whose LAST dimension is 2 is read as (fx, fy) pairs.
+    Deliberate differences from upstream pixelNeRF: it uses the row scale alone for everything; like upstream, the half-pixel
+    shift of c under pixel-centre-at-integer coordinates is ignored."""
+    H, W, Ht, Wt = _sizes(src_size, dst_size)
+    sx, sy = Wt / W, Ht / H
+    if c is not None:
+        ct = torch.as_tensor(c)
+        if ct.shape[-1:] != (2,):
+            raise ValueError(f"c must be (..., 2), got {tuple(ct.shape)}")
+        c = (ct.double() * torch.tensor([sx, sy], dtype=torch.float64, device=ct.device)).to(ct.dtype if ct.is_floating_point() else torch.float32)
+    if not torch.is_tensor(focal):
+        if Wt * H == Ht * W:
+            return float(focal) * sx, c
+        focal = torch.tensor(float(focal), dtype=torch.float32)
+    dtype = focal.dtype if focal.is_floating_point() else torch.float32
+    if Wt * H == Ht * W:
+        return (focal.double() * sx).to(dtype), c
+    pair = focal if focal.shape[-1:] == (2,) else torch.stack((focal, focal), dim=-1)
+    return (pair.double() * torch.tensor([sx, sy], dtype=torch.float64, device=pair.device)).to(dtype), c
