@@ -38,7 +38,8 @@ extern "C" {
                                   * pnr_color_jitter_workspace_bytes / pnr_color_jitter_plan / pnr_train_batch_u8_jitter /
                                   * pnr_views_to_tensor_u8_jitter; the data-parallel training step — an object base in the keyed
                                   * draws and a divisor folded into the optimiser, pnr_train_draw_at / pnr_color_jitter_plan_at /
-                                  * pnr_adam_step_div; area resampling of images, pnr_resize_area_u8 / pnr_resize_area_f32 */
+                                  * pnr_adam_step_div; area resampling of images, pnr_resize_area_u8 / pnr_resize_area_f32; empty-space
+                                  * culling, pnr_occ_build / pnr_ray_bounds_workspace_bytes / pnr_ray_bounds / pnr_frame_from_hits */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -946,6 +947,83 @@ int32_t pnr_resize_area_u8(const uint8_t* in_u8 /* (F, H, W, C), any byte alignm
                            int64_t out_stride /* bytes per frame */, int32_t Ht, int32_t Wt, void* stream);
 int32_t pnr_resize_area_f32(const float* in /* (F, H, W) */, int32_t F, int32_t H, int32_t W, float* out /* (F, Ht, Wt) */,
                             int32_t Ht, int32_t Wt, void* stream);
+
+/* ---- empty-space culling in front of the render launch, csrc/occupancy.hip ------------------------------------------------------
+ *
+ * The render launch evaluates every sample of every ray it is given.  These three calls give it fewer: a bit grid of the cells
+ * of a box that hold density, each frame's rays reduced to the ORDERED list of those that pass through such a cell, with
+ * [near, far] (ray columns 6:8) tightened to the occupied stretch, and the gather that puts the rendered list back into a
+ * frame.  The reference has no counterpart.  This text is the specification; tests/occupancy_util.py restates it in numpy.
+ *
+ * The grid.  Samples on the lattice of pnr_grid_points, (nx, ny, nz), every axis >= 2; cells (cx, cy, cz) = (nx - 1, ny - 1,
+ * nz - 1), cell (i, j, k) between samples i .. i + 1, j .. j + 1, k .. k + 1.  Bit k & 31 of the uint32 word
+ * (i cy + j) wz + (k >> 5), wz = ceil(cz / 32), says cell (i, j, k) is occupied; the padding bits k >= cz of a last word are 0.
+ *
+ * pnr_occ_build: element p = (i ny + j) nz + k of the field is read at field[p * stride], as pnr_mc_count reads it.
+ *     hot sample     !((double)f < thresh): f >= thresh, or f is NaN.  Conservative, the opposite of marching cubes' inside.
+ *                    (thresh = -inf makes every sample hot, thresh = NaN too.)
+ *     raw-occupied   a cell with at least one hot corner sample among its 8
+ *     occupied       a cell with a raw-occupied cell within `dilate` cells of it in Chebyshev distance (max over the axes),
+ *                    dilate = 0 .. 4; cells outside the grid do not exist
+ *     accumulate     != 0: the new words are ORed into those `bits` holds (several view-direction sets, or two MLPs, as one
+ *                    grid); 0: `bits` is overwritten, padding included
+ *   One thread owns one word, no atomics, one launch, no workspace.
+ *     PNR_E_NULL   field or bits NULL
+ *     PNR_E_SHAPE  an axis < 2 or with more than 2^20 cells, stride < 1, dilate outside 0..4, 2^31 samples or words or more
+ *     PNR_E_ALIGN  field or bits not 4-byte aligned
+ *
+ * pnr_ray_bounds: rays (n, 8) = [origin, direction, near, far], frame f = rows f R .. f R + R - 1, R = rays_per_frame, n a
+ * multiple of R.  c1, c2 (the box's corners, doubles) and cells (cx, cy, cz) are HOST arrays of 3.  Host side, per axis a:
+ *     lo = (float)c1, hi = (float)c2, h = (float)((c2 - c1) / cells), inv_h = (float)(cells / (c2 - c1)), the quotients in
+ *     fp64; pad32 = (float)pad.
+ * Per ray, ALL in fp32, every operation rounded on its own (no fused multiply-add), division IEEE; min(a, b) is "b if b < a
+ * else a" and max(a, b) is "b if b > a else a" (so the sign of a zero is settled too):
+ *   1. miss if any of the 8 values is NaN or Inf, if the direction is (0, 0, 0), or if near > far.
+ *   2. t0 = near, t1 = far.  For a = 0, 1, 2 in this order: if d_a == 0 then miss if o_a < lo_a or o_a > hi_a; else
+ *      ta = (lo_a - o_a) / d_a, tb = (hi_a - o_a) / d_a, t0 = max(t0, min(ta, tb)), t1 = min(t1, max(ta, tb)).
+ *      Miss if t0 > t1 (t0 == t1, a ray that touches the box, goes on).
+ *   3. Start cell, per axis: p = o_a + t0 * d_a;  f = floor((p - lo_a) * inv_h_a);  f = min(cells_a - 1, max(0, f));  c_a = (int)f.
+ *      step_a = +1 / -1 / 0 by the sign of d_a.  Boundary b (0 .. cells_a) of an axis lies at B(b) = hi_a for b == cells_a,
+ *      else lo_a + (float)b * h_a.  tmax_a = +inf for step_a == 0, else (B(c_a + (step_a > 0 ? 1 : 0)) - o_a) / d_a —
+ *      recomputed from the boundary index at every step, never accumulated.
+ *   4. hit = false, t_cur = t0.  At most cx + cy + cz + 3 times (a walk changes one index by one per step and cannot be longer;
+ *      the bound holds whatever the floating-point values are):
+ *        tm = min(min(tmax_0, tmax_1), tmax_2);  te = max(min(tm, t1), t_cur)
+ *        if cell c is occupied: on the first such cell t_in = t_cur and hit = true; t_out = te
+ *        stop unless tm < t1
+ *        axis = 0 if tmax_0 <= tmax_1 and tmax_0 <= tmax_2, else 1 if tmax_1 <= tmax_2, else 2
+ *        c_axis += step_axis; stop if it left 0 .. cells_axis - 1; tmax_axis from the new boundary; t_cur = te
+ *   5. miss unless hit.  near' = max(near, t_in - pad32), far' = min(far, t_out + pad32).
+ * So a ray hits iff its clipped segment passes through an occupied cell; t_in is the entry parameter of the first and t_out
+ * the exit parameter of the last one.  Outputs, per frame f with count_f hits:
+ *     rays_out (n, 8)   rows f R .. f R + count_f - 1: the hit rays in ASCENDING ray order, columns 0:6 copied, 6:8 =
+ *                       (near', far'); the rows past the count are not written.  Must not overlap `rays`.
+ *     slot_out (n)      int32: ray i's position in its frame's list, or -1
+ *     counts_out (F)    int64, F = n / R
+ * The order comes from integer scans in a fixed order, as in mesh.hip, no atomics: the result equals a sequential walk over the
+ * rays.  Three launches, nothing read back.  n == 0 returns PNR_OK without a launch.  Every check is made before any launch:
+ *     PNR_E_NULL       any pointer NULL
+ *     PNR_E_SHAPE      n < 0 or >= 2^31, R < 1, n not a multiple of R, too many workgroups for one launch; a cell count < 1 or
+ *                      > 2^20, 2^31 words or more; c1 / c2 not finite, or a box or cell that does not survive the rounding
+ *                      to fp32 (hi <= lo, h <= 0, inv_h not finite); pad negative, NaN or Inf
+ *     PNR_E_WORKSPACE  fewer workspace bytes than pnr_ray_bounds_workspace_bytes(n, R) (about 8 per ray; 0 for bad sizes)
+ *     PNR_E_ALIGN      rays, rays_out or workspace not 16-byte aligned; bits, slot_out not 4-byte, counts_out not 8-byte aligned
+ *
+ * pnr_frame_from_hits: rec holds one record of rec_stride >= 4 floats per row, [r, g, b, depth, ...], frame f's list from row
+ * f R on (what the render launch wrote for rays_out's rows f R .. f R + count_f - 1).  Pixel i of out (n rows of out_stride >=
+ * 4 floats, 4 written): [bg, bg, bg, 0] where slot[i] < 0 (or >= R, which pnr_ray_bounds never writes), else the first four
+ * floats of record (i / R) R + slot[i].  One thread per pixel, one launch.
+ *     PNR_E_NULL   rec, slot or out NULL
+ *     PNR_E_SHAPE  n, R as above; a stride < 4
+ *     PNR_E_ALIGN  a pointer not 4-byte aligned */
+int32_t pnr_occ_build(const float* field, int32_t stride, int32_t nx, int32_t ny, int32_t nz, double thresh, int32_t dilate,
+                      int32_t accumulate, uint32_t* bits, void* stream);
+uint64_t pnr_ray_bounds_workspace_bytes(int64_t n, int64_t rays_per_frame);
+int32_t pnr_ray_bounds(const float* rays, int64_t n, int64_t rays_per_frame, const double* c1, const double* c2,
+                       const int32_t* cells, const uint32_t* bits, double pad, void* workspace, uint64_t workspace_bytes,
+                       float* rays_out, int32_t* slot_out, int64_t* counts_out, void* stream);
+int32_t pnr_frame_from_hits(const float* rec, int32_t rec_stride, const int32_t* slot, int64_t n, int64_t rays_per_frame, float bg,
+                            float* out, int32_t out_stride, void* stream);
 
 /* Timing hook for bench.py: microseconds between the first and last point-MLP launch of the most recent
  * pnr_render on this thread is NOT kept (no global state); instead the caller brackets calls with

@@ -200,6 +200,11 @@ PROTOTYPES = {
                                        C.POINTER(C.c_void_p), _fp]),
     "pnr_resize_area_u8": (_i32, [_fp, _i64, _i32, _i32, _i32, _i32, _fp, _i64, _i32, _i32, _fp]),
     "pnr_resize_area_f32": (_i32, [_fp, _i32, _i32, _i32, _fp, _i32, _i32, _fp]),
+    "pnr_occ_build": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, _i32, _i32, _fp, _fp]),
+    "pnr_ray_bounds_workspace_bytes": (_u64, [_i64, _i64]),
+    "pnr_ray_bounds": (_i32, [_fp, _i64, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _fp, C.c_double,
+                              _fp, _u64, _fp, _fp, _fp, _fp]),                 # c1, c2, cells: HOST arrays
+    "pnr_frame_from_hits": (_i32, [_fp, _i32, _fp, _i64, _i64, _f, _fp, _i32, _fp]),
     "pnr_event_create": (_i32, [C.POINTER(C.c_void_p)]),
     "pnr_event_record": (_i32, [_fp, _fp]),
     "pnr_event_elapsed_ms": (_i32, [_fp, _fp, C.POINTER(C.c_float)]),

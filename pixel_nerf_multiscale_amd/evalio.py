@@ -382,7 +382,7 @@ class _DeviceBackEnd(_BackEnd):
 def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None, eval_view_list=None,
              include_src=False, scale=1.0, multicat=False, gpu_id=None, ray_batch_size=50000, no_compare_gt=False,
              write_compare=False, write_images=True, max_objects=50, z_near=None, z_far=None,
-             verbose=True, seed=None, metrics="host", write_depth=False, depth_png=False, lut=None):
+             verbose=True, seed=None, metrics="host", write_depth=False, depth_png=False, lut=None, occupancy=None):
     """The per-object evaluation loop of the reference (eval/eval.py:186-362) on this package's renderer.
 
     dataset: a sequence of per-object dicts as the reference's datasets yield them (unbatched): "path", "images"
@@ -424,9 +424,22 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
     (the return value is the same everywhere) and rank 0 alone copies bytes out and writes.  A ground truth whose size differs
     from the render's (scale != 1 with comparison) is a ValueError: there is no resampling on the device.
 
+    occupancy (None: everything above, unchanged): a dict of render.occupancy.OccupancyGrid.from_net's keywords
+    (sigma_thresh is required) plus an optional "pad".  The grid is built once per object, after encode, and ALL target
+    views of the object are bounded in one NeRFRenderer.render_frames_bounded call (empty space culled, one host read of the
+    counts per object; see there for the noise) under the seeds the views have without it; the back ends get the frames
+    unchanged.  A ValueError under a process group of several ranks, before anything is written.
+
     finish.txt holds the metrics of the unquantised frames; calc_metrics() recomputes them on the PNGs written here."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
+    if occupancy is not None:
+        from .render import occupancy as occ
+        occ.refuse_sharded("evaluate")
+        if not isinstance(occupancy, dict):
+            raise TypeError("evaluate builds one grid per object: occupancy must be a dict of OccupancyGrid.from_net keywords")
+        if "sigma_thresh" not in occupancy:
+            raise TypeError("occupancy needs sigma_thresh: no default has been measured on a trained model")
     dev = net.poses.device
     z_near = float(getattr(dataset, "z_near", None) if z_near is None else z_near)
     z_far = float(getattr(dataset, "z_far", None) if z_far is None else z_far)
@@ -476,9 +489,16 @@ def evaluate(net, renderer, dataset, output_dir="", *, source="", viewlist=None,
                 obj_seed = frame_seed(base_seed, obj_idx)
                 views = novel.tolist()
                 back.begin(os.path.join(output_dir, obj_name) if writes_files else None, images, tgt_mask, views, H, W)
+                if occupancy is not None and views:
+                    grid, pad = occ.resolve(occupancy, net)
+                    all_rgb, all_depth = renderer._render_frames_bounded(net, poses[views], W, H, focal, z_near, z_far, grid, c, pad,
+                                                                         None, [frame_seed(obj_seed, vi) for vi in views])
                 for i, vi in enumerate(views):
-                    rgb, depth = _render_view(net, renderer, render_par, frame_seed(obj_seed, vi), poses[vi], W, H, focal, c,
-                                              z_near, z_far, ray_batch_size)
+                    if occupancy is not None:
+                        rgb, depth = all_rgb[i], all_depth[i]
+                    else:
+                        rgb, depth = _render_view(net, renderer, render_par, frame_seed(obj_seed, vi), poses[vi], W, H, focal, c,
+                                                  z_near, z_far, ray_batch_size)
                     back.frame(i, vi, rgb, depth)
                 curr_psnr, curr_ssim = back.finish()
                 log.append(obj_name, curr_psnr, curr_ssim, 1)

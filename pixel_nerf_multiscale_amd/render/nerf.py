@@ -344,6 +344,72 @@ class NeRFRenderer(torch.nn.Module):
         lvl = out.fine if self.using_fine else out.coarse
         return lvl.rgb.reshape(height, width, 3), lvl.depth.reshape(height, width)
 
+    def render_frames_bounded(self, net, poses, W, H, focal, z_near, z_far, occupancy, c=None, pad=None, seed=None):
+        """F target views with empty space culled by an occupancy grid (render/occupancy.py): poses (F, 4, 4) camera-to-world
+        on the host, occupancy an OccupancyGrid on the network's device -> rgb (F, H, W, 3), depth (F, H, W) on the device.
+          1. util.gen_rays_device per pose into one (F H W, 8) buffer
+          2. ONE occupancy.ray_bounds call: per frame the ordered list of the rays that pass through an occupied cell, with
+             [near, far] tightened to the occupied stretch and widened by `pad` (None: one cell diagonal)
+          3. ONE host read, of the F counts (occupancy.read_counts) — the only wait; everything else passes under
+             torch.cuda.set_sync_debug_mode("error")
+          4. per frame with a count above 0, the ordinary render call on its list under self.keyed(frame_seed(seed, f))
+             (seed=None: drawn from torch's generator): the fused launch for a PixelNeRFNet, self(net, rays) otherwise; a frame
+             without a hit launches nothing
+          5. ONE pnr_frame_from_hits: a pixel whose ray missed is the background (1 with white_bkgd, else 0) with depth 0.
+        Noise: compact ray j of a frame draws the noise of ray index j, whatever pixel it came from.  A frame is therefore
+        reproducible under its seed, but it is NOT the unbounded frame's bits — except where every ray hits and no bound moves
+        (a full grid around every segment, pad = 0), where it is render_image under that seed bit for bit.
+        Per-sample weights are not offered on this path, and it is not sharded over a process group."""
+        return self._render_frames_bounded(net, poses, W, H, focal, z_near, z_far, occupancy, c, pad, seed, None)
+
+    def _render_frames_bounded(self, net, poses, W, H, focal, z_near, z_far, grid, c, pad, seed, frame_seeds):
+        """render_frames_bounded with the frames' seeds given one by one (frame_seeds, a list of F; None: frame_seed(seed, f))
+        — evalio.evaluate keys a view by its index in the object, not by its place in the call."""
+        from .. import util
+        from ..model.models import PixelNeRFNet
+        from ..parallel import frame_seed
+        from . import occupancy as occ
+        if not isinstance(grid, occ.OccupancyGrid):
+            raise TypeError(f"occupancy must be an OccupancyGrid, got {type(grid).__name__}")
+        if getattr(net, "num_objs", 1) != 1:
+            raise ValueError(f"bounded rendering needs exactly one encoded object, the network holds {net.num_objs}")
+        poses = torch.as_tensor(poses, dtype=torch.float32)
+        if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] < 1:
+            raise ValueError(f"poses must be (F, 4, 4) with F >= 1, got {tuple(poses.shape)}")
+        if poses.is_cuda:
+            poses = poses.cpu()
+        F, W, H = int(poses.shape[0]), int(W), int(H)
+        HW = H * W
+        if frame_seeds is None:
+            seed = util.seed_from_torch() if seed is None else int(seed)
+            frame_seeds = [frame_seed(seed, f) for f in range(F)]
+        elif len(frame_seeds) != F:
+            raise ValueError(f"{len(frame_seeds)} seeds for {F} frames")
+        dev = N.same_device(grid.bits, getattr(net, "poses", None))     # a generic callable has no cameras of its own
+        with torch.no_grad():
+            self._apply_sched()
+            fx, fy, cx, cy = util.intrinsics(focal, c, W, H)          # read once: focal and c may live on the device
+            rays = torch.empty(F * HW, 8, device=dev, dtype=torch.float32)
+            for f in range(F):
+                util.gen_rays_device(poses[f], W, H, (fx, fy), z_near, z_far, c=(cx, cy), out=rays[f * HW:(f + 1) * HW])
+            rays_out, slot, counts = occ.ray_bounds(grid, rays, HW, pad)
+            record = torch.empty(F * HW, 4, device=dev, dtype=torch.float32)
+            fused = isinstance(net, PixelNeRFNet) and not net.wants_grad(net.poses)
+            level = "fine" if self.using_fine else "coarse"
+            for f, count in enumerate(occ.read_counts(counts)):
+                if count <= 0:
+                    continue
+                hits = rays_out[f * HW:f * HW + count]
+                with self.keyed(frame_seeds[f]):
+                    if fused:
+                        self._forward_fused(net, hits[None], False, packed=(record[f * HW:f * HW + count].view(1, count, 4), (level,)))
+                    else:
+                        out = self(net, hits[None])[level]
+                        record[f * HW:f * HW + count, :3] = out.rgb.reshape(count, 3)
+                        record[f * HW:f * HW + count, 3] = out.depth.reshape(count)
+            frames = occ.frame_from_hits(record, slot, HW, 1.0 if self.white_bkgd else 0.0)
+        return frames[:, :3].reshape(F, H, W, 3), frames[:, 3].reshape(F, H, W)
+
     @staticmethod
     def frame_to_host_async(rgb, depth):
         """Asynchronous D2H of a rendered frame into pinned host buffers (instead of the reference's per-chunk

@@ -73,7 +73,7 @@ def quat_path(t_in, quats, scales, n_out):
 
 
 # ----------------------------------------------------------------------------------------------------------- the render
-def render_video(net, renderer, poses, W, H, focal, z_near, z_far, c=None, seed=None):
+def render_video(net, renderer, poses, W, H, focal, z_near, z_far, c=None, seed=None, occupancy=None):
     """poses (F, 4, 4) c2w on the host, rendered from the views `net` has encoded -> (frames_u8 (F, H, W, 3) uint8,
     n_out_of_range 0-dim int64), both on the device.  One fused render launch per pose (pnr_render_camera: the rays are made
     inside the launch), each writing its pixels into its slice of ONE packed (F*H*W, 4) [rgb, depth] record — the mechanism
@@ -81,8 +81,15 @@ def render_video(net, renderer, poses, W, H, focal, z_near, z_far, c=None, seed=
     under parallel.frame_seed(seed, f) (seed=None: drawn from torch's generator), so it is the frame render_image gives
     under that seed.  Nothing here reads the device: the call passes under torch.cuda.set_sync_debug_mode("error").  A model
     that render_image routes through the generic path (not a PixelNeRFNet, several objects) is rendered by render_image
-    frame by frame, which may wait."""
+    frame by frame, which may wait.
+    occupancy (None: everything above, unchanged): an OccupancyGrid, or a dict of OccupancyGrid.from_net's keywords plus an
+    optional "pad", built here from the encoded network — the frames are then NeRFRenderer.render_frames_bounded's (empty
+    space culled, ONE host read of the per-frame counts; see there for the noise) under the same per-frame seeds.  A
+    ValueError under a process group of several ranks."""
     from .model.models import PixelNeRFNet
+    if occupancy is not None:
+        from .render import occupancy as occ
+        occ.refuse_sharded("render_video")
     poses = torch.as_tensor(poses, dtype=torch.float32)
     if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] < 1:
         raise ValueError(f"poses must be (F, 4, 4) with F >= 1, got {tuple(poses.shape)}")
@@ -93,7 +100,11 @@ def render_video(net, renderer, poses, W, H, focal, z_near, z_far, c=None, seed=
     seed = util.seed_from_torch() if seed is None else int(seed)
     dev = net.poses.device
     with torch.no_grad():
-        if isinstance(net, PixelNeRFNet) and net.num_objs == 1 and not net.wants_grad(net.poses):
+        if occupancy is not None:
+            grid, pad = occ.resolve(occupancy, net)
+            rgb = renderer.render_frames_bounded(net, poses, W, H, focal, z_near, z_far, grid, c=c, pad=pad, seed=seed)[0]
+            rgb = rgb.reshape(F * HW, 3)                              # still a view into the (F H W, 4) record
+        elif isinstance(net, PixelNeRFNet) and net.num_objs == 1 and not net.wants_grad(net.poses):
             renderer._apply_sched()
             fx, fy, cx, cy = util.intrinsics(focal, c, W, H)          # read once: focal and c may live on the device
             level = ("fine",) if renderer.using_fine else ("coarse",)
@@ -159,7 +170,7 @@ def _write_frames(frames_dir, frames):
 
 
 def gen_video(net, renderer, data, out_dir, source, num_views=40, elevation=-10.0, radius=0.0, scale=1.0, *, z_near, z_far,
-              path=None, write="png", ensure_resolution=True, subset=0, split="train", fps=30, seed=None):
+              path=None, write="png", ensure_resolution=True, subset=0, split="train", fps=30, seed=None, occupancy=None):
     """The body of eval/gen_video.py for one object.  data: a dataset item — "images" (NV, 3, H, W) in [-1, 1], "poses"
     (NV, 4, 4) c2w, "focal" (float | tensor), optional "c"; source: the list of source views ([-1]: one random view).
     The path is orbit_poses(num_views, elevation, radius) with radius 0 = (z_near + z_far) / 2 (:159-172), or `path`, any
@@ -170,8 +181,12 @@ def gen_video(net, renderer, data, out_dir, source, num_views=40, elevation=-10.
     <out_dir>/video<name>_frames/0000.png .. and <out_dir>/video<name>_view.png (the source views side by side,
     util.view_strip; the reference writes a .jpg through imageio) are written with evalio.write_png, <name> =
     video_name(source, subset, split).  write="gif" adds <out_dir>/video<name>.gif through PIL (parity unpinned against
-    imageio; no mp4 is written).  -> VideoResult."""
+    imageio; no mp4 is written).  occupancy: as render_video takes it; a dict is turned into a grid after the source views
+    are encoded.  -> VideoResult."""
     from .evalio import _render_size, write_png
+    if occupancy is not None:
+        from .render import occupancy as occ
+        occ.refuse_sharded("gen_video")
     if write not in ("png", "gif"):
         raise ValueError(f"write must be 'png' or 'gif', got {write!r}")
     dev = net.poses.device
@@ -203,7 +218,7 @@ def gen_video(net, renderer, data, out_dir, source, num_views=40, elevation=-10.
             net.encode(src_images.unsqueeze(0), torch.as_tensor(data["poses"]).float()[src].to(dev).unsqueeze(0), focal[None].to(dev),
                        c=None if c is None else c.to(dev).unsqueeze(0))
             frames_u8, count = render_video(net, renderer, path, W, H, focal * scale, z_near, z_far,
-                                            c=None if c is None else c * scale, seed=seed)
+                                            c=None if c is None else c * scale, seed=seed, occupancy=occupancy)
             strip = util.view_strip(src_images)
             strip_h = torch.empty(strip.shape, dtype=torch.uint8, pin_memory=True)
             strip_h.copy_(strip, non_blocking=True)               # in front of the frames on the stream: their wait covers it
