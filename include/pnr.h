@@ -39,7 +39,9 @@ extern "C" {
                                   * pnr_views_to_tensor_u8_jitter; the data-parallel training step — an object base in the keyed
                                   * draws and a divisor folded into the optimiser, pnr_train_draw_at / pnr_color_jitter_plan_at /
                                   * pnr_adam_step_div; area resampling of images, pnr_resize_area_u8 / pnr_resize_area_f32; empty-space
-                                  * culling, pnr_occ_build / pnr_ray_bounds_workspace_bytes / pnr_ray_bounds / pnr_frame_from_hits */
+                                  * culling, pnr_occ_build / pnr_ray_bounds_workspace_bytes / pnr_ray_bounds / pnr_frame_from_hits;
+                                  * mask-weighted training draws, pnr_mask_table_build / pnr_train_draw_masked /
+                                  * pnr_train_draw_masked_at */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -734,6 +736,54 @@ int32_t pnr_train_draw(const float* bbox /* (SB, NV, 4) cmin rmin cmax rmax, or 
  *   PNR_E_SHAPE  obj_base < 0, or obj_base + SB or (obj_base + SB) * B past int64 */
 int32_t pnr_train_draw_at(const float* bbox, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B, int32_t NS, uint64_t seed,
                           int64_t obj_base, int64_t* pix_inds_out, int64_t* view_ord_out, void* stream);
+
+/* ---- mask-weighted training draws on the device, csrc/mask_draw.hip ----------------------------------------------------------------
+ * The reference's other pixel sampler, util.masked_sample(masks, num_pix, prop_inside, thresh) (util/util.py:210-222): a fixed
+ * share of an object's rays falls on its foreground, the rest on its background, each uniform over ALL views' pixels of that
+ * kind.  Here: a bit table per object, built once (pnr_mask_table_build), and the step's draws from it keyed like
+ * pnr_train_draw's (pnr_train_draw_masked).  All arithmetic is integer; no atomics; nothing is allocated or read back; every
+ * check runs before any launch.
+ *
+ * pnr_mask_table_build.  Pixel p = (view * H + row) * W + col of object n has its mask byte at
+ * masks_u8[(n * NV * H * W + p) * pix_stride] — pix_stride 1 reads a mask plane, pix_stride 4 with the pointer advanced by 3 an
+ * alpha channel where it lies; any byte alignment.  A pixel is INSIDE iff byte >= thresh, thresh in 1..255 (128: b / 255 >= 0.5,
+ * the reference's thresh = 0.5 on a float mask).  With Wd = ceil(W / 32) and R = NV * H:
+ *   bits_out (N, R, Wd) uint32   bit (col & 31) of word (col >> 5) of row (view * H + row) is set iff the pixel is inside — LSB
+ *                                first; the bits at col >= W are ZERO
+ *   rows_out (N, R + 1) uint32   rows[0] = 0, rows[r + 1] = rows[r] + popcount(row r): rows[R] is the object's inside count, and
+ *                                the outside count before row r is r * W - rows[r], so one prefix serves both populations
+ *   PNR_E_NULL   masks_u8, bits_out or rows_out NULL
+ *   PNR_E_SHAPE  N, NV, H or W < 1, NV * H * W >= 2^31, pix_stride < 1, thresh outside 1..255
+ *   PNR_E_ALIGN  bits_out or rows_out not 4-byte aligned
+ *
+ * pnr_train_draw_masked_at.  The VIEWS are pnr_train_draw_at's own (draw id 9, the same device function): view_ord_out equals
+ * it bit for bit for the same seed, NV, NS and obj_base.  The PIXELS use draw id 11 (0..3 the render samplers', 8 and 9
+ * pnr_train_draw's, 10 the colour jitter's; 4..7 stay free for the render path):
+ *   pixel (o, j), r = (obj_base + o) * B + j:  (x, _, _, _) = philox4x32(seed, lo32(r), hi32(r), 11, 0)
+ *   n_in = rows[o, R], n_out = R * W - n_in.  Slot j < B_inside draws from the inside population, slot j >= B_inside from the
+ *   outside population; a slot whose population is EMPTY draws from the other one with the same x (both cannot be empty).  The
+ *   reference's randint(0, 0) raises there; the device cannot, and a -1 row would make the optimiser skip the object's every step.
+ *   k = mulhi(x, n), n the population's size; the pixel is the k-th of the population in ascending linear index p, all NV views
+ *   pooled: np.flatnonzero(inside.ravel())[k], or np.flatnonzero(~inside.ravel())[k].
+ *   Selection: with cum[r] = rows[o, r] (inside) or r * W - rows[o, r] (outside), both non-decreasing, the row is the LAST r in
+ *   [0, R) with cum[r] <= k — an upper-bound binary search over the R + 1 prefix entries; then the row's Wd words are walked with
+ *   popcounts for the (k - cum[r])-th set bit.  Outside, each word is complemented; the last word is masked to its W & 31 valid
+ *   bits (when W & 31 != 0), so a tail bit is a pixel of neither population.
+ *   pix_inds_out[o, j] = r * W + col.  Whatever the table holds, nothing outside bits[o] / rows[o] is read (the search stays in
+ *   [0, R], the walk in [0, Wd)); a bit that is not found — an inconsistent table — writes -1, a NaN row downstream.
+ * B_inside is the caller's int(B * prop_inside + 0.5) (util.py:214).  pnr_train_draw_masked is the call with obj_base 0.
+ *   Checks and codes of pnr_train_draw_at, and
+ *   PNR_E_SHAPE  B_inside < 0 or B_inside > B
+ *   PNR_E_NULL   bits or rows NULL with B > 0 */
+int32_t pnr_mask_table_build(const uint8_t* masks_u8, int32_t N, int32_t NV, int32_t H, int32_t W, int64_t pix_stride, int32_t thresh,
+                             uint32_t* bits_out /* (N, NV * H, ceil(W / 32)) */, uint32_t* rows_out /* (N, NV * H + 1) */,
+                             void* stream);
+int32_t pnr_train_draw_masked(const uint32_t* bits, const uint32_t* rows, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B,
+                              int64_t B_inside, int32_t NS, uint64_t seed, int64_t* pix_inds_out /* (SB, B) */,
+                              int64_t* view_ord_out /* (SB, NS), NULL iff NS == 0 */, void* stream);
+int32_t pnr_train_draw_masked_at(const uint32_t* bits, const uint32_t* rows, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B,
+                                 int64_t B_inside, int32_t NS, uint64_t seed, int64_t obj_base, int64_t* pix_inds_out,
+                                 int64_t* view_ord_out, void* stream);
 
 /* Mesh extraction (util/recon.py: marching_cubes, with util.gen_grid util.py:98-115 and PyMCubes behind it), csrc/mesh.hip.
  *

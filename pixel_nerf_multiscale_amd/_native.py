@@ -182,6 +182,9 @@ PROTOTYPES = {
     "pnr_views_to_tensor_u8_jitter": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
     "pnr_train_draw": (_i32, [_fp, _i32, _i32, _i32, _i32, _i64, _i32, _u64, _fp, _fp, _fp]),
     "pnr_train_draw_at": (_i32, [_fp, _i32, _i32, _i32, _i32, _i64, _i32, _u64, _i64, _fp, _fp, _fp]),
+    "pnr_mask_table_build": (_i32, [_fp, _i32, _i32, _i32, _i32, _i64, _i32, _fp, _fp, _fp]),
+    "pnr_train_draw_masked": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _u64, _fp, _fp, _fp]),
+    "pnr_train_draw_masked_at": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _u64, _i64, _fp, _fp, _fp]),
     "pnr_grid_points": (_i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _i64, _i64, _i32, _fp, _fp, _fp]),
     "pnr_mc_workspace_bytes": (_u64, [_i32, _i32, _i32]),
     "pnr_mc_count": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, _fp, _u64, _fp, _fp]),

@@ -2,14 +2,9 @@
 // caller's per-step key — instead of drawn on the host from two global generators and uploaded.  include/pnr.h fixes the
 // arithmetic (all integer, so a host model pins it bit for bit); the outputs are the index buffers pnr_train_batch /
 // pnr_train_batch_u8 / pnr_views_to_tensor_u8 already take.  One launch, latency-bound: a step draws some thousand pixels.
-#include "train_batch.h"
+#include "train_draw.h"
 
 namespace pnr {
-
-enum { DRAW_PIX = 8, DRAW_VIEWS = 9 };                  // 0..3 are the render samplers' (pnr_common.h)
-constexpr int DRAW_MAX_NS = 64;
-
-__device__ __forceinline__ uint32_t mulhi(uint32_t x, uint32_t n) { return __umulhi(x, n); }    // (uint64(x) * n) >> 32: in [0, n)
 
 // A box coordinate: the float truncated towards zero.  NaN, inf and anything at or past +-2^31 cannot be a coordinate
 // (W, H < 2^31) and would not survive the conversion: they come back as -1, which the range check below refuses.
@@ -18,9 +13,8 @@ __device__ __forceinline__ int box_coord(float f) {
 }
 
 // Work items [0, n_pix): pixel (o, j) = i / B, i % B.  Work items [n_pix, n_pix + SB): the NS source views of object i - n_pix
-// (when NS > 0).  The view walk keeps its chosen views ascending in a 64-entry private array (insertion, NS^2 / 4 moves): NS
-// is a handful in training.  obj_base: the call's object o is object obj_base + o of the step — it enters the two counters and
-// nothing else (boxes and outputs are the call's own rows), so a call over a slice of a batch writes that slice's rows.
+// (when NS > 0; draw_views, train_draw.h).  obj_base: the call's object o is object obj_base + o of the step — it enters the two
+// counters and nothing else (boxes and outputs are the call's own rows), so a call over a slice of a batch writes that slice's rows.
 __global__ void __launch_bounds__(256) k_train_draw(const float* __restrict__ bbox, int SB, int NV, int W, int H, int64_t B, int NS,
                                                     uint64_t seed, int64_t obj_base, int64_t n_pix, int64_t* __restrict__ pix_out,
                                                     int64_t* __restrict__ view_out) {
@@ -46,20 +40,7 @@ __global__ void __launch_bounds__(256) k_train_draw(const float* __restrict__ bb
     }
     const int64_t o = i - n_pix;
     if (NS <= 0 || o >= SB) return;
-    int chosen[DRAW_MAX_NS];                             // ascending
-    u32x4 r = {0u, 0u, 0u, 0u};
-    const uint64_t ctr = (uint64_t)(obj_base + o);
-    for (int s = 0; s < NS; ++s) {
-        if ((s & 3) == 0) r = philox4x32(seed, (uint32_t)ctr, (uint32_t)(ctr >> 32), DRAW_VIEWS, (uint32_t)(s >> 2));
-        const int w = s & 3;
-        const uint32_t word = w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w;
-        int t = (int)mulhi(word, (uint32_t)(NV - s));    // the t-th view not chosen yet
-        int k = 0;
-        while (k < s && t >= chosen[k]) { ++t; ++k; }    // every chosen c <= t (after the steps before it) pushes t by one
-        for (int m = s; m > k; --m) chosen[m] = chosen[m - 1];
-        chosen[k] = t;
-        view_out[o * NS + s] = t;
-    }
+    draw_views(seed, (uint64_t)(obj_base + o), NV, NS, view_out + o * NS);
 }
 
 }  // namespace pnr
@@ -68,15 +49,11 @@ using namespace pnr;
 
 extern "C" int32_t pnr_train_draw_at(const float* bbox, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B, int32_t NS,
                                      uint64_t seed, int64_t obj_base, int64_t* pix_inds_out, int64_t* view_ord_out, void* stream) {
-    if (NS < 0 || NS > DRAW_MAX_NS || !batch_shape_ok(SB, NV, W, H, B) || NS > NV) return PNR_E_SHAPE;
-    if ((B > 0 && !pix_inds_out) || (NS > 0 && !view_ord_out)) return PNR_E_NULL;
-    // the last pixel counter, (obj_base + SB) * B - 1, and the last view counter stay inside int64
-    constexpr int64_t I64_MAX = 0x7fffffffffffffffLL;
-    if (obj_base < 0 || obj_base > I64_MAX - SB || (B > 0 && obj_base + SB > I64_MAX / B)) return PNR_E_SHAPE;
+    const int32_t rc = draw_args_check(SB, NV, W, H, B, NS, obj_base, pix_inds_out, view_ord_out);
+    if (rc != PNR_OK) return rc;
     if (B == 0 && NS == 0) return PNR_OK;
     const int64_t n_pix = (int64_t)SB * B;
     const int64_t total = n_pix + SB;
-    if ((total + 255) / 256 > (((int64_t)1 << 31) - 1)) return PNR_E_SHAPE;                    // one launch: the grid's x extent
     hipLaunchKernelGGL(k_train_draw, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bbox, SB, NV, W, H, B, NS,
                        seed, obj_base, n_pix, pix_inds_out, view_ord_out);
     PNR_LAUNCH_CHECK();

@@ -26,9 +26,16 @@ class ResidentSplit:
     rounded to the nearest byte) writes them into the object's slot; max_bytes is judged on the resized pool; the boxes come
     through util.resize_bbox and focal / c through util.resize_intrinsics (both differ from upstream's float scaling on
     purpose: see there).  batch() and batches() keep their form.  With None or the items' own size nothing changes, not a
-    bit.  data.ResizedDataset gives evaluation and validation the same resolution."""
+    bit.  data.ResizedDataset gives evaluation and validation the same resolution.
 
-    def __init__(self, dataset, device, max_bytes=None, device_boxes=False, image_size=None):
+    device_masks=True also keeps each object's mask on the card as the bit table of util.mask_table, built while the pool is
+    filled: mask_bits (N, NV * H, ceil(W / 32)) and mask_rows (N, NV * H + 1), int32, and batch() adds "mask_bits" and
+    "mask_rows", their rows gathered on the device: what train.make_batch(draws="device", prop_inside=...) draws from without an
+    upload.  The items' "masks" are uint8 (NV, H, W), inside at >= 128; with image_size they go through util.resize_area_u8
+    first, so a target pixel is inside iff its window's mean is >= 127.5 (the resize rounds a tie up).  A dataset without
+    "masks" raises ValueError; max_bytes is judged on pool + tables.  With the default nothing changes."""
+
+    def __init__(self, dataset, device, max_bytes=None, device_boxes=False, image_size=None, device_masks=False):
         if not getattr(dataset, "as_bytes", False):
             raise ValueError("ResidentSplit needs a dataset built with as_bytes=True")
         N = len(dataset)
@@ -49,11 +56,18 @@ class ResidentSplit:
                     raise ValueError(f"image_size must be positive, got {(Ht, Wt)}")
                 resized = (Ht, Wt) != (H, W)
                 nbytes = N * NV * Ht * Wt * C
+                if device_masks:
+                    R, Wd = NV * Ht, (Wt + 31) // 32
+                    nbytes += 4 * N * (R * Wd + R + 1)
                 if max_bytes is not None and nbytes > max_bytes:
                     raise ValueError(f"the split needs a pool of {nbytes} bytes, above max_bytes = {max_bytes}")
                 self.images = torch.empty(N, NV, Ht, Wt, C, dtype=torch.uint8, device=self.device)
                 self.poses = torch.empty(N, NV, 4, 4, dtype=torch.float32, device=self.device)
                 staging = torch.empty(NV, H, W, C, dtype=torch.uint8, device=self.device) if resized else None
+                if device_masks:
+                    self.mask_bits = torch.empty(N, R, Wd, dtype=torch.int32, device=self.device)
+                    self.mask_rows = torch.empty(N, R + 1, dtype=torch.int32, device=self.device)
+                    mask_staging = torch.empty(NV, H, W, 1, dtype=torch.uint8, device=self.device)
             elif tuple(images.shape) != (NV, H, W, C):
                 raise ValueError(f"{item['path']}: images {tuple(images.shape)}, the objects before it {(NV, H, W, C)}; "
                                  "a resident pool needs one shape")
@@ -62,6 +76,14 @@ class ResidentSplit:
                 util.resize_area_u8(staging, (Ht, Wt), out=self.images[i])
             else:
                 self.images[i].copy_(images)
+            if device_masks:
+                masks = item.get("masks")
+                if masks is None or masks.dtype != torch.uint8 or tuple(masks.shape) != (NV, H, W):
+                    raise ValueError(f"{item['path']}: device_masks=True needs 'masks' as uint8 {(NV, H, W)}, got "
+                                     f"{None if masks is None else (masks.dtype, tuple(masks.shape))}")
+                mask_staging.copy_(masks[..., None])
+                small = util.resize_area_u8(mask_staging, (Ht, Wt)) if resized else mask_staging
+                util.mask_table(small[..., 0], out=(self.mask_bits[i:i + 1], self.mask_rows[i:i + 1]))
             self.poses[i].copy_(item["poses"])
             self.paths.append(item["path"])
             if i > 0 and ("bbox" in item) != bool(bbox):
@@ -80,13 +102,16 @@ class ResidentSplit:
         self.c = None if c[0] is None else torch.stack(c)
         self.bbox_dev = util.upload(self.bbox.to(torch.float32).contiguous(), self.device) if device_boxes else None
         self.image_size = (Ht, Wt)
+        if not device_masks:
+            self.mask_bits = self.mask_rows = None
 
     def __len__(self):
         return len(self.paths)
 
     @property
     def nbytes(self):
-        return self.images.numel()
+        tables = 0 if self.mask_bits is None else 4 * (self.mask_bits.numel() + self.mask_rows.numel())
+        return self.images.numel() + tables
 
     def batch(self, ids):
         """ids: object indices (a sequence or a host int tensor) -> {"path", "img_id", "images" (SB, NV, H, W, 3) uint8 and
@@ -106,6 +131,8 @@ class ResidentSplit:
             data["c"] = self.c[ids]
         if self.bbox_dev is not None:
             data["bbox_dev"] = self.bbox_dev[on_dev]
+        if self.mask_bits is not None:
+            data["mask_bits"], data["mask_rows"] = self.mask_bits[on_dev], self.mask_rows[on_dev]
         return data
 
     def batches(self, batch_size, shuffle=True, generator=None, drop_last=True):

@@ -17,7 +17,7 @@ def curr_nviews_for(nviews, seed):
 
 
 def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=True, is_train=True, balanced=True,
-               draws="host", seed=None, jitter=None, obj_base=0):
+               draws="host", seed=None, jitter=None, obj_base=0, prop_inside=None):
     """The front end of calc_losses (train/train.py:243-317): host draws, ONE upload of the (SB, ray_batch_size) pixel
     indices (the source-view choice rides in the same buffer) and one of the intrinsics, both from pinned memory, one launch
     for the rays and colours, and the source views picked on the device.
@@ -47,7 +47,17 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
     obj_base (draws="device" only; ValueError with host draws): `data` holds objects obj_base .. obj_base + SB - 1 of the
     step's batch — a rank's share of a data-parallel step.  The pixel draw, the view draw and the jitter record of its object
     o are keyed as object obj_base + o (pnr_train_draw_at, pnr_color_jitter_plan_at), so the six outputs are rows
-    obj_base .. obj_base + SB - 1 of the whole batch's outputs, bit for bit."""
+    obj_base .. obj_base + SB - 1 of the whole batch's outputs, bit for bit.
+
+    prop_inside, a number in [0, 1], with is_train and use_bbox: the object's MASK takes the place of its boxes — of an object's
+    ray_batch_size pixels util.num_inside(ray_batch_size, prop_inside) are uniform over its foreground and the rest over its
+    background, all views pooled (the reference's util.masked_sample).  draws="device": the bit table comes from
+    data["mask_bits"] / data["mask_rows"] (data.ResidentSplit(device_masks=True)), else it is built from data["masks"]
+    (uploaded when on the host) by one util.mask_table call, and ONE util.train_draw_masked launch keyed by the seed takes the
+    place of util.train_draw; an object without foreground (or without background) draws every pixel from what it has.
+    draws="host": util.masked_sample per object where util.bbox_sample stood, and such an object raises ValueError.  uint8
+    masks are inside at >= 128, float masks at >= 0.5.  A batch with neither table nor masks raises ValueError; is_train=False
+    or use_bbox=False ignore prop_inside; None (the default) makes the calls made without it."""
     if draws not in ("host", "device"):
         raise ValueError(f"draws must be 'host' or 'device', got {draws!r}")
     obj_base = int(obj_base)
@@ -65,29 +75,49 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
                          "keyed by the step's seed")
     if as_bytes and (data["images"].dim() != 5 or data["images"].shape[-1] not in (3, 4)):
         raise ValueError(f"a uint8 batch must be (SB, NV, H, W, 3 | 4), got {tuple(data['images'].shape)}")
+    B = int(ray_batch_size)
+    by_mask = prop_inside is not None and is_train and use_bbox
+    if by_mask:
+        util.num_inside(B, prop_inside)                 # ValueError outside [0, 1], before anything is moved or drawn
+        if data.get("masks") is None and not (draws == "device" and data.get("mask_bits") is not None
+                                              and data.get("mask_rows") is not None):
+            raise ValueError("prop_inside needs the batch's masks: data['masks'], or data['mask_bits'] and data['mask_rows'] "
+                             "(data.ResidentSplit(device_masks=True)) under draws='device'")
     all_images = util.upload(data["images"], device)
     all_poses = util.upload(data["poses"], device)
     if as_bytes:
         SB, NV, H, W, _ = all_images.shape
     else:
         SB, NV, _, H, W = all_images.shape
-    B = int(ray_batch_size)
     if draws == "device":
         boxes = None
-        if is_train and use_bbox:
+        if is_train and use_bbox and not by_mask:
             boxes = data.get("bbox_dev")
             if boxes is None and data.get("bbox") is not None:
                 boxes = util.upload(torch.as_tensor(data["bbox"], dtype=torch.float32), device)
         if boxes is not None:
             boxes = boxes.to(device=device, dtype=torch.float32)
-        pix_inds, image_ord = util.train_draw(boxes, SB, NV, W, H, B, curr_nviews_for(nviews, seed), seed,
-                                              out_pix=torch.empty(SB, B, dtype=torch.long, device=device), obj_base=obj_base)
+        out_pix = torch.empty(SB, B, dtype=torch.long, device=device)
+        if by_mask:
+            bits, rows = data.get("mask_bits"), data.get("mask_rows")
+            if bits is None or rows is None:
+                bits, rows = util.mask_table(util.mask_bytes(util.upload(data["masks"], device)))
+            pix_inds, image_ord = util.train_draw_masked(bits, rows, SB, NV, W, H, B, curr_nviews_for(nviews, seed), seed,
+                                                         prop_inside, out_pix=out_pix, obj_base=obj_base)
+        else:
+            pix_inds, image_ord = util.train_draw(boxes, SB, NV, W, H, B, curr_nviews_for(nviews, seed), seed,
+                                                  out_pix=out_pix, obj_base=obj_base)
         record = None if jitter is None else util.color_jitter_plan(all_images, jitter, seed, obj_base=obj_base)
         return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced, record)
 
     all_bboxes = data.get("bbox") if (is_train and use_bbox) else None
     if all_bboxes is not None and all_bboxes.is_cuda:
         raise ValueError("data['bbox'] must be a host tensor: it steers host-side draws and is never read from the device")
+    if by_mask:
+        all_masks = data["masks"]
+        if all_masks.is_cuda:
+            raise ValueError("data['masks'] must be a host tensor under draws='host': it steers host-side draws")
+        mask_thresh = 128 if all_masks.dtype == torch.uint8 else 0.5
 
     curr_nviews = nviews[int(torch.randint(0, len(nviews), ()))]
     host = torch.empty(SB * (B + curr_nviews), dtype=torch.long, pin_memory=True)
@@ -97,7 +127,10 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
     for obj in range(SB):
         if curr_nviews > 1:
             image_ord[obj] = torch.from_numpy(np.random.choice(NV, curr_nviews, replace=False))
-        if all_bboxes is not None:
+        if by_mask:
+            pix = util.masked_sample(all_masks[obj], B, prop_inside, thresh=mask_thresh)
+            pix_inds[obj] = pix[:, 0] * (H * W) + pix[:, 1] * W + pix[:, 2]
+        elif all_bboxes is not None:
             pix = util.bbox_sample(all_bboxes[obj], B)
             pix_inds[obj] = pix[:, 0] * (H * W) + pix[:, 1] * W + pix[:, 2]
         else:
@@ -139,7 +172,7 @@ def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_ne
 
 
 def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far, loss, use_bbox=True, is_train=True,
-                balanced=True, draws="host", seed=None, jitter=None, obj_base=0):
+                balanced=True, draws="host", seed=None, jitter=None, obj_base=0, prop_inside=None):
     """One batch of the data loader -> (loss, loss_dict), ready for loss.backward().
 
     net          PixelNeRFNet (on the device)
@@ -161,6 +194,9 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     obj_base     draws="device" only: `data` is the slice [obj_base, obj_base + SB) of the step's batch (make_batch), and the
                  render runs with the renderer's ray_index_base = obj_base * ray_batch_size, so its keyed noise is that of
                  those rays of the whole batch's render.  The loss is the mean over the slice's own rays.
+    prop_inside  None, or the share of an object's rays that falls on its mask's foreground: make_batch's mask-weighted draws
+                 in place of the boxes (needs data["masks"], or the tables of data.ResidentSplit(device_masks=True); training
+                 only, and only while use_bbox is on)
 
     loss_dict has "rc", "rf" (only with a fine pass) and "t".  Unlike the reference, which returns Python floats (three
     .item() calls, i.e. three host synchronisations per step), each value is a 0-dim view of ONE 3-float device buffer:
@@ -176,7 +212,8 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     dev = net.poses.device
     all_rays, all_rgb_gt, src_images, src_poses, focal, c = make_batch(
         data, dev, ray_batch_size=ray_batch_size, nviews=nviews, z_near=z_near, z_far=z_far, use_bbox=use_bbox, is_train=is_train,
-        balanced=balanced, draws=draws, seed=seed, jitter=jitter, obj_base=obj_base)
+        balanced=balanced, draws=draws, seed=seed, jitter=jitter, obj_base=obj_base,
+        **({} if prop_inside is None else {"prop_inside": prop_inside}))
     net.encode(src_images, src_poses, focal, c=c)
 
     if obj_base:
@@ -203,7 +240,8 @@ def train_step(net, render_par, data, optim, *, grad_hook=None, **calc_losses_kw
                  parallel.allreduce_gradients(params); a gradient it replaces is re-adopted by optim.step()
                  — and for optim.allreduce, DeviceAdam's own all-reduce of its flat gradient buffer (one collective; the
                  mean's divide is folded into the step)
-    the rest     calc_losses' keywords (ray_batch_size, nviews, z_near, z_far, loss, use_bbox, is_train, jitter, obj_base)
+    the rest     calc_losses' keywords (ray_batch_size, nviews, z_near, z_far, loss, use_bbox, is_train, jitter, obj_base,
+                 prop_inside)
 
     -> calc_losses' loss_dict with "grad_norm" added (the fp64 norm of the unscaled gradients before clipping, what
     clip_grad_norm_ returns): 0-dim device views, like the others.  Nothing in here waits for the device; whether the step

@@ -128,6 +128,10 @@ class Trainer:
     seed, draws        the base of every key; "device" (pnr_train_draw) or "host" — see the module text
     jitter             None or a data.ColorJitter: training steps augment their 8-bit batch's colours on the device, keyed like
                        the draws (train.make_batch); needs draws="device"; validation and the picture never see it
+    prop_inside        None or a number in [0, 1]: training steps draw that share of an object's rays on its mask's foreground and
+                       the rest on its background (train.make_batch) where they would draw inside its boxes — so no_bbox_step
+                       ends it too; the batches need "masks", or a data.ResidentSplit(device_masks=True); keyed like every
+                       draw under draws="device", so a checkpoint needs nothing new; validation never sees it
     print_interval (steps), save_interval / eval_interval / vis_interval (epochs), keep_last_checkpoints, save_strategy
     resume             False, True (latest.pth of this run if it exists) or a path (FileNotFoundError if missing)
     writer             None or an object with add_scalar(tag, value, step) / add_image(tag, hwc_uint8, step, dataformats="HWC")
@@ -159,7 +163,7 @@ class Trainer:
                  nviews, loss, num_epochs=100, lr=1e-4, lr_policy="none", gamma=0.1, step_size=10000, milestones=(10000, 20000),
                  grad_clip=None, scaler=None, no_bbox_step=100000, freeze_enc=False, seed=0, draws="device", print_interval=10,
                  save_interval=1, eval_interval=10, vis_interval=10, keep_last_checkpoints=20, save_strategy="keep_last",
-                 resume=False, writer=None, z_near=None, z_far=None, jitter=None, data_parallel=False):
+                 resume=False, writer=None, z_near=None, z_far=None, jitter=None, data_parallel=False, prop_inside=None):
         import torch.distributed as dist
         self.group, self.world, self.rank = None, 1, 0
         if data_parallel is not False and data_parallel is not None and dist.is_available() and dist.is_initialized():
@@ -195,6 +199,9 @@ class Trainer:
         self.z_far = float(train_data.z_far if z_far is None else z_far)
         self.balanced = bool(getattr(train_data, "balanced", True))
         self.jitter = jitter
+        if prop_inside is not None:
+            util.num_inside(self.ray_batch_size, prop_inside)       # ValueError outside [0, 1]
+        self.prop_inside = None if prop_inside is None else float(prop_inside)
         self.device = next(net.parameters()).device
 
         self.log_dir = os.path.join(logs_path, name)
@@ -341,6 +348,8 @@ class Trainer:
     def train_step(self, data, global_step):
         key = frame_seed(self.seed, global_step)
         more = dict(use_bbox=global_step < self.no_bbox_step, jitter=self.jitter)
+        if self.prop_inside is not None:
+            more.update(prop_inside=self.prop_inside)
         if self.world > 1:
             more.update(obj_base=self.obj_base, grad_hook=self._allreduce)
         with self._keyed(key):

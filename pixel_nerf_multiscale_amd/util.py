@@ -459,6 +459,138 @@ def train_draw(bbox, SB, NV, W, H, B, NS, seed, out_pix=None, out_views=None, ob
     return pix, views
 
 
+def masked_sample(masks, num_pix, prop_inside, thresh=0.5):
+    """num_pix pixels of which int(num_pix * prop_inside + 0.5) lie inside the mask and the rest outside, each uniform over all
+    views' pixels of its kind (reference util.py:210-222): masks (NV, H, W) or (NV, 1, H, W) on the host, inside where
+    masks >= thresh -> (num_pix, 3) long rows (view, row, col), the insides first.  Consumes torch's global CPU generator in the
+    reference's order — one randint for the insides, one for the outsides — so the same torch.manual_seed gives the same pixels
+    (tests/golden/masked_sample.npz).  An empty population raises ValueError (the reference's randint(0, 0) raises too)."""
+    masks = torch.as_tensor(masks)
+    if masks.dim() == 4 and masks.shape[1] == 1:
+        masks = masks[:, 0]
+    if masks.dim() != 3:
+        raise ValueError(f"masks must be (NV, H, W) or (NV, 1, H, W), got {tuple(masks.shape)}")
+    num_pix = int(num_pix)
+    num_inside = int(num_pix * prop_inside + 0.5)
+    if not 0 <= num_inside <= num_pix:
+        raise ValueError(f"prop_inside must lie in [0, 1], got {prop_inside}")
+    inside = (masks >= thresh).nonzero(as_tuple=False)
+    outside = (masks < thresh).nonzero(as_tuple=False)
+    if inside.shape[0] == 0 or outside.shape[0] == 0:
+        raise ValueError(f"masked_sample needs pixels inside and outside the mask, got {inside.shape[0]} and {outside.shape[0]}")
+    pix_inside = inside[torch.randint(0, inside.shape[0], (num_inside,))]
+    pix_outside = outside[torch.randint(0, outside.shape[0], (num_pix - num_inside,))]
+    return torch.cat((pix_inside, pix_outside))
+
+
+def num_inside(B, prop_inside):
+    """The inside slots of B mask-weighted draws: int(B * prop_inside + 0.5), as reference util.py:214 rounds."""
+    prop_inside = float(prop_inside)
+    if not 0.0 <= prop_inside <= 1.0:
+        raise ValueError(f"prop_inside must lie in [0, 1], got {prop_inside}")
+    return min(int(int(B) * prop_inside + 0.5), int(B))
+
+
+def mask_bytes(masks):
+    """Masks as the bytes mask_table thresholds: uint8 is used as it lies, bool / float becomes 0 / 255 by `>= 0.5`.  A float
+    BATCH with the channel axis the datasets give their float masks, (SB, NV, 1, H, W), loses that axis; anything else keeps its
+    shape.  -> uint8 (.., NV, H, W)."""
+    if not torch.is_tensor(masks):
+        raise ValueError(f"masks must be a tensor, got {type(masks).__name__}")
+    if masks.dim() == 5 and masks.shape[2] == 1 and masks.is_floating_point():
+        masks = masks.squeeze(2)
+    if masks.dtype == torch.uint8:
+        return masks
+    if masks.dtype == torch.bool:
+        return masks.to(torch.uint8) * 255
+    return (masks >= 0.5).to(torch.uint8) * 255
+
+
+def mask_table(masks, thresh=128, pix_stride=1, out=None):
+    """The bit table mask-weighted draws select from (pnr_mask_table_build; include/pnr.h writes the layout down): masks
+    (N, NV, H, W) or (NV, H, W) on the device — uint8 as it lies, bool / float through mask_bytes first — a pixel inside iff
+    byte >= thresh (1..255).  -> (bits (N, NV * H, ceil(W / 32)), rows (N, NV * H + 1)), int32 device tensors holding the uint32
+    patterns: the pixels' bits LSB first with a zero tail, and the prefix of the rows' popcounts.
+    pix_stride > 1: masks is (N, NV, H, W, pix_stride) uint8 (or without N) and the byte of channel 0 of each pixel is read where
+    it lies — hand in images[..., 3:] (a view, not copied) for an alpha channel.  out: (bits, rows) contiguous int32 tensors of
+    those shapes to fill, e.g. an object's slot of a pool.  Reads nothing back."""
+    from . import _native as N
+    thresh, pix_stride = int(thresh), int(pix_stride)
+    if not 1 <= thresh <= 255:
+        raise ValueError(f"thresh must lie in 1..255, got {thresh}")
+    if pix_stride < 1:
+        raise ValueError(f"pix_stride must be >= 1, got {pix_stride}")
+    if pix_stride == 1:
+        masks = mask_bytes(masks)
+        if masks.dim() == 3:
+            masks = masks[None]
+        if masks.dim() != 4:
+            raise ValueError(f"masks must be (N, NV, H, W) or (NV, H, W), got {tuple(masks.shape)}")
+        masks = masks.contiguous()
+        n, NV, H, W = (int(s) for s in masks.shape)
+    else:
+        if not torch.is_tensor(masks) or masks.dtype != torch.uint8 or masks.dim() not in (4, 5):
+            raise ValueError("with pix_stride > 1 masks must be uint8 (N, NV, H, W, channels) or (NV, H, W, channels)")
+        if masks.dim() == 4:
+            masks = masks[None]
+        n, NV, H, W = (int(s) for s in masks.shape[:4])
+        want = (NV * H * W * pix_stride, H * W * pix_stride, W * pix_stride, pix_stride)
+        if masks.shape[4] < 1 or any(masks.shape[d] > 1 and masks.stride(d) != want[d] for d in range(4)):
+            raise ValueError(f"masks must view pixels {pix_stride} bytes apart in a contiguous (N, NV, H, W, {pix_stride}) buffer, "
+                             f"got strides {masks.stride()}")
+    if min(n, NV, H, W) < 1 or NV * H * W >= 1 << 31:
+        raise ValueError(f"mask_table needs N, NV, H, W >= 1 and NV * H * W < 2^31, got {(n, NV, H, W)}")
+    R, Wd = NV * H, (W + 31) // 32
+    if out is None:
+        dev = N.same_device(masks)
+        bits = torch.empty(n, R, Wd, dtype=torch.int32, device=dev)
+        rows = torch.empty(n, R + 1, dtype=torch.int32, device=dev)
+    else:
+        bits, rows = out
+        dev = N.same_device(masks, bits, rows)
+        for name, t, shape in (("bits", bits, (n, R, Wd)), ("rows", rows, (n, R + 1))):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"out {name} must be a contiguous int32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    N.check(N.lib.pnr_mask_table_build(masks.data_ptr(), n, NV, H, W, pix_stride, thresh, bits.data_ptr(), rows.data_ptr(),
+                                       N.current_stream(dev)), "pnr_mask_table_build")
+    return bits, rows
+
+
+def train_draw_masked(bits, rows, SB, NV, W, H, B, NS, seed, prop_inside, out_pix=None, out_views=None, obj_base=0):
+    """train_draw with a mask in place of the boxes (pnr_train_draw_masked_at; include/pnr.h writes the arithmetic down): of the B
+    pixels of an object the first num_inside(B, prop_inside) are uniform over its INSIDE pixels, the rest over its OUTSIDE
+    pixels, all NV views pooled — the reference's masked_sample, keyed by `seed` alone.  bits (SB, NV * H, ceil(W / 32)) and
+    rows (SB, NV * H + 1): mask_table's int32 tensors on the device.  The views, the outputs, out_pix / out_views and obj_base
+    are train_draw's.  An object without inside (or without outside) pixels draws every slot from the population it has.
+    Reads nothing back."""
+    from . import _native as N
+    SB, NV, W, H, B, NS, seed = int(SB), int(NV), int(W), int(H), int(B), int(NS), int(seed)
+    obj_base = _obj_base(obj_base)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
+    if SB < 1 or NV < 1 or W < 1 or H < 1 or B < 0:
+        raise ValueError(f"train_draw_masked needs SB, NV, W, H >= 1 and B >= 0, got {(SB, NV, W, H, B)}")
+    if not 0 <= NS <= min(NV, 64):
+        raise ValueError(f"NS must lie in [0, min(NV, 64)] = [0, {min(NV, 64)}], got {NS}")
+    B_inside = num_inside(B, prop_inside)
+    for name, t, shape in (("bits", bits, (SB, NV * H, (W + 31) // 32)), ("rows", rows, (SB, NV * H + 1))):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be int32 {shape} (mask_table), got {getattr(t, 'dtype', None)} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    bits, rows = bits.contiguous(), rows.contiguous()
+    for name, t, shape in (("out_pix", out_pix, (SB, B)), ("out_views", out_views, (SB, NS))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.long or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int64 {shape} tensor, got {getattr(t, 'dtype', None)} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    dev = N.same_device(bits, rows, out_pix, out_views)
+    pix = torch.empty(SB, B, dtype=torch.long, device=dev) if out_pix is None else out_pix
+    views = torch.empty(SB, NS, dtype=torch.long, device=dev) if out_views is None else out_views
+    N.check(N.lib.pnr_train_draw_masked_at(bits.data_ptr(), rows.data_ptr(), SB, NV, W, H, B, B_inside, NS, seed, obj_base,
+                                           pix.data_ptr() if B else None, views.data_ptr() if NS else None,
+                                           N.current_stream(dev)), "pnr_train_draw_masked_at")
+    return pix, views
+
+
 def _record_stride(t, lead, last, name):
     """Floats per element of a tensor of shape lead [+ (last,)] — lead = (H, W) for a frame, (n,) for per-ray outputs — that is
     dense or a regular view into a packed per-element record: unit stride inside the element and, for a frame, row-major
