@@ -41,7 +41,7 @@ extern "C" {
                                   * pnr_adam_step_div; area resampling of images, pnr_resize_area_u8 / pnr_resize_area_f32; empty-space
                                   * culling, pnr_occ_build / pnr_ray_bounds_workspace_bytes / pnr_ray_bounds / pnr_frame_from_hits;
                                   * mask-weighted training draws, pnr_mask_table_build / pnr_train_draw_masked /
-                                  * pnr_train_draw_masked_at */
+                                  * pnr_train_draw_masked_at; the opacity losses, pnr_mask_gather / pnr_alpha_loss / pnr_alpha_loss_bwd */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -401,6 +401,48 @@ int32_t pnr_rgb_loss_bwd(const float* coarse_rgb, const float* fine_rgb, const f
                          int32_t use_l1, float lambda_coarse, float lambda_fine,
                          const float* d_total /* 1 float; NULL = 1 */,
                          float* d_coarse_rgb, float* d_fine_rgb /* (n_rays, 3); either may be NULL */, void* stream);
+
+/* ---- opacity losses on the compositing weights, csrc/opacity_loss.hip ------------------------------------------------------------
+ * The reference's AlphaLossNV2 (model/loss.py:24-37) in both of its modes and a binary cross entropy against a foreground mask, for
+ * the coarse and / or the fine pass's weights (n_rays, K) as the renderer leaves them under want_weights.  Everything from the
+ * weights' sum to the loss is fp64; each output is rounded to fp32 once.  No atomics: the same inputs give the same bits.
+ *
+ * Per pass alpha_r = sum_k (double) w[r, k], one wave per ray, in an order the shape alone fixes: lane l (0..63) adds w[r, l],
+ * w[r, l + 64], .. in ascending k starting from +0, then the 64 lane sums are folded by an xor butterfly over lane distances
+ * 32, 16, 8, 4, 2, 1 (v = v + v[lane ^ d]).  alpha_out[0, r] is the coarse pass's, alpha_out[1, r] the fine pass's; the row of a
+ * NULL pass is not written.  a = alpha < lo ? lo : (alpha > hi ? hi : alpha) with lo = (double) clamp_lo, hi = (double) clamp_hi:
+ * torch.clamp, a NaN stays a NaN.  The per-ray term t_r:
+ *   PNR_ALPHA_NV2     t = log a + log(1 - a), then t < -clamp_alpha ? -clamp_alpha : t        (loss.py:32-33)
+ *   PNR_ALPHA_OPAQUE  t = -log a                                                              (BCELoss(a, 1), loss.py:28-30)
+ *   PNR_ALPHA_MASK    t = -(m log a + (1 - m) log(1 - a)), m = (double) mask[r], any m in [0, 1]
+ * L = (sum_r t_r) / n_rays: ray r goes to thread r % 1024 of ONE workgroup, a thread adds its rays in ascending r, a wave folds by
+ * the butterfly above, and the 16 wave sums are added in ascending wave order.  (The term is evaluated by the workgroup that sums
+ * it: the call has no workspace, and alpha_out is what the backward needs.)
+ *   losses[0] = (float)((double) lambda_coarse * Lc), 0 for a NULL pass;  losses[1] = (float)((double) lambda_fine * Lf), likewise
+ *   losses[2] = losses[0] + losses[1] in fp32.  The lambdas ALWAYS apply — unlike pnr_rgb_loss, whose total drops lambda_coarse
+ *   when there is no fine pass.  n_rays == 0 writes three zeros.
+ * Two launches: a grid over the rays for alpha, one workgroup for the terms and their sum.
+ *
+ * pnr_alpha_loss_bwd, one launch, one wave per ray: with g = t'(a) —
+ *   NV2  1 / a - 1 / (1 - a), and 0 where log a + log(1 - a) < -clamp_alpha;   OPAQUE  -1 / a;   MASK  -(m / a - (1 - m) / (1 - a))
+ * — and g = 0 where alpha < lo or alpha > hi (both bounds pass at equality: torch's clamp backward; a NaN alpha passes and stays a
+ * NaN), d_w[r, k] = (float)((double) d_total * ((double) lambda / n_rays * g)) for every k.  d_total is read on the device; a
+ * power of two scales every element exactly.  alpha is what the forward wrote; Kc, Kf, mode and the clamps must be the forward's.
+ *   PNR_E_NULL   both passes NULL (forward: coarse_w and fine_w; backward: d_coarse_w and d_fine_w), PNR_ALPHA_MASK without mask,
+ *                alpha_out / alpha or losses NULL
+ *   PNR_E_SHAPE  K < 1 for a pass that is not NULL, n_rays < 0 or > 2^32, a mode outside the three, clamp_lo / clamp_hi not
+ *                satisfying 0 < clamp_lo < clamp_hi < 1
+ *   PNR_E_ALIGN  alpha_out / alpha not 8-byte aligned
+ * Nothing is allocated or read back; every check runs before any launch. */
+enum { PNR_ALPHA_NV2 = 0, PNR_ALPHA_OPAQUE = 1, PNR_ALPHA_MASK = 2 };
+int32_t pnr_alpha_loss(const float* coarse_w /* (n_rays, Kc) or NULL */, int32_t Kc, const float* fine_w /* (n_rays, Kf) or NULL */,
+                       int32_t Kf, const float* mask /* (n_rays); PNR_ALPHA_MASK only */, int64_t n_rays, int32_t mode,
+                       float lambda_coarse, float lambda_fine, float clamp_lo, float clamp_hi, float clamp_alpha,
+                       double* alpha_out /* (2, n_rays) */, float* losses /* 3 floats */, void* stream);
+int32_t pnr_alpha_loss_bwd(const double* alpha /* (2, n_rays), what the forward wrote */, const float* mask, int64_t n_rays, int32_t Kc,
+                           int32_t Kf, int32_t mode, float lambda_coarse, float lambda_fine, float clamp_lo, float clamp_hi,
+                           float clamp_alpha, const float* d_total /* 1 float on the device; NULL = 1 */,
+                           float* d_coarse_w /* (n_rays, Kc) or NULL */, float* d_fine_w /* (n_rays, Kf) or NULL */, void* stream);
 
 /* ---- evaluation back end: what eval/eval.py:286-347 does with a rendered frame, on the device ---------------------------- */
 /* One frame, where the render left it: x = clamp(rgb, 0, 1) (eval.py:291-293; a NaN stays a NaN), g = 0.5 * gt + 0.5
@@ -784,6 +826,16 @@ int32_t pnr_train_draw_masked(const uint32_t* bits, const uint32_t* rows, int32_
 int32_t pnr_train_draw_masked_at(const uint32_t* bits, const uint32_t* rows, int32_t SB, int32_t NV, int32_t W, int32_t H, int64_t B,
                                  int64_t B_inside, int32_t NS, uint64_t seed, int64_t obj_base, int64_t* pix_inds_out,
                                  int64_t* view_ord_out, void* stream);
+
+/* pnr_mask_gather: the ground truth of a mask loss at the step's pixels, read from the table the draws use.
+ * mask_out[o, j] = 1.0f if bit (col & 31) of word (col >> 5) of row p / W of bits[o] is set, p = pix_inds[o, j], col = p % W —
+ * pnr_mask_table_build's layout — else 0.0f.  An index outside [0, NV * H * W) reads nothing and writes NaN, as a row of
+ * pnr_train_batch does.  Nothing outside bits[o] is read.  One launch, one thread per pixel.
+ *   PNR_E_SHAPE  pnr_train_batch's size conditions (SB, NV, W, H < 1, B < 0, NV * H * W >= 2^31, SB * B past one launch)
+ *   PNR_E_NULL   bits, pix_inds or mask_out NULL with B > 0
+ *   PNR_E_ALIGN  bits or mask_out not 4-byte aligned, pix_inds not 8-byte aligned */
+int32_t pnr_mask_gather(const uint32_t* bits /* (SB, NV * H, ceil(W / 32)) */, int32_t SB, int32_t NV, int32_t H, int32_t W,
+                        const int64_t* pix_inds /* (SB, B) */, int64_t B, float* mask_out /* (SB, B) */, void* stream);
 
 /* Mesh extraction (util/recon.py: marching_cubes, with util.gen_grid util.py:98-115 and PyMCubes behind it), csrc/mesh.hip.
  *

@@ -19,6 +19,7 @@ PNR_F32, PNR_BF16, PNR_F16 = 0, 1, 2
 PNR_BF16X3 = 3     # training entry points only
 PRECISIONS = {"fp32": PNR_F32, "f32": PNR_F32, "bf16": PNR_BF16, "fp16": PNR_F16, "f16": PNR_F16, "bf16x3": PNR_BF16X3}
 COMBINE = {"average": 0, "max": 1}
+PNR_ALPHA_NV2, PNR_ALPHA_OPAQUE, PNR_ALPHA_MASK = 0, 1, 2
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -185,6 +186,9 @@ PROTOTYPES = {
     "pnr_mask_table_build": (_i32, [_fp, _i32, _i32, _i32, _i32, _i64, _i32, _fp, _fp, _fp]),
     "pnr_train_draw_masked": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _u64, _fp, _fp, _fp]),
     "pnr_train_draw_masked_at": (_i32, [_fp, _fp, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _u64, _i64, _fp, _fp, _fp]),
+    "pnr_mask_gather": (_i32, [_fp, _i32, _i32, _i32, _i32, _fp, _i64, _fp, _fp]),
+    "pnr_alpha_loss": (_i32, [_fp, _i32, _fp, _i32, _fp, _i64, _i32, _f, _f, _f, _f, _f, _fp, _fp, _fp]),
+    "pnr_alpha_loss_bwd": (_i32, [_fp, _fp, _i64, _i32, _i32, _i32, _f, _f, _f, _f, _f, _fp, _fp, _fp, _fp]),
     "pnr_grid_points": (_i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _i64, _i64, _i32, _fp, _fp, _fp]),
     "pnr_mc_workspace_bytes": (_u64, [_i32, _i32, _i32]),
     "pnr_mc_count": (_i32, [_fp, _i32, _i32, _i32, _i32, C.c_double, _fp, _u64, _fp, _fp]),

@@ -111,6 +111,23 @@ __global__ void __launch_bounds__(256) k_train_draw_masked(const uint32_t* __res
     draw_views(seed, (uint64_t)(obj_base + o), NV, NS, view_out + o * NS);
 }
 
+// One thread per gathered pixel (o, j): the bit of pixel pix_inds[o, j] in bits[o], as 1.0f / 0.0f.  The indices live on the device, so
+// the kernel is the range check: an index outside [0, R * W) reads nothing and writes NaN.  row < R and col >> 5 < Wd: the one
+// word read lies inside bits[o].
+__global__ void __launch_bounds__(256) k_mask_gather(const uint32_t* __restrict__ bits, int W, int R, int Wd, const int64_t* __restrict__ pix_inds,
+                                                     int64_t B, int64_t total, float* __restrict__ mask_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t p = pix_inds[i];
+    float v = __builtin_nanf("");
+    if (p >= 0 && p < (int64_t)R * W) {
+        const int64_t o = i / B;
+        const int row = (int)(p / W), col = (int)(p - (int64_t)row * W);
+        v = (bits[(o * R + row) * Wd + (col >> 5)] >> (col & 31)) & 1u ? 1.0f : 0.0f;
+    }
+    mask_out[i] = v;
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -152,4 +169,17 @@ extern "C" int32_t pnr_train_draw_masked(const uint32_t* bits, const uint32_t* r
                                          int64_t B, int64_t B_inside, int32_t NS, uint64_t seed, int64_t* pix_inds_out,
                                          int64_t* view_ord_out, void* stream) {
     return pnr_train_draw_masked_at(bits, rows, SB, NV, W, H, B, B_inside, NS, seed, 0, pix_inds_out, view_ord_out, stream);
+}
+
+extern "C" int32_t pnr_mask_gather(const uint32_t* bits, int32_t SB, int32_t NV, int32_t H, int32_t W, const int64_t* pix_inds, int64_t B,
+                                   float* mask_out, void* stream) {
+    if (!batch_shape_ok(SB, NV, W, H, B)) return PNR_E_SHAPE;
+    if (B > 0 && (!bits || !pix_inds || !mask_out)) return PNR_E_NULL;
+    if ((((uintptr_t)bits) | ((uintptr_t)mask_out)) & 3 || (((uintptr_t)pix_inds) & 7)) return PNR_E_ALIGN;
+    if (B == 0) return PNR_OK;
+    const int64_t total = (int64_t)SB * B;
+    hipLaunchKernelGGL(k_mask_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bits, W, NV * H,
+                       (W + 31) / 32, pix_inds, B, total, mask_out);
+    PNR_LAUNCH_CHECK();
+    return PNR_OK;
 }

@@ -2,13 +2,14 @@
 Training path: the renderer under autograd, as train/train.py:324-346,382-410 uses the
 reference (calc_losses -> renderer(net, rays, want_weights=True) -> loss.backward()).
 
-Three torch.autograd.Functions, each a thin shell over a forward/backward pair of libpnr_hip.so entry
+torch.autograd.Functions, each a thin shell over a forward/backward pair of libpnr_hip.so entry
 points (csrc/train_f32.hip) — no PyTorch arithmetic on the per-point data:
 
   PointMLP      pnr_point_mlp_train_fwd / pnr_point_mlp_bwd    PixelNeRFNet.forward (models.py.backup2:155-282)
   Composite     pnr_composite / pnr_composite_bwd              NeRFRenderer.composite (nerf.py:178-182,223-249)
   SampleFine    pnr_sample_fine / pnr_sample_fine_bwd          sample_fine* + cat + sort (nerf.py:120-161,285-295)
   RGBLoss       pnr_rgb_loss / pnr_rgb_loss_bwd                the trainer's rgb loss (train.py:338-346, loss.py:99-103)
+  AlphaLoss     pnr_alpha_loss / pnr_alpha_loss_bwd            the opacity losses on the weights (loss.py:24-37, and a mask BCE)
 
 Gradients reach the MLP weights, the encoder's latent maps (and through them the ResNet trunk, which stays
 a PyTorch module) and — because nerf.py:287-289 does not detach the depth-guided samples — the coarse depth
@@ -249,6 +250,61 @@ class RGBLoss(torch.autograd.Function):
         N.check(N.lib.pnr_rgb_loss_bwd(N.ptr(c), N.ptr(f), N.ptr(g), n, use_l1, lc, lf, N.ptr(d_total), N.ptr(d_c), N.ptr(d_f),
                                        N.current_stream(c.device)), "pnr_rgb_loss_bwd")
         return d_c, d_f, None, None, None, None
+
+
+class AlphaLoss(torch.autograd.Function):
+    """(total, stats) = an opacity loss of the coarse and / or the fine pass's compositing weights (..., K) — either may be None,
+    not both: mode N.PNR_ALPHA_NV2 / PNR_ALPHA_OPAQUE (the reference's AlphaLossNV2, loss.py:24-37) or PNR_ALPHA_MASK, a binary
+    cross entropy of the weights' sum against mask (...), any values in [0, 1] (include/pnr.h writes the arithmetic down: fp64
+    from the sum to the loss).  total: 0-dim, differentiable in the two weight tensors only.  stats: the 3-float device buffer
+    [lambda_c Lc, lambda_f Lf, total], not differentiable.  The fp64 sums are kept for the backward; nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, coarse_w, fine_w, mask, mode, lambda_coarse, lambda_fine, clamp_lo, clamp_hi, clamp_alpha):
+        dev = N.same_device(coarse_w, fine_w, mask)
+        first = coarse_w if coarse_w is not None else fine_w
+        if first is None:
+            raise ValueError("AlphaLoss needs the weights of at least one pass")
+        if first.dim() < 1 or (coarse_w is not None and fine_w is not None and coarse_w.shape[:-1] != fine_w.shape[:-1]):
+            raise ValueError("weights must share their ray axes (..., K): coarse "
+                             f"{None if coarse_w is None else tuple(coarse_w.shape)}, fine {None if fine_w is None else tuple(fine_w.shape)}")
+        n_rays = first.numel() // max(first.shape[-1], 1)
+        if mask is not None and mask.numel() != n_rays:
+            raise ValueError(f"mask must hold one value per ray ({n_rays}), got {tuple(mask.shape)}")
+        c = None if coarse_w is None else N.f32c(coarse_w.detach())
+        f = None if fine_w is None else N.f32c(fine_w.detach())
+        m = None if mask is None else N.f32c(mask.detach())
+        Kc, Kf = (0 if c is None else c.shape[-1]), (0 if f is None else f.shape[-1])
+        cfg = (n_rays, Kc, Kf, int(mode), float(lambda_coarse), float(lambda_fine), float(clamp_lo), float(clamp_hi),
+               float(clamp_alpha))
+        alpha = torch.empty(2, n_rays, dtype=torch.float64, device=dev)
+        stats = torch.empty(3, device=dev)
+        N.check(N.lib.pnr_alpha_loss(N.ptr(c), Kc, N.ptr(f), Kf, N.ptr(m), n_rays, *cfg[3:], alpha.data_ptr(), N.ptr(stats),
+                                     N.current_stream(dev)), "pnr_alpha_loss")
+        ctx.cfg = cfg
+        ctx.shapes = (None if c is None else c.shape, None if f is None else f.shape)
+        ctx.has_mask = m is not None
+        ctx.save_for_backward(alpha, *([m] if m is not None else []))
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)        # no zero tensor for the stats' absent gradient
+        return stats[2], stats                  # total: a 0-dim view of the stats buffer, no copy
+
+    @staticmethod
+    def backward(ctx, d_total, _d_stats):
+        if d_total is None:
+            return (None,) * 9
+        alpha = ctx.saved_tensors[0]
+        m = ctx.saved_tensors[1] if ctx.has_mask else None
+        n_rays, Kc, Kf = ctx.cfg[:3]
+        dev = alpha.device
+        d_c = torch.empty(ctx.shapes[0], device=dev) if (ctx.shapes[0] is not None and ctx.needs_input_grad[0]) else None
+        d_f = torch.empty(ctx.shapes[1], device=dev) if (ctx.shapes[1] is not None and ctx.needs_input_grad[1]) else None
+        if d_c is None and d_f is None:
+            return (None,) * 9
+        d_total = N.f32c(d_total, dev)
+        N.check(N.lib.pnr_alpha_loss_bwd(alpha.data_ptr(), N.ptr(m), n_rays, Kc, Kf, *ctx.cfg[3:], N.ptr(d_total), N.ptr(d_c),
+                                         N.ptr(d_f), N.current_stream(dev)), "pnr_alpha_loss_bwd")
+        return (d_c, d_f) + (None,) * 7
 
 
 # ---------------------------------------------------------------------------------------------------------------

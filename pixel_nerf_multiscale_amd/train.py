@@ -17,7 +17,7 @@ def curr_nviews_for(nviews, seed):
 
 
 def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=True, is_train=True, balanced=True,
-               draws="host", seed=None, jitter=None, obj_base=0, prop_inside=None):
+               draws="host", seed=None, jitter=None, obj_base=0, prop_inside=None, want_mask=False):
     """The front end of calc_losses (train/train.py:243-317): host draws, ONE upload of the (SB, ray_batch_size) pixel
     indices (the source-view choice rides in the same buffer) and one of the intrinsics, both from pinned memory, one launch
     for the rays and colours, and the source views picked on the device.
@@ -57,7 +57,13 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
     place of util.train_draw; an object without foreground (or without background) draws every pixel from what it has.
     draws="host": util.masked_sample per object where util.bbox_sample stood, and such an object raises ValueError.  uint8
     masks are inside at >= 128, float masks at >= 0.5.  A batch with neither table nor masks raises ValueError; is_train=False
-    or use_bbox=False ignore prop_inside; None (the default) makes the calls made without it."""
+    or use_bbox=False ignore prop_inside; None (the default) makes the calls made without it.
+
+    want_mask=True: a seventh value, mask_gt (SB, B) float32 — 1.0 where the ray's pixel lies on the object's mask, else 0.0 (the
+    ground truth of model.loss.MaskLoss), read by ONE util.mask_gather launch from the bit table: data["mask_bits"] when present,
+    else the table built from data["masks"] (uploaded when on the host) — the one prop_inside draws from; it is built at most
+    once per step.  Training or not, host or device draws.  A batch with neither raises ValueError.  False (the default)
+    returns exactly the six values above."""
     if draws not in ("host", "device"):
         raise ValueError(f"draws must be 'host' or 'device', got {draws!r}")
     obj_base = int(obj_base)
@@ -83,8 +89,24 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
                                               and data.get("mask_rows") is not None):
             raise ValueError("prop_inside needs the batch's masks: data['masks'], or data['mask_bits'] and data['mask_rows'] "
                              "(data.ResidentSplit(device_masks=True)) under draws='device'")
+    if want_mask and data.get("masks") is None and data.get("mask_bits") is None:
+        raise ValueError("want_mask needs the batch's masks: data['masks'], or data['mask_bits'] "
+                         "(data.ResidentSplit(device_masks=True))")
     all_images = util.upload(data["images"], device)
     all_poses = util.upload(data["poses"], device)
+    table = []
+
+    def mask_tables():
+        """(bits, rows) of the step's objects: the batch's own, or built from its masks — once, whoever asks first."""
+        if not table:
+            bits, rows = data.get("mask_bits"), data.get("mask_rows")
+            if data.get("masks") is not None and (bits is None or rows is None):
+                bits, rows = util.mask_table(util.mask_bytes(util.upload(data["masks"], device)))
+            table.append((bits, rows))
+        return table[0]
+
+    def with_mask(out, pix_inds):
+        return out + (util.mask_gather(mask_tables()[0], pix_inds, NV, H, W),) if want_mask else out
     if as_bytes:
         SB, NV, H, W, _ = all_images.shape
     else:
@@ -99,16 +121,15 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
             boxes = boxes.to(device=device, dtype=torch.float32)
         out_pix = torch.empty(SB, B, dtype=torch.long, device=device)
         if by_mask:
-            bits, rows = data.get("mask_bits"), data.get("mask_rows")
-            if bits is None or rows is None:
-                bits, rows = util.mask_table(util.mask_bytes(util.upload(data["masks"], device)))
+            bits, rows = mask_tables()
             pix_inds, image_ord = util.train_draw_masked(bits, rows, SB, NV, W, H, B, curr_nviews_for(nviews, seed), seed,
                                                          prop_inside, out_pix=out_pix, obj_base=obj_base)
         else:
             pix_inds, image_ord = util.train_draw(boxes, SB, NV, W, H, B, curr_nviews_for(nviews, seed), seed,
                                                   out_pix=out_pix, obj_base=obj_base)
         record = None if jitter is None else util.color_jitter_plan(all_images, jitter, seed, obj_base=obj_base)
-        return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced, record)
+        return with_mask(_gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced, record),
+                         pix_inds)
 
     all_bboxes = data.get("bbox") if (is_train and use_bbox) else None
     if all_bboxes is not None and all_bboxes.is_cuda:
@@ -137,7 +158,7 @@ def make_batch(data, device, *, ray_batch_size, nviews, z_near, z_far, use_bbox=
             pix_inds[obj] = torch.randint(0, NV * H * W, (B,))
     on_dev = host.to(device, non_blocking=True)
     pix_inds, image_ord = on_dev[:SB * B].view(SB, B), on_dev[SB * B:].view(SB, curr_nviews)
-    return _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced)
+    return with_mask(_gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced), pix_inds)
 
 
 def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_near, z_far, balanced, jitter=None):
@@ -172,7 +193,7 @@ def _gather_batch(data, device, all_images, all_poses, pix_inds, image_ord, z_ne
 
 
 def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far, loss, use_bbox=True, is_train=True,
-                balanced=True, draws="host", seed=None, jitter=None, obj_base=0, prop_inside=None):
+                balanced=True, draws="host", seed=None, jitter=None, obj_base=0, prop_inside=None, alpha_loss=None, mask_loss=None):
     """One batch of the data loader -> (loss, loss_dict), ready for loss.backward().
 
     net          PixelNeRFNet (on the device)
@@ -197,6 +218,13 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     prop_inside  None, or the share of an object's rays that falls on its mask's foreground: make_batch's mask-weighted draws
                  in place of the boxes (needs data["masks"], or the tables of data.ResidentSplit(device_masks=True); training
                  only, and only while use_bbox is on)
+    alpha_loss   None, or a model.loss.AlphaLossNV2: applied to the fine pass's weights when there is one, else to the coarse
+                 pass's (the reference's alpha_fine); its own epoch gate decides whether anything is launched
+    mask_loss    None, or a model.loss.MaskLoss: make_batch(want_mask=True) gathers the mask at the step's pixels (the batch
+                 needs "masks", or the tables of data.ResidentSplit(device_masks=True)), and the loss supervises both passes.
+                 Both losses are added to the total on the device, in validation (is_train=False) too; loss_dict gains "a" / "m"
+                 (0-dim device views) only for the losses given, and "t" is then the sum.  With both None every call made
+                 without them is made unchanged.
 
     loss_dict has "rc", "rf" (only with a fine pass) and "t".  Unlike the reference, which returns Python floats (three
     .item() calls, i.e. three host synchronisations per step), each value is a 0-dim view of ONE 3-float device buffer:
@@ -210,10 +238,11 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     if "images" not in data:
         return {}
     dev = net.poses.device
-    all_rays, all_rgb_gt, src_images, src_poses, focal, c = make_batch(
+    batch = make_batch(
         data, dev, ray_batch_size=ray_batch_size, nviews=nviews, z_near=z_near, z_far=z_far, use_bbox=use_bbox, is_train=is_train,
         balanced=balanced, draws=draws, seed=seed, jitter=jitter, obj_base=obj_base,
-        **({} if prop_inside is None else {"prop_inside": prop_inside}))
+        **({} if prop_inside is None else {"prop_inside": prop_inside}), **({} if mask_loss is None else {"want_mask": True}))
+    all_rays, all_rgb_gt, src_images, src_poses, focal, c = batch[:6]
     net.encode(src_images, src_poses, focal, c=c)
 
     if obj_base:
@@ -228,6 +257,18 @@ def calc_losses(net, render_par, data, *, ray_batch_size, nviews, z_near, z_far,
     if fine is not None and len(fine) > 0:
         loss_dict["rf"] = stats[1]
     loss_dict["t"] = stats[2]
+    if mask_loss is not None:
+        m_total, m_stats = mask_loss(render_dict, batch[6])
+        total = total + m_total
+        loss_dict["m"] = m_stats[2]
+    if alpha_loss is not None:
+        has_fine = fine is not None and len(fine) > 0
+        a_total = alpha_loss((fine if has_fine else render_dict["coarse"])["weights"])
+        if getattr(alpha_loss, "active", True):          # an inactive loss is a cached zero: nothing to add, nothing launched
+            total = total + a_total
+        loss_dict["a"] = a_total.detach()
+    if mask_loss is not None or alpha_loss is not None:
+        loss_dict["t"] = total.detach()
     return total, loss_dict
 
 
@@ -241,7 +282,7 @@ def train_step(net, render_par, data, optim, *, grad_hook=None, **calc_losses_kw
                  — and for optim.allreduce, DeviceAdam's own all-reduce of its flat gradient buffer (one collective; the
                  mean's divide is folded into the step)
     the rest     calc_losses' keywords (ray_batch_size, nviews, z_near, z_far, loss, use_bbox, is_train, jitter, obj_base,
-                 prop_inside)
+                 prop_inside, alpha_loss, mask_loss)
 
     -> calc_losses' loss_dict with "grad_norm" added (the fp64 norm of the unscaled gradients before clipping, what
     clip_grad_norm_ returns): 0-dim device views, like the others.  Nothing in here waits for the device; whether the step
@@ -261,7 +302,7 @@ def train_step(net, render_par, data, optim, *, grad_hook=None, **calc_losses_kw
 
 def eval_step(net, renderer, render_par, data, **calc_losses_kw):
     """Trainer.eval_step of the reference (train/train.py:414-421): calc_losses(..., is_train=False) under torch.no_grad()
-    with the renderer in eval mode -> the loss_dict ("rc", "rf" with a fine pass, "t"), the part Trainer.validate consumes,
+    with the renderer in eval mode -> the loss_dict ("rc", "rf" with a fine pass, "t"; "a" / "m" with alpha_loss / mask_loss), the part Trainer.validate consumes,
     its values still on the device; {} for a batch without images.  The reference ends with an unconditional
     renderer.train(); this RESTORES the mode the renderer was in instead.  Nothing in here waits for the device."""
     calc_losses_kw.pop("is_train", None)

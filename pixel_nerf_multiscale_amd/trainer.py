@@ -132,6 +132,12 @@ class Trainer:
                        the rest on its background (train.make_batch) where they would draw inside its boxes — so no_bbox_step
                        ends it too; the batches need "masks", or a data.ResidentSplit(device_masks=True); keyed like every
                        draw under draws="device", so a checkpoint needs nothing new; validation never sees it
+    alpha_loss         None or a model.loss.AlphaLossNV2: added to every step's and every validation batch's loss (train.calc_losses);
+                       its epoch gate is set from the Trainer's own counter at every epoch's start (set_epoch), so a checkpoint
+                       needs nothing new; logged as "a"
+    mask_loss          None or a model.loss.MaskLoss: the silhouette loss against the batches' masks ("masks", or a
+                       data.ResidentSplit(device_masks=True)), training and validation; logged as "m".  Under data_parallel both
+                       are the mean over the rank's own rays, as the rgb loss is.  With both None every call is made unchanged.
     print_interval (steps), save_interval / eval_interval / vis_interval (epochs), keep_last_checkpoints, save_strategy
     resume             False, True (latest.pth of this run if it exists) or a path (FileNotFoundError if missing)
     writer             None or an object with add_scalar(tag, value, step) / add_image(tag, hwc_uint8, step, dataformats="HWC")
@@ -163,7 +169,8 @@ class Trainer:
                  nviews, loss, num_epochs=100, lr=1e-4, lr_policy="none", gamma=0.1, step_size=10000, milestones=(10000, 20000),
                  grad_clip=None, scaler=None, no_bbox_step=100000, freeze_enc=False, seed=0, draws="device", print_interval=10,
                  save_interval=1, eval_interval=10, vis_interval=10, keep_last_checkpoints=20, save_strategy="keep_last",
-                 resume=False, writer=None, z_near=None, z_far=None, jitter=None, data_parallel=False, prop_inside=None):
+                 resume=False, writer=None, z_near=None, z_far=None, jitter=None, data_parallel=False, prop_inside=None,
+                 alpha_loss=None, mask_loss=None):
         import torch.distributed as dist
         self.group, self.world, self.rank = None, 1, 0
         if data_parallel is not False and data_parallel is not None and dist.is_available() and dist.is_initialized():
@@ -202,6 +209,7 @@ class Trainer:
         if prop_inside is not None:
             util.num_inside(self.ray_batch_size, prop_inside)       # ValueError outside [0, 1]
         self.prop_inside = None if prop_inside is None else float(prop_inside)
+        self.alpha_loss, self.mask_loss = alpha_loss, mask_loss
         self.device = next(net.parameters()).device
 
         self.log_dir = os.path.join(logs_path, name)
@@ -335,6 +343,10 @@ class Trainer:
     def _losses_kw(self, key, **more):
         kw = dict(ray_batch_size=self.ray_batch_size, nviews=self.nviews, z_near=self.z_near, z_far=self.z_far, loss=self.loss,
                   balanced=self.balanced, **more)
+        if self.alpha_loss is not None:
+            kw.update(alpha_loss=self.alpha_loss)
+        if self.mask_loss is not None:
+            kw.update(mask_loss=self.mask_loss)
         if self.draws == "device":
             kw.update(draws="device", seed=key)
         return kw
@@ -371,6 +383,8 @@ class Trainer:
         return dict(zip(keys, vals))
 
     def train_epoch(self, epoch):
+        if self.alpha_loss is not None:
+            self.alpha_loss.set_epoch(epoch)
         self._net_train()
         self.renderer.train()
         total, count = None, 0
@@ -554,6 +568,8 @@ class Trainer:
         self._log(f"training {self.name}: device {self.device}, batch size {self.batch_size}, lr {self.lr}, {self.num_epochs} epochs, "
                   f"draws {self.draws}, seed {self.seed}, checkpoints {self.checkpoint_dir} ({self.save_strategy}), logs {self.log_dir}"
                   + (f", {self.world} ranks of {self.rank_batch} objects" if self.world > 1 else ""))
+        if self.alpha_loss is not None:
+            self.alpha_loss.set_epoch(self.epoch)
         if self.epoch > 0 and self.epoch % self.eval_interval == 0:        # a resumed epoch on an evaluation node
             self._validate_and_keep_best()
         for epoch in range(self.epoch, self.num_epochs):

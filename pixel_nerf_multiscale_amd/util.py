@@ -591,6 +591,32 @@ def train_draw_masked(bits, rows, SB, NV, W, H, B, NS, seed, prop_inside, out_pi
     return pix, views
 
 
+def mask_gather(bits, pix_inds, NV, H, W, out=None):
+    """The mask's value at sampled pixels, read from the bit table the mask-weighted draws use (pnr_mask_gather): bits
+    (SB, NV * H, ceil(W / 32)) int32 (mask_table, or data.ResidentSplit(device_masks=True)) and pix_inds (SB, B) int64, both on
+    the device -> float32 (SB, B): 1.0 where the pixel's bit is set, else 0.0; NaN for an index outside [0, NV * H * W), as
+    train_batch gives such a row.  out: a contiguous float32 (SB, B) tensor to fill.  One launch; reads nothing back."""
+    from . import _native as N
+    NV, H, W = int(NV), int(H), int(W)
+    if min(NV, H, W) < 1 or NV * H * W >= 1 << 31:
+        raise ValueError(f"mask_gather needs NV, H, W >= 1 and NV * H * W < 2^31, got {(NV, H, W)}")
+    if not torch.is_tensor(pix_inds) or pix_inds.dim() != 2 or pix_inds.dtype != torch.long:
+        raise ValueError(f"pix_inds must be (SB, B) int64, got {getattr(pix_inds, 'dtype', None)} {tuple(getattr(pix_inds, 'shape', ()))}")
+    SB, B = (int(x) for x in pix_inds.shape)
+    shape = (SB, NV * H, (W + 31) // 32)
+    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or tuple(bits.shape) != shape or SB < 1:
+        raise ValueError(f"bits must be int32 {shape} (mask_table), got {getattr(bits, 'dtype', None)} {tuple(getattr(bits, 'shape', ()))}")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (SB, B) or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 {(SB, B)} tensor, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(getattr(out, 'shape', ()))}")
+    dev = N.same_device(bits, pix_inds, out)
+    bits, pix_inds = bits.contiguous(), pix_inds.contiguous()
+    mask = torch.empty(SB, B, device=dev) if out is None else out
+    N.check(N.lib.pnr_mask_gather(bits.data_ptr(), SB, NV, H, W, pix_inds.data_ptr(), B, mask.data_ptr(), N.current_stream(dev)),
+            "pnr_mask_gather")
+    return mask
+
+
 def _record_stride(t, lead, last, name):
     """Floats per element of a tensor of shape lead [+ (last,)] — lead = (H, W) for a frame, (n,) for per-ray outputs — that is
     dense or a regular view into a packed per-element record: unit stride inside the element and, for a frame, row-major
