@@ -314,6 +314,69 @@ def scratch(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def _want(dtype, shape):
+    """'float32 (..., 3|4, ?, 8)': what arg and out say they wanted."""
+    dims = []
+    for w in shape:
+        if w is ...:
+            dims.append("...")
+        elif w is None:
+            dims.append("?")
+        elif isinstance(w, tuple):
+            dims.append("|".join(str(s) for s in w))
+        else:
+            dims.append(str(w))
+    kind = "a tensor" if dtype is None else str(dtype).replace("torch.", "")
+    return f"{kind} ({', '.join(dims)})"
+
+
+def arg(t, name, dtype, shape, *, contiguous=False):
+    """The one check of a tensor argument: dtype (None: any) and shape, a tuple whose entries are an int (exactly), None (any
+    size) or a tuple of allowed sizes, behind an optional leading ... for any number of leading dimensions.  Anything else —
+    no tensor at all included — is a ValueError that names the argument, what it must be and what it is.  -> t, made
+    contiguous when contiguous=True.  The device is same_device's to judge, so host tensors pass."""
+    # written out flat, the good case first: wrappers on the per-step path call this several times
+    if isinstance(t, torch.Tensor) and (dtype is None or t.dtype == dtype):
+        got = t.shape
+        fits = got == shape
+        if not fits:
+            has_lead = len(shape) > 0 and shape[0] is ...
+            dims = shape[1:] if has_lead else shape
+            if has_lead and len(got) > len(dims):
+                got = got[len(got) - len(dims):]
+            if len(got) == len(dims):
+                for s, w in zip(got, dims):
+                    if w is not None and s != w and not (isinstance(w, tuple) and s in w):
+                        break
+                else:
+                    fits = True
+        if fits:
+            return t.contiguous() if contiguous else t
+    got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+    raise ValueError(f"{name} must be {_want(dtype, shape)}, got {got}")
+
+
+def out(out, name, dtype, shape, dev):
+    """The one rule of an optional output tensor (shape: a tuple): None -> a new one of this dtype and shape on dev; a given
+    one must have exactly that dtype and shape and be contiguous (at any offset of a larger buffer: a pool's slot), else
+    ValueError, and is returned as it is, never copied."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not isinstance(out, torch.Tensor) or out.dtype != dtype or out.shape != shape or not out.is_contiguous():
+        got = f"{out.dtype} {tuple(out.shape)} strides {out.stride()}" if isinstance(out, torch.Tensor) else type(out).__name__
+        raise ValueError(f"{name} must be a contiguous {_want(dtype, shape)}, got {got}")
+    return out
+
+
+def key64(v, name, limit=1 << 64):
+    """A key or an index of the keyed kernels as a host int: 0 <= v < limit (an unsigned 64-bit seed; 1 << 63 for what
+    travels as int64)."""
+    v = int(v)
+    if not 0 <= v < limit:
+        raise ValueError(f"{name} must lie in [0, 2^{limit.bit_length() - 1}), got {v}")
+    return v
+
+
 def f32c(t, device=None):
     """float32 + contiguous (+ device) view/copy of t."""
     if device is not None and t.device != device:

@@ -19,16 +19,11 @@ def extract_mesh(field, iso, origin=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0)):
     index coordinate * scale + origin, triangles (T, 3) int32) on the device.  A grid point is inside iff field >= iso;
     normals point from inside to outside.  One host read (the two counts) sits between the two calls."""
     from . import _native as N
-    if field.dim() != 3 or field.dtype != torch.float32:
-        raise ValueError(f"field must be float32 (nx, ny, nz), got {field.dtype} {tuple(field.shape)}")
-    dev = N.same_device(field)
-    nx, ny, nz = (int(s) for s in field.shape)
-    st = field.stride()
-    s = int(st[2])
-    if s < 1 or st[1] != nz * s or st[0] != ny * nz * s:
-        raise ValueError(f"field must be dense or a regularly strided view of a per-point record, got strides {st}")
+    s = util._field_stride(field, "field")
+    nx, ny, nz = (int(n) for n in field.shape)
     if len(origin) != 3 or len(scale) != 3:
         raise ValueError("origin and scale must have 3 entries each")
+    dev = N.same_device(field)
     nbytes = int(N.lib.pnr_mc_workspace_bytes(nx, ny, nz))
     ws = N.scratch(nbytes, dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)

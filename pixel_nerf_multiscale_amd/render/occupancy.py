@@ -84,16 +84,11 @@ class OccupancyGrid:
         output is read where it lies) -> the grid of the cells with a corner sample >= thresh (or NaN), grown by `dilate`
         cells (0 .. 4, Chebyshev).  into: a grid of the same box and size to OR the result into (it is returned)."""
         from .. import _native as N
-        if sigma.dim() != 3 or sigma.dtype != torch.float32:
-            raise ValueError(f"sigma must be float32 (nx, ny, nz), got {sigma.dtype} {tuple(sigma.shape)}")
+        s = util._field_stride(sigma, "sigma")
+        nx, ny, nz = (int(n) for n in sigma.shape)
         if not 0 <= int(dilate) <= MAX_DILATE:
             raise ValueError(f"dilate must be 0 .. {MAX_DILATE}, got {dilate}")
         dev = N.same_device(sigma)
-        nx, ny, nz = (int(s) for s in sigma.shape)
-        st = sigma.stride()
-        s = int(st[2])
-        if s < 1 or st[1] != nz * s or st[0] != ny * nz * s:
-            raise ValueError(f"sigma must be dense or a regularly strided view of a per-point record, got strides {st}")
         if into is None:
             grid = cls(c1, c2, (nx, ny, nz), torch.empty(_words((nx, ny, nz)), dtype=torch.int32, device=dev))
         else:
@@ -177,13 +172,13 @@ def ray_bounds(grid, rays, rays_per_frame=None, pad=None):
     [max(near, t_in - pad), min(far, t_out + pad)]; the rows past a count are not written.  slot[i]: ray i's place in its
     frame's list, or -1.  pad=None: one cell diagonal, computed in fp64 on the host."""
     from .. import _native as N
-    if rays.dim() != 2 or rays.shape[1] != 8 or rays.dtype != torch.float32 or not rays.is_contiguous():
-        raise ValueError(f"rays must be a contiguous float32 (n, 8), got {rays.dtype} {tuple(rays.shape)}")
-    dev = N.same_device(rays, grid.bits)
+    if not N.arg(rays, "rays", torch.float32, (None, 8)).is_contiguous():
+        raise ValueError(f"rays must be contiguous, got strides {rays.stride()}")
     n = int(rays.shape[0])
     R = n if rays_per_frame is None else int(rays_per_frame)
     if R < 1 or n % R:
         raise ValueError(f"{n} rays are no whole number of frames of {R}")
+    dev = N.same_device(rays, grid.bits)
     pad = grid.cell_diagonal() if pad is None else float(pad)
     rays_out = torch.empty_like(rays)
     slot = torch.empty(n, dtype=torch.int32, device=dev)
@@ -200,16 +195,17 @@ def frame_from_hits(rec, slot, rays_per_frame, bg, out=None):
     """rec (n, >= 4) float32 rows [rgb, depth, ...] with row stride rec.stride(0), frame f's list from row f R on; slot (n) int32
     -> out (n, 4): [bg, bg, bg, 0] where slot < 0, the record's first four floats otherwise."""
     from .. import _native as N
+    if not N.arg(slot, "slot", torch.int32, (None,)).is_contiguous():
+        raise ValueError(f"slot must be contiguous, got stride {slot.stride()}")
     n, R = int(slot.shape[0]), int(rays_per_frame)
-    if rec.dim() != 2 or rec.dtype != torch.float32 or rec.shape[0] != n or rec.shape[1] < 4 or rec.stride(1) != 1:
-        raise ValueError(f"rec must be float32 ({n}, >= 4) with unit column stride, got {rec.dtype} {tuple(rec.shape)}")
-    if slot.dtype != torch.int32 or slot.dim() != 1 or not slot.is_contiguous():
-        raise ValueError("slot must be a contiguous int32 (n)")
-    dev = N.same_device(rec, slot)
+    # records and frames are rows of at least 4 floats at any row stride: a rule of this call's own, not N.out's exact shape
+    if N.arg(rec, "rec", torch.float32, (n, None)).shape[1] < 4 or rec.stride(1) != 1:
+        raise ValueError(f"rec must be float32 ({n}, >= 4) with unit column stride, got {tuple(rec.shape)} strides {rec.stride()}")
+    if out is not None and (N.arg(out, "out", torch.float32, (n, None)).shape[1] < 4 or out.stride(1) != 1):
+        raise ValueError(f"out must be float32 ({n}, >= 4) with unit column stride, got {tuple(out.shape)} strides {out.stride()}")
+    dev = N.same_device(rec, slot, out)
     if out is None:
         out = torch.empty(n, 4, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n or out.shape[1] < 4 or out.stride(1) != 1 or out.device != dev:
-        raise ValueError(f"out must be float32 ({n}, >= 4) on the records' device")
     N.check(N.lib.pnr_frame_from_hits(rec.data_ptr(), max(int(rec.stride(0)), 4), slot.data_ptr(),
                                       n, R, float(bg), out.data_ptr(), max(int(out.stride(0)), 4),
                                       N.current_stream(dev)), "pnr_frame_from_hits")

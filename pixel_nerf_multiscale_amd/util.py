@@ -285,15 +285,22 @@ def train_batch(images, poses, focal, c, pix_inds, z_near, z_far):
     device); pix_inds (SB, B) long on the device, view * H * W + row * W + col.  -> rays (SB, B, 8), rgb_gt (SB, B, 3) in
     [0, 1].  An index outside [0, NV*H*W) gives a NaN row (the indices are never read on the host)."""
     from . import _native as N
-    dev = N.same_device(images, poses, pix_inds)
-    if images.dim() != 5 or images.shape[2] != 3:
-        raise ValueError(f"images must be (SB, NV, 3, H, W), got {tuple(images.shape)}")
+    images = N.arg(images, "images", None, (None, None, 3, None, None))
     SB, NV, _, H, W = images.shape
-    if tuple(poses.shape) != (SB, NV, 4, 4):
-        raise ValueError(f"poses must be ({SB}, {NV}, 4, 4), got {tuple(poses.shape)}")
-    if pix_inds.dim() != 2 or pix_inds.shape[0] != SB or pix_inds.dtype != torch.long:
-        raise ValueError(f"pix_inds must be ({SB}, B) int64, got {tuple(pix_inds.shape)} {pix_inds.dtype}")
-    images, poses, pix_inds = N.f32c(images), N.f32c(poses), pix_inds.contiguous()
+    return _gather_batch(N, "pnr_train_batch", N.f32c(images), (SB, NV, H, W), poses, focal, c, pix_inds, z_near, z_far)
+
+
+def _gather_batch(N, entry, images, dims, poses, focal, c, pix_inds, z_near, z_far, *tail, jitter=None):
+    """What train_batch and train_batch_u8 share, from the checked image batch to the call of `entry`: poses and pix_inds are
+    checked, focal / c uploaded and expanded to (SB, 2), rays and rgb_gt allocated.  tail: the entry point's arguments behind
+    rgb_gt; a jitter record goes behind those.  N: the caller's _native."""
+    SB, NV, H, W = dims
+    poses = N.arg(poses, "poses", None, (SB, NV, 4, 4))
+    pix_inds = N.arg(pix_inds, "pix_inds", torch.long, (SB, None), contiguous=True)
+    if jitter is not None:
+        jitter = N.arg(jitter, "jitter", torch.float32, (SB, 8), contiguous=True)
+    dev = N.same_device(images, poses, pix_inds, jitter)
+    poses = N.f32c(poses)
     focal = upload(torch.as_tensor(focal, dtype=torch.float32), dev)
     if focal.dim() <= 1:
         focal = focal.reshape(-1, 1).expand(-1, 2)
@@ -303,35 +310,15 @@ def train_batch(images, poses, focal, c, pix_inds, z_near, z_far):
     B = pix_inds.shape[1]
     rays = torch.empty(SB, B, 8, device=dev)
     rgb_gt = torch.empty(SB, B, 3, device=dev)
-    N.check(N.lib.pnr_train_batch(N.ptr(images), N.ptr(poses), N.ptr(focal), N.ptr(c), SB, NV, W, H, float(z_near),
-                                  float(z_far), pix_inds.data_ptr(), B, N.ptr(rays), N.ptr(rgb_gt), N.current_stream(dev)),
-            "pnr_train_batch")
+    if jitter is not None:
+        tail += (N.ptr(jitter),)
+    N.check(getattr(N.lib, entry)(N.ptr(images), N.ptr(poses), N.ptr(focal), N.ptr(c), SB, NV, W, H, float(z_near), float(z_far),
+                                  pix_inds.data_ptr(), B, N.ptr(rays), N.ptr(rgb_gt), *tail, N.current_stream(dev)), entry)
     return rays, rgb_gt
 
 
-def _images_u8(images_u8):
-    """A uint8 batch (SB, NV, H, W, 3 | 4), made contiguous when it is not (a slice of a pool along its first axis is), and its
-    shape."""
-    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 5 or images_u8.shape[4] not in (3, 4):
-        raise ValueError(f"images_u8 must be uint8 (SB, NV, H, W, 3 | 4), got {getattr(images_u8, 'dtype', None)} "
-                         f"{tuple(getattr(images_u8, 'shape', ()))}")
-    return images_u8.contiguous(), tuple(int(s) for s in images_u8.shape)
-
-
-def _jitter_record(jitter, SB):
-    """A colour-jitter record for the gathers: float32 (SB, 8), contiguous (color_jitter_plan's output)."""
-    if not torch.is_tensor(jitter) or jitter.dtype != torch.float32 or tuple(jitter.shape) != (SB, 8):
-        raise ValueError(f"jitter must be a float32 ({SB}, 8) record, got {getattr(jitter, 'dtype', None)} "
-                         f"{tuple(getattr(jitter, 'shape', ()))}")
-    return jitter.contiguous()
-
-
-def _obj_base(obj_base):
-    """The first object of a call over a slice of a step's batch, as the keyed kernels take it."""
-    obj_base = int(obj_base)
-    if not 0 <= obj_base < 1 << 63:
-        raise ValueError(f"obj_base must be a non-negative int64, got {obj_base}")
-    return obj_base
+_U8_BATCH = (None, None, None, None, (3, 4))     # N.arg's shape of a uint8 batch (SB, NV, H, W, 3 | 4); a pool's slice is made contiguous
+_OBJ_BASE_END = 1 << 63                         # obj_base, the first object of a call over a slice of a step's batch, travels as int64
 
 
 def color_jitter_plan(images_u8, ranges, seed, out=None, obj_base=0):
@@ -345,17 +332,14 @@ def color_jitter_plan(images_u8, ranges, seed, out=None, obj_base=0):
     are those rows of the whole batch's plan, bit for bit."""
     from . import _native as N
     import ctypes
-    images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
+    images_u8 = N.arg(images_u8, "images_u8", torch.uint8, _U8_BATCH, contiguous=True)
+    SB, NV, H, W, C = images_u8.shape
     ranges = tuple(float(r) for r in getattr(ranges, "ranges", ranges))
-    seed, obj_base = int(seed), _obj_base(obj_base)
+    seed, obj_base = N.key64(seed, "seed"), N.key64(obj_base, "obj_base", _OBJ_BASE_END)
     if len(ranges) != 4:
         raise ValueError(f"ranges must be (brightness, contrast, saturation, hue), got {ranges}")
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
-    dev = N.same_device(images_u8, out)
-    rec = torch.empty(SB, 8, dtype=torch.float32, device=dev) if out is None else _jitter_record(out, SB)
-    if out is not None and rec.data_ptr() != out.data_ptr():
-        raise ValueError("out must be contiguous")
+    rec = N.out(out, "out", torch.float32, (SB, 8), images_u8.device)
+    dev = N.same_device(images_u8, rec)
     nbytes = int(N.lib.pnr_color_jitter_workspace_bytes(SB, NV, W, H)) if ranges[1] != 0.0 else 0
     ws = N.scratch(nbytes, dev)
     N.check(N.lib.pnr_color_jitter_plan_at(N.ptr(images_u8), SB, NV, W, H, C, (ctypes.c_float * 4)(*ranges), seed, obj_base,
@@ -372,30 +356,10 @@ def train_batch_u8(images_u8, poses, focal, c, pix_inds, z_near, z_far, balanced
     jitter: color_jitter_plan's record (SB, 8) — each sampled pixel goes through its object's colour chain between the
     division by 255 and the balanced map (pnr_train_batch_u8_jitter); None: the call and the bits without it."""
     from . import _native as N
-    images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
-    dev = N.same_device(images_u8, poses, pix_inds, jitter)
-    if tuple(poses.shape) != (SB, NV, 4, 4):
-        raise ValueError(f"poses must be ({SB}, {NV}, 4, 4), got {tuple(poses.shape)}")
-    if pix_inds.dim() != 2 or pix_inds.shape[0] != SB or pix_inds.dtype != torch.long:
-        raise ValueError(f"pix_inds must be ({SB}, B) int64, got {tuple(pix_inds.shape)} {pix_inds.dtype}")
-    poses, pix_inds = N.f32c(poses), pix_inds.contiguous()
-    focal = upload(torch.as_tensor(focal, dtype=torch.float32), dev)
-    if focal.dim() <= 1:
-        focal = focal.reshape(-1, 1).expand(-1, 2)
-    focal = focal.expand(SB, 2).contiguous()
-    if c is not None:
-        c = upload(torch.as_tensor(c, dtype=torch.float32), dev).reshape(-1, 2).expand(SB, 2).contiguous()
-    B = pix_inds.shape[1]
-    rays = torch.empty(SB, B, 8, device=dev)
-    rgb_gt = torch.empty(SB, B, 3, device=dev)
-    args = (N.ptr(images_u8), N.ptr(poses), N.ptr(focal), N.ptr(c), SB, NV, W, H, float(z_near), float(z_far), pix_inds.data_ptr(),
-            B, N.ptr(rays), N.ptr(rgb_gt), C, int(bool(balanced)))
-    if jitter is None:
-        N.check(N.lib.pnr_train_batch_u8(*args, N.current_stream(dev)), "pnr_train_batch_u8")
-    else:
-        N.check(N.lib.pnr_train_batch_u8_jitter(*args, N.ptr(_jitter_record(jitter, SB)), N.current_stream(dev)),
-                "pnr_train_batch_u8_jitter")
-    return rays, rgb_gt
+    images_u8 = N.arg(images_u8, "images_u8", torch.uint8, _U8_BATCH, contiguous=True)
+    SB, NV, H, W, C = images_u8.shape
+    return _gather_batch(N, "pnr_train_batch_u8" if jitter is None else "pnr_train_batch_u8_jitter", images_u8, (SB, NV, H, W), poses,
+                         focal, c, pix_inds, z_near, z_far, C, int(bool(balanced)), jitter=jitter)
 
 
 def views_to_tensor_u8(images_u8, view_ord, balanced=True, jitter=None):
@@ -406,19 +370,21 @@ def views_to_tensor_u8(images_u8, view_ord, balanced=True, jitter=None):
     jitter: color_jitter_plan's record (SB, 8) — every pixel of a selected view goes through its object's colour chain
     (pnr_views_to_tensor_u8_jitter); None: the call and the bits without it."""
     from . import _native as N
-    images_u8, (SB, NV, H, W, C) = _images_u8(images_u8)
-    dev = N.same_device(images_u8, view_ord, jitter)
-    if view_ord.dim() != 2 or view_ord.shape[0] != SB or view_ord.shape[1] < 1 or view_ord.dtype != torch.long:
-        raise ValueError(f"view_ord must be ({SB}, NS >= 1) int64, got {tuple(view_ord.shape)} {view_ord.dtype}")
-    view_ord = view_ord.contiguous()
+    images_u8 = N.arg(images_u8, "images_u8", torch.uint8, _U8_BATCH, contiguous=True)
+    SB, NV, H, W, C = images_u8.shape
+    view_ord = N.arg(view_ord, "view_ord", torch.long, (SB, None), contiguous=True)
     NS = int(view_ord.shape[1])
+    if NS < 1:
+        raise ValueError(f"view_ord must name at least one view per object, got {tuple(view_ord.shape)}")
+    if jitter is not None:
+        jitter = N.arg(jitter, "jitter", torch.float32, (SB, 8), contiguous=True)
+    dev = N.same_device(images_u8, view_ord, jitter)
     out = torch.empty(SB, NS, 3, H, W, dtype=torch.float32, device=dev)
     args = (N.ptr(images_u8), view_ord.data_ptr(), SB, NV, NS, W, H, C, int(bool(balanced)), N.ptr(out))
     if jitter is None:
         N.check(N.lib.pnr_views_to_tensor_u8(*args, N.current_stream(dev)), "pnr_views_to_tensor_u8")
     else:
-        N.check(N.lib.pnr_views_to_tensor_u8_jitter(*args, N.ptr(_jitter_record(jitter, SB)), N.current_stream(dev)),
-                "pnr_views_to_tensor_u8_jitter")
+        N.check(N.lib.pnr_views_to_tensor_u8_jitter(*args, N.ptr(jitter), N.current_stream(dev)), "pnr_views_to_tensor_u8_jitter")
     return out
 
 
@@ -433,30 +399,31 @@ def train_draw(bbox, SB, NV, W, H, B, NS, seed, out_pix=None, out_views=None, ob
     obj_base: the call draws objects obj_base .. obj_base + SB - 1 of the step's batch (pnr_train_draw_at; bbox and the outputs
     are those SB objects' rows): what it writes are those rows of the whole batch's draw, bit for bit."""
     from . import _native as N
-    SB, NV, W, H, B, NS, seed = int(SB), int(NV), int(W), int(H), int(B), int(NS), int(seed)
-    obj_base = _obj_base(obj_base)
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
+    SB, NV, W, H, B, NS = int(SB), int(NV), int(W), int(H), int(B), int(NS)
+    if bbox is not None:
+        bbox = N.arg(bbox, "bbox", torch.float32, (SB, NV, 4), contiguous=True)
+    seed, obj_base, pix, views, dev = _draw_setup(N, "train_draw", SB, NV, W, H, B, NS, seed, obj_base, out_pix, out_views, bbox)
+    N.check(N.lib.pnr_train_draw_at(N.dptr(bbox), SB, NV, W, H, B, NS, seed, obj_base,
+                                    pix.data_ptr() if B else None, views.data_ptr() if NS else None, N.current_stream(dev)),
+            "pnr_train_draw_at")
+    return pix, views
+
+
+def _draw_setup(N, what, SB, NV, W, H, B, NS, seed, obj_base, out_pix, out_views, t0, t1=None):
+    """What train_draw and train_draw_masked share, on sizes that are host ints already and input tensors (t0, t1; None where
+    there is none) that are checked already: the sizes' ranges, the two keys, the outputs, given or new, and the device of the
+    call: the one its tensors share, or the current one when there is none (no boxes, no outputs).  N: the caller's _native.
+    -> (seed, obj_base, pix, views, dev)."""
     if SB < 1 or NV < 1 or W < 1 or H < 1 or B < 0:
-        raise ValueError(f"train_draw needs SB, NV, W, H >= 1 and B >= 0, got {(SB, NV, W, H, B)}")
+        raise ValueError(f"{what} needs SB, NV, W, H >= 1 and B >= 0, got {(SB, NV, W, H, B)}")
     if not 0 <= NS <= min(NV, 64):
         raise ValueError(f"NS must lie in [0, min(NV, 64)] = [0, {min(NV, 64)}], got {NS}")
-    if bbox is not None:
-        if not torch.is_tensor(bbox) or bbox.dtype != torch.float32 or tuple(bbox.shape) != (SB, NV, 4):
-            raise ValueError(f"bbox must be float32 ({SB}, {NV}, 4), got {getattr(bbox, 'dtype', None)} "
-                             f"{tuple(getattr(bbox, 'shape', ()))}")
-        bbox = bbox.contiguous()
-    for name, t, shape in (("out_pix", out_pix, (SB, B)), ("out_views", out_views, (SB, NS))):
-        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.long or tuple(t.shape) != shape or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous int64 {shape} tensor, got {getattr(t, 'dtype', None)} "
-                             f"{tuple(getattr(t, 'shape', ()))}")
-    given = [t for t in (bbox, out_pix, out_views) if t is not None]
-    dev = N.same_device(*given) if given else torch.device("cuda", torch.cuda.current_device())
-    pix = torch.empty(SB, B, dtype=torch.long, device=dev) if out_pix is None else out_pix
-    views = torch.empty(SB, NS, dtype=torch.long, device=dev) if out_views is None else out_views
-    N.check(N.lib.pnr_train_draw_at(N.dptr(bbox), SB, NV, W, H, B, NS, seed, obj_base, pix.data_ptr() if B else None,
-                                    views.data_ptr() if NS else None, N.current_stream(dev)), "pnr_train_draw_at")
-    return pix, views
+    seed, obj_base = N.key64(seed, "seed"), N.key64(obj_base, "obj_base", _OBJ_BASE_END)
+    first = t0 if t0 is not None else out_pix if out_pix is not None else out_views
+    where = torch.device("cuda", torch.cuda.current_device()) if first is None else getattr(first, "device", None)
+    pix = N.out(out_pix, "out_pix", torch.long, (SB, B), where)
+    views = N.out(out_views, "out_views", torch.long, (SB, NS), where)
+    return seed, obj_base, pix, views, N.same_device(t0, t1, pix, views)
 
 
 def masked_sample(masks, num_pix, prop_inside, thresh=0.5):
@@ -524,15 +491,12 @@ def mask_table(masks, thresh=128, pix_stride=1, out=None):
         masks = mask_bytes(masks)
         if masks.dim() == 3:
             masks = masks[None]
-        if masks.dim() != 4:
-            raise ValueError(f"masks must be (N, NV, H, W) or (NV, H, W), got {tuple(masks.shape)}")
-        masks = masks.contiguous()
+        masks = N.arg(masks, "masks", torch.uint8, (None, None, None, None), contiguous=True)
         n, NV, H, W = (int(s) for s in masks.shape)
     else:
-        if not torch.is_tensor(masks) or masks.dtype != torch.uint8 or masks.dim() not in (4, 5):
-            raise ValueError("with pix_stride > 1 masks must be uint8 (N, NV, H, W, channels) or (NV, H, W, channels)")
-        if masks.dim() == 4:
+        if torch.is_tensor(masks) and masks.dim() == 4:
             masks = masks[None]
+        masks = N.arg(masks, "masks", torch.uint8, (None, None, None, None, None))
         n, NV, H, W = (int(s) for s in masks.shape[:4])
         want = (NV * H * W * pix_stride, H * W * pix_stride, W * pix_stride, pix_stride)
         if masks.shape[4] < 1 or any(masks.shape[d] > 1 and masks.stride(d) != want[d] for d in range(4)):
@@ -541,16 +505,12 @@ def mask_table(masks, thresh=128, pix_stride=1, out=None):
     if min(n, NV, H, W) < 1 or NV * H * W >= 1 << 31:
         raise ValueError(f"mask_table needs N, NV, H, W >= 1 and NV * H * W < 2^31, got {(n, NV, H, W)}")
     R, Wd = NV * H, (W + 31) // 32
-    if out is None:
-        dev = N.same_device(masks)
-        bits = torch.empty(n, R, Wd, dtype=torch.int32, device=dev)
-        rows = torch.empty(n, R + 1, dtype=torch.int32, device=dev)
-    else:
-        bits, rows = out
-        dev = N.same_device(masks, bits, rows)
-        for name, t, shape in (("bits", bits, (n, R, Wd)), ("rows", rows, (n, R + 1))):
-            if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"out {name} must be a contiguous int32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    bits, rows = (None, None) if out is None else out
+    if out is not None and (bits is None or rows is None):
+        raise ValueError("out must be a (bits, rows) pair of tensors")
+    bits = N.out(bits, "out bits", torch.int32, (n, R, Wd), masks.device)
+    rows = N.out(rows, "out rows", torch.int32, (n, R + 1), masks.device)
+    dev = N.same_device(masks, bits, rows)
     N.check(N.lib.pnr_mask_table_build(masks.data_ptr(), n, NV, H, W, pix_stride, thresh, bits.data_ptr(), rows.data_ptr(),
                                        N.current_stream(dev)), "pnr_mask_table_build")
     return bits, rows
@@ -564,27 +524,12 @@ def train_draw_masked(bits, rows, SB, NV, W, H, B, NS, seed, prop_inside, out_pi
     are train_draw's.  An object without inside (or without outside) pixels draws every slot from the population it has.
     Reads nothing back."""
     from . import _native as N
-    SB, NV, W, H, B, NS, seed = int(SB), int(NV), int(W), int(H), int(B), int(NS), int(seed)
-    obj_base = _obj_base(obj_base)
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
-    if SB < 1 or NV < 1 or W < 1 or H < 1 or B < 0:
-        raise ValueError(f"train_draw_masked needs SB, NV, W, H >= 1 and B >= 0, got {(SB, NV, W, H, B)}")
-    if not 0 <= NS <= min(NV, 64):
-        raise ValueError(f"NS must lie in [0, min(NV, 64)] = [0, {min(NV, 64)}], got {NS}")
+    SB, NV, W, H, B, NS = int(SB), int(NV), int(W), int(H), int(B), int(NS)
     B_inside = num_inside(B, prop_inside)
-    for name, t, shape in (("bits", bits, (SB, NV * H, (W + 31) // 32)), ("rows", rows, (SB, NV * H + 1))):
-        if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be int32 {shape} (mask_table), got {getattr(t, 'dtype', None)} "
-                             f"{tuple(getattr(t, 'shape', ()))}")
-    bits, rows = bits.contiguous(), rows.contiguous()
-    for name, t, shape in (("out_pix", out_pix, (SB, B)), ("out_views", out_views, (SB, NS))):
-        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.long or tuple(t.shape) != shape or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous int64 {shape} tensor, got {getattr(t, 'dtype', None)} "
-                             f"{tuple(getattr(t, 'shape', ()))}")
-    dev = N.same_device(bits, rows, out_pix, out_views)
-    pix = torch.empty(SB, B, dtype=torch.long, device=dev) if out_pix is None else out_pix
-    views = torch.empty(SB, NS, dtype=torch.long, device=dev) if out_views is None else out_views
+    bits = N.arg(bits, "bits", torch.int32, (SB, NV * H, (W + 31) // 32), contiguous=True)
+    rows = N.arg(rows, "rows", torch.int32, (SB, NV * H + 1), contiguous=True)
+    seed, obj_base, pix, views, dev = _draw_setup(N, "train_draw_masked", SB, NV, W, H, B, NS, seed, obj_base, out_pix, out_views,
+                                                  bits, rows)
     N.check(N.lib.pnr_train_draw_masked_at(bits.data_ptr(), rows.data_ptr(), SB, NV, W, H, B, B_inside, NS, seed, obj_base,
                                            pix.data_ptr() if B else None, views.data_ptr() if NS else None,
                                            N.current_stream(dev)), "pnr_train_draw_masked_at")
@@ -600,18 +545,13 @@ def mask_gather(bits, pix_inds, NV, H, W, out=None):
     NV, H, W = int(NV), int(H), int(W)
     if min(NV, H, W) < 1 or NV * H * W >= 1 << 31:
         raise ValueError(f"mask_gather needs NV, H, W >= 1 and NV * H * W < 2^31, got {(NV, H, W)}")
-    if not torch.is_tensor(pix_inds) or pix_inds.dim() != 2 or pix_inds.dtype != torch.long:
-        raise ValueError(f"pix_inds must be (SB, B) int64, got {getattr(pix_inds, 'dtype', None)} {tuple(getattr(pix_inds, 'shape', ()))}")
+    pix_inds = N.arg(pix_inds, "pix_inds", torch.long, (None, None), contiguous=True)
     SB, B = (int(x) for x in pix_inds.shape)
-    shape = (SB, NV * H, (W + 31) // 32)
-    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or tuple(bits.shape) != shape or SB < 1:
-        raise ValueError(f"bits must be int32 {shape} (mask_table), got {getattr(bits, 'dtype', None)} {tuple(getattr(bits, 'shape', ()))}")
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (SB, B) or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous float32 {(SB, B)} tensor, got {getattr(out, 'dtype', None)} "
-                         f"{tuple(getattr(out, 'shape', ()))}")
-    dev = N.same_device(bits, pix_inds, out)
-    bits, pix_inds = bits.contiguous(), pix_inds.contiguous()
-    mask = torch.empty(SB, B, device=dev) if out is None else out
+    if SB < 1:
+        raise ValueError(f"pix_inds must hold at least one object, got {tuple(pix_inds.shape)}")
+    bits = N.arg(bits, "bits", torch.int32, (SB, NV * H, (W + 31) // 32), contiguous=True)
+    mask = N.out(out, "out", torch.float32, (SB, B), bits.device)
+    dev = N.same_device(bits, pix_inds, mask)
     N.check(N.lib.pnr_mask_gather(bits.data_ptr(), SB, NV, H, W, pix_inds.data_ptr(), B, mask.data_ptr(), N.current_stream(dev)),
             "pnr_mask_gather")
     return mask
@@ -621,15 +561,27 @@ def _record_stride(t, lead, last, name):
     """Floats per element of a tensor of shape lead [+ (last,)] — lead = (H, W) for a frame, (n,) for per-ray outputs — that is
     dense or a regular view into a packed per-element record: unit stride inside the element and, for a frame, row-major
     pixels ((H, W, 3) with strides (W s, s, 1), (H, W) with (W s, s); (n, last) with (s, 1), (n,) with s)."""
-    want = (*lead, last) if last else tuple(lead)
-    if tuple(t.shape) != want or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32 {want}, got {t.dtype} {tuple(t.shape)}")
+    from . import _native as N
+    N.arg(t, name, torch.float32, (*lead, last) if last else tuple(lead))
     if t.is_contiguous():
         return max(last, 1)
     st, k = t.stride(), len(lead)
     s = st[k - 1]
     if s < max(last, 1) or (last > 1 and st[k] != 1) or (k == 2 and lead[0] > 1 and st[0] != lead[1] * s):
         raise ValueError(f"{name} must be dense or a view into a per-{'pixel' if k == 2 else 'ray'} record, got strides {st}")
+    return s
+
+
+def _field_stride(t, name):
+    """Floats per sample of a float32 (nx, ny, nz) field that is dense or a regularly strided view — one column of a per-point
+    record, read where it lies —: strides (ny nz s, nz s, s) with s >= 1.  What recon.extract_mesh and
+    OccupancyGrid.from_sigma take."""
+    from . import _native as N
+    _, ny, nz = N.arg(t, name, torch.float32, (None, None, None)).shape
+    st = t.stride()
+    s = int(st[2])
+    if s < 1 or st[1] != nz * s or st[0] != ny * nz * s:
+        raise ValueError(f"{name} must be dense or a regularly strided view of a per-point record, got strides {st}")
     return s
 
 
@@ -642,9 +594,7 @@ def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True,
     metrics_out: a contiguous (2,) float64 device tensor to write the pair into (one row of a per-object buffer).  Nothing
     here waits for the device; PSNR = 10 log10(1 / metrics[0]) is the caller's, on the host."""
     from . import _native as N
-    if rgb.dim() != 3 or rgb.shape[2] != 3:
-        raise ValueError(f"rgb must be (H, W, 3), got {tuple(rgb.shape)}")
-    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    H, W = (int(s) for s in N.arg(rgb, "rgb", torch.float32, (None, None, 3)).shape[:2])
     if (want_compare or want_metrics) and gt is None:
         raise ValueError("want_compare / want_metrics need the ground truth gt")
     if want_depth and depth is None:
@@ -653,22 +603,18 @@ def eval_frame(rgb, depth=None, gt=None, *, z_near=0.0, z_far=1.0, want_u8=True,
         depth = None
     if not (want_compare or want_metrics):
         gt = None
-    dev = N.same_device(rgb, depth, gt, metrics_out)
     rs = _record_stride(rgb, (H, W), 3, "rgb")
     ds = 0 if depth is None else _record_stride(depth, (H, W), 0, "depth")
     if gt is not None:
-        if tuple(gt.shape) != (3, H, W) or gt.dtype != torch.float32:
-            raise ValueError(f"gt must be float32 (3, {H}, {W}), got {gt.dtype} {tuple(gt.shape)}")
-        gt = gt.contiguous()
+        gt = N.arg(gt, "gt", torch.float32, (3, H, W), contiguous=True)
+    metrics = N.out(metrics_out, "metrics_out", torch.float64, (2,), rgb.device) if want_metrics else None
+    dev = N.same_device(rgb, depth, gt, metrics_out)
     rgb_u8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if want_u8 else None
     compare_u8 = torch.empty(H, 2 * W, 3, dtype=torch.uint8, device=dev) if want_compare else None
     depth_norm = torch.empty(H, W, dtype=torch.float32, device=dev) if want_depth else None
-    metrics = ws = None
+    ws = None
     nbytes = 0
     if want_metrics:
-        metrics = torch.empty(2, dtype=torch.float64, device=dev) if metrics_out is None else metrics_out
-        if tuple(metrics.shape) != (2,) or metrics.dtype != torch.float64 or not metrics.is_contiguous():
-            raise ValueError(f"metrics_out must be a contiguous float64 (2,), got {metrics.dtype} {tuple(metrics.shape)}")
         nbytes = int(N.lib.pnr_eval_frame_workspace_bytes(W, H))
         ws = N.scratch(nbytes, dev)
     N.check(N.lib.pnr_eval_frame(rgb.data_ptr(), rs, N.dptr(depth), ds, N.dptr(gt), W, H, float(z_near), float(z_far),
@@ -686,22 +632,19 @@ def eval_frames(rgb, gt, *, clamp=False, metrics_out=None):
     -> (F, 2) float64 on the device, rows [mean squared error, mean SSIM]; metrics_out: a contiguous (F, 2) float64 device
     tensor to write into.  Nothing here waits for the device; PSNR = 10 log10(1 / mse) is the caller's, on the host."""
     from . import _native as N
-    if gt.dim() != 4 or gt.shape[1] != 3 or gt.dtype != torch.float32:
-        raise ValueError(f"gt must be float32 (F, 3, H, W), got {gt.dtype} {tuple(gt.shape)}")
+    gt = N.arg(gt, "gt", torch.float32, (None, 3, None, None), contiguous=True)
     F, _, H, W = (int(s) for s in gt.shape)
-    if F < 1 or rgb.dim() not in (3, 4) or rgb.shape[0] != F:
-        raise ValueError(f"rgb must be ({F}, {H}, {W}, 3) or ({F}, {H * W}, 3) with F >= 1, got {tuple(rgb.shape)}")
-    dev = N.same_device(rgb, gt, metrics_out)
+    if F < 1:
+        raise ValueError(f"gt must hold at least one frame, got {tuple(gt.shape)}")
+    N.arg(rgb, "rgb", torch.float32, (F, H * W, 3) if torch.is_tensor(rgb) and rgb.dim() == 3 else (F, H, W, 3))
     rs = _record_stride(rgb[0], (H, W) if rgb.dim() == 4 else (H * W,), 3, "a frame of rgb")
     fs = 0
     if F > 1:
         fs = int(rgb.stride(0))
         if fs < H * W * rs:
             raise ValueError(f"the frames of rgb must follow each other at >= {H * W * rs} floats, got strides {rgb.stride()}")
-    gt = gt.contiguous()
-    metrics = torch.empty(F, 2, dtype=torch.float64, device=dev) if metrics_out is None else metrics_out
-    if tuple(metrics.shape) != (F, 2) or metrics.dtype != torch.float64 or not metrics.is_contiguous():
-        raise ValueError(f"metrics_out must be a contiguous float64 ({F}, 2), got {metrics.dtype} {tuple(metrics.shape)}")
+    metrics = N.out(metrics_out, "metrics_out", torch.float64, (F, 2), gt.device)
+    dev = N.same_device(rgb, gt, metrics)
     nbytes = int(N.lib.pnr_eval_frames_workspace_bytes(F, W, H))
     ws = N.scratch(nbytes, dev)
     N.check(N.lib.pnr_eval_frames(rgb.data_ptr(), rs, fs, gt.data_ptr(), F, W, H, int(bool(clamp)), metrics.data_ptr(),
@@ -718,17 +661,13 @@ def eval_frames_u8(pred_u8, gt_u8, *, want_planar=False, metrics_out=None):
     gt_planar), the two (F, 3, H, W) float32 tensors x * 2 - 1, the LPIPS inputs of :232-233.  metrics_out: a contiguous
     (F, 2) float64 device tensor to write into.  Nothing here waits for the device; PSNR is the caller's, on the host."""
     from . import _native as N
-    for name, t in (("pred_u8", pred_u8), ("gt_u8", gt_u8)):
-        if t.dim() != 4 or t.dtype != torch.uint8 or t.shape[3] not in (3, 4):
-            raise ValueError(f"{name} must be uint8 (F, H, W, 3 or 4), got {t.dtype} {tuple(t.shape)}")
+    pred_u8 = N.arg(pred_u8, "pred_u8", torch.uint8, (None, None, None, (3, 4)), contiguous=True)
     F, H, W, pc = (int(s) for s in pred_u8.shape)
-    if F < 1 or tuple(gt_u8.shape[:3]) != (F, H, W):
-        raise ValueError(f"gt_u8 must be ({F}, {H}, {W}, 3 or 4) with F >= 1, got {tuple(gt_u8.shape)}")
-    dev = N.same_device(pred_u8, gt_u8, metrics_out)
-    pred_u8, gt_u8 = pred_u8.contiguous(), gt_u8.contiguous()
-    metrics = torch.empty(F, 2, dtype=torch.float64, device=dev) if metrics_out is None else metrics_out
-    if tuple(metrics.shape) != (F, 2) or metrics.dtype != torch.float64 or not metrics.is_contiguous():
-        raise ValueError(f"metrics_out must be a contiguous float64 ({F}, 2), got {metrics.dtype} {tuple(metrics.shape)}")
+    if F < 1:
+        raise ValueError(f"pred_u8 must hold at least one frame, got {tuple(pred_u8.shape)}")
+    gt_u8 = N.arg(gt_u8, "gt_u8", torch.uint8, (F, H, W, (3, 4)), contiguous=True)
+    metrics = N.out(metrics_out, "metrics_out", torch.float64, (F, 2), pred_u8.device)
+    dev = N.same_device(pred_u8, gt_u8, metrics)
     pred_planar = torch.empty(F, 3, H, W, dtype=torch.float32, device=dev) if want_planar else None
     gt_planar = torch.empty(F, 3, H, W, dtype=torch.float32, device=dev) if want_planar else None
     nbytes = int(N.lib.pnr_eval_frames_u8_workspace_bytes(F, W, H))
@@ -799,10 +738,9 @@ def upsample_concat(levels, half_dtype=None):
         raise ValueError(f"upsample_concat takes 1..{N.PNR_MAX_LEVELS} levels, got {len(levels)}")
     if half_dtype not in (None, torch.float16, torch.bfloat16):
         raise ValueError(f"half_dtype must be None, torch.float16 or torch.bfloat16, got {half_dtype}")
-    for l in levels:
-        if l.dim() != 4 or l.dtype != torch.float32 or l.shape[0] != levels[0].shape[0]:
-            raise ValueError(f"every level must be float32 (N, C, H, W) with one N, got {l.dtype} {tuple(l.shape)}")
-    return _UpsampleConcat.apply(half_dtype, *[l.contiguous() for l in levels])
+    levels = [N.arg(l, f"level {i} (all of one N)", torch.float32, (levels[0].shape[0] if i else None, None, None, None), contiguous=True)
+              for i, l in enumerate(levels)]
+    return _UpsampleConcat.apply(half_dtype, *levels)
 
 
 # ------------------------------------------------------------------------------------------- colour map and the vis_step panel
@@ -839,10 +777,15 @@ def image_float_to_uint8(img):
 def cmap(img, lut=None):
     """The reference's util.cmap (src/util/util.py:26-30) on the host in pure numpy, with the colour table as data:
     lut[image_float_to_uint8(img)] -> (H, W, 3) uint8.  lut (256, 3) uint8; None = hot_lut() (parity unpinned, see there)."""
-    lut = hot_lut() if lut is None else np.asarray(lut)
-    if lut.shape != (256, 3) or lut.dtype != np.uint8:
-        raise ValueError(f"lut must be uint8 (256, 3), got {lut.dtype} {lut.shape}")
+    lut = hot_lut() if lut is None else _checked_lut(np.asarray(lut), np.uint8)
     return lut[image_float_to_uint8(img)]
+
+
+def _checked_lut(lut, uint8):
+    """A colour table, array or tensor, that is (256, 3) of its library's uint8."""
+    if tuple(lut.shape) != (256, 3) or lut.dtype != uint8:
+        raise ValueError(f"lut must be uint8 (256, 3), got {lut.dtype} {tuple(lut.shape)}")
+    return lut
 
 
 _LUT_CACHE = {}
@@ -858,9 +801,7 @@ def _device_lut(lut, dev):
         return t
     if not torch.is_tensor(lut):
         lut = torch.from_numpy(np.ascontiguousarray(lut))
-    if tuple(lut.shape) != (256, 3) or lut.dtype != torch.uint8:
-        raise ValueError(f"lut must be uint8 (256, 3), got {lut.dtype} {tuple(lut.shape)}")
-    return upload(lut, dev).contiguous()
+    return upload(_checked_lut(lut, torch.uint8), dev).contiguous()
 
 
 def cmap_device(map, lut=None):
@@ -869,9 +810,7 @@ def cmap_device(map, lut=None):
     lut: (256, 3) uint8, numpy or tensor; None = hot_lut(), uploaded once per device (parity unpinned, see hot_lut).  Nothing
     here waits for the device."""
     from . import _native as N
-    if not torch.is_tensor(map) or map.dim() != 2:
-        raise ValueError(f"map must be a float32 (H, W) tensor, got {tuple(getattr(map, 'shape', ()))}")
-    H, W = int(map.shape[0]), int(map.shape[1])
+    H, W = (int(s) for s in N.arg(map, "map", torch.float32, (None, None)).shape)
     stride = _record_stride(map, (H, W), 0, "map")
     dev = N.same_device(map)
     lut = _device_lut(lut, dev)
@@ -903,8 +842,7 @@ def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, wa
     -> VisPanel; everything stays on the device and nothing waits.  lut as in cmap_device.  include/pnr.h fixes the arithmetic
     (alpha is an fp64 sum in ascending k, not torch's .sum(-1); the default table is parity unpinned)."""
     from . import _native as N
-    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
-        raise ValueError(f"images must be float32 (NV, 3, H, W), got {images.dtype} {tuple(images.shape)}")
+    images = N.arg(images, "images", torch.float32, (None, 3, None, None), contiguous=True)
     NV, _, H, W = (int(s) for s in images.shape)
     src = [int(v) for v in (src_views.tolist() if hasattr(src_views, "tolist") else src_views)]
     NS, n_pass = len(src), len(passes)
@@ -912,20 +850,16 @@ def vis_panel(images, src_views, gt_view, passes, *, lut=None, want_f32=True, wa
         raise ValueError(f"vis_panel takes 1..{N.PNR_VIS_MAX_SRC} source views, got {NS}")
     if n_pass not in (1, 2):
         raise ValueError(f"vis_panel takes one or two passes, got {n_pass}")
-    images = images.contiguous()
-    dev = N.same_device(images, *[t for ps in passes for t in ps])
-    lut = _device_lut(lut, dev)
-    N.same_device(images, lut)
     arr = (N.pnr_vis_pass * n_pass)()
     for i, (rgb, depth, weights) in enumerate(passes):
-        if weights.dim() != 2:
-            raise ValueError(f"weights must be (H*W, K), got {tuple(weights.shape)}")
-        K = int(weights.shape[1])
-        arr[i].rgb, arr[i].depth, arr[i].weights = rgb.data_ptr(), depth.data_ptr(), weights.data_ptr()
+        K = arr[i].K = int(N.arg(weights, "weights", torch.float32, (H * W, None)).shape[1])
         arr[i].rgb_stride = _record_stride(rgb, (H * W,), 3, "rgb")
         arr[i].depth_stride = _record_stride(depth, (H * W,), 0, "depth")
         arr[i].weights_stride = _record_stride(weights, (H * W,), K, "weights")
-        arr[i].K = K
+        arr[i].rgb, arr[i].depth, arr[i].weights = rgb.data_ptr(), depth.data_ptr(), weights.data_ptr()
+    dev = N.same_device(images, *[t for ps in passes for t in ps])
+    lut = _device_lut(lut, dev)
+    N.same_device(images, lut)
     panel = torch.empty(n_pass * H, (NS + 4) * W, 3, dtype=torch.float32, device=dev) if want_f32 else None
     panel_u8 = torch.empty(n_pass * H, (NS + 4) * W, 3, dtype=torch.uint8, device=dev) if want_u8 else None
     alpha = torch.empty(n_pass, H, W, dtype=torch.float32, device=dev) if want_alpha else None
@@ -951,21 +885,20 @@ def video_frames(rgb, F, H, W, out=None, count=None):
     from . import _native as N
     F, H, W = int(F), int(H), int(W)
     P = F * H * W
-    if not torch.is_tensor(rgb) or rgb.dtype != torch.float32:
-        raise ValueError(f"rgb must be a float32 tensor, got {getattr(rgb, 'dtype', type(rgb))}")
-    if rgb.is_contiguous() and rgb.numel() == 3 * P:
+    if N.arg(rgb, "rgb", torch.float32, (...,)).is_contiguous() and rgb.numel() == 3 * P:
         stride = 3
     else:
         stride = _record_stride(rgb, (P,), 3, "rgb")
+    # out and count are "N elements of any shape", which N.out's exact shape does not say: their rule stays written out here
+    if out is not None and (out.dtype != torch.uint8 or out.numel() != 3 * P or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of {3 * P} elements, got {out.dtype} {tuple(out.shape)}")
+    if count is not None and (count.dtype != torch.int64 or count.numel() != 1 or not count.is_contiguous()):
+        raise ValueError(f"count must be a contiguous int64 tensor of one element, got {count.dtype} {tuple(count.shape)}")
     dev = N.same_device(rgb, out, count)
     if out is None:
         out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or out.numel() != 3 * P or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous uint8 tensor of {3 * P} elements, got {out.dtype} {tuple(out.shape)}")
     if count is None:
         count = torch.empty((), dtype=torch.int64, device=dev)
-    elif count.dtype != torch.int64 or count.numel() != 1 or not count.is_contiguous():
-        raise ValueError(f"count must be a contiguous int64 tensor of one element, got {count.dtype} {tuple(count.shape)}")
     N.check(N.lib.pnr_video_frames(rgb.data_ptr(), stride, F, W, H, out.data_ptr(), count.data_ptr(), N.current_stream(dev)),
             "pnr_video_frames")
     return out.view(F, H, W, 3), count
@@ -977,16 +910,10 @@ def view_strip(images, scale=0.5, lo=0.5, out=None):
     np.hstack of ((x * scale + lo) * 255).astype(np.uint8) over the views, with video_frames' saturation outside numpy's
     range.  scale = lo = 0.5 for a [-1, 1] input, scale = 1, lo = 0 for [0, 1]."""
     from . import _native as N
-    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
-        raise ValueError(f"images must be a float32 (NS, 3, H, W) tensor, got {getattr(images, 'dtype', None)} "
-                         f"{tuple(getattr(images, 'shape', ()))}")
+    images = N.arg(images, "images", torch.float32, (None, 3, None, None), contiguous=True)
     NS, _, H, W = (int(s) for s in images.shape)
-    images = images.contiguous()
+    out = N.out(out, "out", torch.uint8, (H, NS * W, 3), images.device)
     dev = N.same_device(images, out)
-    if out is None:
-        out = torch.empty(H, NS * W, 3, dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (H, NS * W, 3) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous uint8 ({H}, {NS * W}, 3), got {out.dtype} {tuple(out.shape)}")
     N.check(N.lib.pnr_view_strip(images.data_ptr(), NS, W, H, float(scale), float(lo), out.data_ptr(), N.current_stream(dev)),
             "pnr_view_strip")
     return out
@@ -1001,8 +928,7 @@ def image_to_tensor(img_u8, balanced=False, device="cuda"):
     from . import _native as N
     if not torch.is_tensor(img_u8):
         img_u8 = torch.from_numpy(np.ascontiguousarray(img_u8))
-    if img_u8.dim() != 3 or img_u8.shape[2] != 3 or img_u8.dtype != torch.uint8:
-        raise ValueError(f"img_u8 must be uint8 (H, W, 3), got {img_u8.dtype} {tuple(img_u8.shape)}")
+    N.arg(img_u8, "img_u8", torch.uint8, (None, None, 3))
     if not img_u8.is_cuda:
         img_u8 = upload(img_u8.contiguous(), torch.device(device))
     img_u8 = img_u8.contiguous()
@@ -1025,14 +951,6 @@ def _target_size(size):
     return size
 
 
-def _resize_out(out, shape, dtype, dev):
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous {dtype} {tuple(shape)}, got {out.dtype} {tuple(out.shape)}")
-    return out
-
-
 def resize_area_u8(images_u8, size, out=None):
     """8-bit images at another size, by area resampling on the GPU by libpnr_hip (pnr_resize_area_u8; include/pnr.h writes the
     arithmetic down): images_u8 (..., H, W, C) uint8 on the device, C = 1..4 and any leading dimensions — (H, W, C),
@@ -1043,16 +961,13 @@ def resize_area_u8(images_u8, size, out=None):
     target.  out: a contiguous uint8 tensor of the result's shape to write into, at any byte offset of a larger buffer (a
     pool's slot).  Nothing here waits for the device."""
     from . import _native as N
-    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() < 3 or not 1 <= images_u8.shape[-1] <= 4:
-        raise ValueError(f"images_u8 must be uint8 (..., H, W, 1..4), got {getattr(images_u8, 'dtype', None)} "
-                         f"{tuple(getattr(images_u8, 'shape', ()))}")
+    images_u8 = N.arg(images_u8, "images_u8", torch.uint8, (..., None, None, (1, 2, 3, 4)), contiguous=True)
     Ht, Wt = _target_size(size)
-    images_u8 = images_u8.contiguous()
     lead = tuple(int(s) for s in images_u8.shape[:-3])
     H, W, C = (int(s) for s in images_u8.shape[-3:])
     F = math.prod(lead)
+    out = N.out(out, "out", torch.uint8, lead + (Ht, Wt, C), images_u8.device)
     dev = N.same_device(images_u8, out)
-    out = _resize_out(out, lead + (Ht, Wt, C), torch.uint8, dev)
     N.check(N.lib.pnr_resize_area_u8(images_u8.data_ptr(), H * W * C, F, H, W, C, out.data_ptr(), Ht * Wt * C, Ht, Wt,
                                      N.current_stream(dev)), "pnr_resize_area_u8")
     return out
@@ -1065,15 +980,12 @@ def resize_area(images, size, out=None):
     rounding.  A NaN or Inf reaches exactly the windows that contain it.  size and out as for resize_area_u8 (out float32).
     Nothing here waits for the device."""
     from . import _native as N
-    if not torch.is_tensor(images) or images.dtype != torch.float32 or images.dim() < 2:
-        raise ValueError(f"images must be float32 (..., H, W), got {getattr(images, 'dtype', None)} "
-                         f"{tuple(getattr(images, 'shape', ()))}")
+    images = N.arg(images, "images", torch.float32, (..., None, None), contiguous=True)
     Ht, Wt = _target_size(size)
-    images = images.contiguous()
     lead = tuple(int(s) for s in images.shape[:-2])
     H, W = int(images.shape[-2]), int(images.shape[-1])
+    out = N.out(out, "out", torch.float32, lead + (Ht, Wt), images.device)
     dev = N.same_device(images, out)
-    out = _resize_out(out, lead + (Ht, Wt), torch.float32, dev)
     N.check(N.lib.pnr_resize_area_f32(images.data_ptr(), math.prod(lead), H, W, out.data_ptr(), Ht, Wt, N.current_stream(dev)),
             "pnr_resize_area_f32")
     return out
