@@ -41,7 +41,8 @@ extern "C" {
                                   * pnr_adam_step_div; area resampling of images, pnr_resize_area_u8 / pnr_resize_area_f32; empty-space
                                   * culling, pnr_occ_build / pnr_ray_bounds_workspace_bytes / pnr_ray_bounds / pnr_frame_from_hits;
                                   * mask-weighted training draws, pnr_mask_table_build / pnr_train_draw_masked /
-                                  * pnr_train_draw_masked_at; the opacity losses, pnr_mask_gather / pnr_alpha_loss / pnr_alpha_loss_bwd */
+                                  * pnr_train_draw_masked_at; the opacity losses, pnr_mask_gather / pnr_alpha_loss / pnr_alpha_loss_bwd;
+                                  * procedural datasets, pnr_synth_render */
 #define PNR_MAX_LEVELS 5         /* encoder levels of a multi-scale latent (encoder.py:62-73) */
 #define PNR_MAX_BLOCKS 8         /* ResnetFC blocks (resnetfc.py:147) */
 
@@ -1126,6 +1127,69 @@ int32_t pnr_ray_bounds(const float* rays, int64_t n, int64_t rays_per_frame, con
                        float* rays_out, int32_t* slot_out, int64_t* counts_out, void* stream);
 int32_t pnr_frame_from_hits(const float* rec, int32_t rec_stride, const int32_t* slot, int64_t n, int64_t rays_per_frame, float bg,
                             float* out, int32_t out_stride, void* stream);
+
+/* ---- procedural datasets: analytic shapes ray-cast into SRN-form frames, csrc/synth.hip ------------------------------------------
+ *
+ * A data source that needs no files: objects made of a few ellipsoids and boxes, ray-cast exactly into the bytes an SRN folder
+ * would hold (white background, mask = "no channel is 255"), with the ground-truth depth.  The reference's counterpart is
+ * scripts/render_shapenet.py (Blender over ShapeNet); nothing of it is restated here.  This text is the specification;
+ * tests/synth_util.py restates it in numpy.
+ *
+ * Scenes.  scenes (n_scenes, P, PNR_SYNTH_REC) floats, P <= PNR_SYNTH_MAX_PRIMS.  One record per primitive:
+ *     [0]      kind: 0 = none, 1 = ellipsoid, 2 = box (compared as floats; any other value is none)
+ *     [1:4]    centre c
+ *     [4:13]   R, world -> local rotation, row major: local = R (world - c)
+ *     [13:16]  half-extents h (semi-axes of the ellipsoid, half edge lengths of the box), > 0
+ *     [16:19]  albedo
+ *     [19]     padding
+ * Frames.  Frame f shows scene scene_ids[f] (int32; an index outside [0, n_scenes) gives a background frame: the kernel is the
+ * range check) from poses[f], a row-major 4 x 4 camera-to-world matrix in the convention of pnr_gen_rays (x right, y up, the
+ * camera looks down -z): C = its upper-left 3 x 3, o = its last column.
+ *
+ * ALL in fp32, every product, sum, quotient and square root rounded on its own (no fused multiply-add), division and square
+ * root IEEE.  dot(a, b) = (a0 b0 + a1 b1) + a2 b2.  Sub-sample (a, b), a, b = 0 .. ss - 1, of pixel (row, col):
+ *   1. x = (float)col + off_a, y = (float)row + off_b, off_k = (k + 0.5) / ss - 0.5 (exact).  u = (x - cx) / fx,
+ *      v = -((y - cy) / fy), len = sqrt((u u + v v) + 1), dc = (u / len, v / len, -1 / len), d_i = dot(C_i, dc) (C_i = row i).
+ *      With ss = 1 this is pnr_gen_rays' pixel, without a half-pixel shift.
+ *   2. Per primitive p = 0 .. P - 1 that is not none: q = o - c, ol_i = dot(R_i, q), dl_i = dot(R_i, d).
+ *      ellipsoid:  tc = -dot(ol, dl), os_i = ol_i + tc dl_i: the origin moved along the ray to the primitive's side, so that B
+ *                  below is small and the discriminant does not cancel.  oe_i = os_i / h_i, de_i = dl_i / h_i (the unit sphere);
+ *                  A = dot(de, de), B = dot(oe, de), Cq = dot(oe, oe) - 1; disc = B B - A Cq; a hit needs disc > 0;
+ *                  tp = (-B - sqrt(disc)) / A (the smaller root), t = tc + tp; a hit needs t > 0.
+ *      box:        tn = -inf, tf = +inf, face = 0.  For a = 0, 1, 2 in this order: if dl_a == 0 the axis contributes no bound
+ *                  and the primitive is missed iff |ol_a| > h_a; else t1 = (-h_a - ol_a) / dl_a, t2 = (h_a - ol_a) / dl_a,
+ *                  lo = t2 if t2 < t1 else t1, hi = t2 if t2 > t1 else t1; if lo > tn then tn = lo and face = a; if hi < tf
+ *                  then tf = hi.  A hit needs tn < tf and tn > 0; t = tn.
+ *      The hit with the smallest t wins; best starts at +inf and is replaced only by t < best, so a tie goes to the lower index
+ *      and a NaN or Inf never wins.
+ *   3. Normal of the winner.  ellipsoid: g_i = (oe_i + tp de_i) / h_i, m_j = (R_0j g_0 + R_1j g_1) + R_2j g_2,
+ *      n = m / sqrt(dot(m, m)).  box: s = -1 if dl_face > 0 else 1, n_j = R_face,j s.
+ *   4. k = dot(n, l); k = k if k > 0 else 0; shade = ambient + one_minus k; colour_c = albedo_c shade.  A miss has colour 1.
+ *      Host side: l = (float)(light / |light|) with the norm and the quotient in fp64, one_minus = 1.0f - ambient in fp32.
+ * Per pixel: acc_c = 0, then acc_c = acc_c + colour_c over the sub-samples in the order b = 0 .. ss - 1 (outer), a = 0 .. ss - 1
+ * (inner); mean_c = acc_c inv, inv = 1 / ss^2 (a power of two); w = mean_c 255 + 0.5; byte = 0 unless w > 0, 255 for w >= 255,
+ * else (int)floor(w).  If any sub-sample hit: mask = 255 and every channel byte = min(byte, 254).  If none hit the bytes are
+ * 255, 255, 255 and the mask is 0.  So SRNDataset's rule mask = (img != 255).all(-1) reads the mask back from the bytes.
+ * depth = t of the FIRST sub-sample (a = b = 0; the pixel centre for ss = 1) when that one hit, else +inf; t is the parameter
+ * along d, which has unit length to fp32 rounding.
+ *
+ * Outputs.  rgb_out: frame f at rgb_out + f rgb_frame_stride bytes, (H, W, 3) bytes interleaved; rgb_frame_stride >= 3 H W (a
+ * pool slot, or a margin between frames); nothing outside the frames' 3 H W bytes is written.  mask_out (F, H, W) bytes and
+ * depth_out (F, H, W) floats are dense and optional (NULL).  One workgroup covers a run of 256 pixels of one frame and loads
+ * the scene's records (and ol) once; a thread owns four neighbouring pixels and writes their 12 colour bytes as three dwords
+ * where the address is 4-byte aligned and the four pixels exist, else byte by byte.  One launch, no atomics, no workspace.
+ *     PNR_E_NULL   scenes, scene_ids, poses or rgb_out NULL
+ *     PNR_E_SHAPE  n_scenes < 0, P < 1 or P > PNR_SYNTH_MAX_PRIMS, F, W or H < 1, F H W >= 2^31, F ceil(H W / 256) >= 2^26 (the
+ *                  threads of one launch), rgb_frame_stride < 3 H W,
+ *                  ss not 1, 2 or 4, fx or fy zero or not finite, cx or cy not finite, ambient outside [0, 1] (NaN included),
+ *                  a light vector that is zero or not finite
+ *     PNR_E_ALIGN  scenes, scene_ids, poses or depth_out not 4-byte aligned */
+#define PNR_SYNTH_MAX_PRIMS 8
+#define PNR_SYNTH_REC 20
+int32_t pnr_synth_render(const float* scenes, int32_t n_scenes, int32_t P, const int32_t* scene_ids, const float* poses, int32_t F,
+                         int32_t W, int32_t H, float fx, float fy, float cx, float cy, int32_t ss, float ambient, float light_x,
+                         float light_y, float light_z, uint8_t* rgb_out, int64_t rgb_frame_stride, uint8_t* mask_out,
+                         float* depth_out, void* stream);
 
 /* Timing hook for bench.py: microseconds between the first and last point-MLP launch of the most recent
  * pnr_render on this thread is NOT kept (no global state); instead the caller brackets calls with

@@ -15,6 +15,8 @@ PNR_MAX_LEVELS = 5
 PNR_MAX_BLOCKS = 8
 PNR_VIS_MAX_SRC = 8
 PNR_JITTER_BLOCK = 4096
+PNR_SYNTH_MAX_PRIMS = 8
+PNR_SYNTH_REC = 20
 PNR_F32, PNR_BF16, PNR_F16 = 0, 1, 2
 PNR_BF16X3 = 3     # training entry points only
 PRECISIONS = {"fp32": PNR_F32, "f32": PNR_F32, "bf16": PNR_BF16, "fp16": PNR_F16, "f16": PNR_F16, "bf16x3": PNR_BF16X3}
@@ -212,6 +214,8 @@ PROTOTYPES = {
     "pnr_ray_bounds": (_i32, [_fp, _i64, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), _fp, C.c_double,
                               _fp, _u64, _fp, _fp, _fp, _fp]),                 # c1, c2, cells: HOST arrays
     "pnr_frame_from_hits": (_i32, [_fp, _i32, _fp, _i64, _i64, _f, _fp, _i32, _fp]),
+    "pnr_synth_render": (_i32, [_fp, _i32, _i32, _fp, _fp, _i32, _i32, _i32, _f, _f, _f, _f, _i32, _f, _f, _f, _f, _fp, _i64, _fp,
+                                _fp, _fp]),
     "pnr_event_create": (_i32, [C.POINTER(C.c_void_p)]),
     "pnr_event_record": (_i32, [_fp, _fp]),
     "pnr_event_elapsed_ms": (_i32, [_fp, _fp, C.POINTER(C.c_float)]),

@@ -11,7 +11,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpnr_hip.so")
 SOURCES = ["pnr_api.hip", "stage_kernels.hip", "point_f32.hip", "point_mfma.hip", "train_f32.hip", "cam_grad.hip", "loss.hip", "eval.hip",
            "mesh.hip", "optim.hip", "upsample.hip", "vis.hip", "video.hip", "data.hip", "jitter.hip", "train_draw.hip", "resize.hip",
-           "occupancy.hip", "mask_draw.hip", "opacity_loss.hip"]
+           "occupancy.hip", "mask_draw.hip", "opacity_loss.hip", "synth.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 

@@ -17,22 +17,28 @@ Another image_size.  The dataset classes read what the files hold and refuse a f
 new size, and ResizedDataset wraps any dataset so that its items come at that size (util.resize_area_u8, util.resize_area,
 util.resize_bbox, util.resize_intrinsics).
 """
+from . import synthetic
 from .dtu import ColorJitter, DTUDataset
 from .dvr import DVRDataset
 from .resident import ResidentSplit
 from .resized import ResizedDataset
 from .srn import SRNDataset
+from .synthetic import SyntheticShapes
 
-__all__ = ["get_split_dataset", "SRNDataset", "DVRDataset", "DTUDataset", "ColorJitter", "ResidentSplit", "ResizedDataset"]
+__all__ = ["get_split_dataset", "SRNDataset", "DVRDataset", "DTUDataset", "ColorJitter", "ResidentSplit", "ResizedDataset",
+           "SyntheticShapes"]
 
 
 def get_split_dataset(dataset_type, datadir, want_split="all", training=True, **kwargs):
     """The dataset(s) of one folder.  dataset_type "srn" -> SRNDataset, "dvr" -> DVRDataset, "dvr_gen" -> DVRDataset with the
-    "gen_" object lists, "dtu" -> DTUDataset; want_split "train" | "val" | "test" returns that one set, anything else the
+    "gen_" object lists, "dtu" -> DTUDataset, "synthetic" -> SyntheticShapes (no folder: datadir is ignored, n_objects is
+    required, and val / test default to max(1, n_objects // 8) objects; see synthetic.split); want_split "train" | "val" | "test" returns that one set, anything else the
     (train, val, test) triple.  kwargs go to the dataset class (image_size, world_scale, balanced, as_bytes, ...).  `training`
     is upstream's switch: for "dtu" it sets max_imgs=49 (a training item is a random 49 of a scan's views); the other types
     ignore it.  "dvr_dtu", upstream's name for the DTU sub-format, stays refused, because upstream reads it through cv2 and
     nothing here was compared against that: "dtu" is the working name of this package's own reading of the layout."""
+    if dataset_type == "synthetic":
+        return synthetic.split(want_split, **kwargs)
     if dataset_type == "srn":
         cls, flags = SRNDataset, {}
     elif dataset_type == "dvr":

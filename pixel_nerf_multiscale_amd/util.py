@@ -940,6 +940,44 @@ def image_to_tensor(img_u8, balanced=False, device="cuda"):
     return out
 
 
+# ------------------------------------------------------------------------------------------- procedural datasets
+def synth_render(scenes, scene_ids, poses, W, H, focal, c=None, *, ss=2, ambient=0.3, light=(0.3, 0.5, 0.8), out=None,
+                 mask_out=None, depth_out=None):
+    """F frames of analytic scenes, ray-cast on the GPU by libpnr_hip in ONE launch (pnr_synth_render; include/pnr.h writes the
+    scene records and every operation down).  scenes (n, P, 20) float32: P <= 8 primitive records per scene (kind, centre,
+    world -> local rotation, half-extents, albedo), data.synthetic.random_scenes or a hand-written table; scene_ids (F,) int32:
+    the scene of each frame (an index outside [0, n) gives a background frame); poses (F, 4, 4) float32 camera-to-world, the
+    convention of gen_rays; focal / c as intrinsics() takes them.  ss: 1, 2 or 4 sub-samples per pixel and axis; ambient in
+    [0, 1] and light, a direction fixed in the world, shade albedo * (ambient + (1 - ambient) * max(0, n . l)).
+    -> (rgb_u8 (F, H, W, 3), mask_u8 (F, H, W) or None, depth (F, H, W) float32 or None) on the device.  Background pixels are
+    255, 255, 255 with mask 0, and no channel of a foreground pixel is 255, so SRNDataset's rule reads the masks back from the
+    bytes; depth is the ray parameter at the pixel's first sub-sample (its centre for ss = 1), +inf where that one missed.
+    out: a contiguous uint8 (F, H, W, 3) to write into, at any byte offset of a larger buffer (a pool's slot).  mask_out /
+    depth_out: None = not wanted, True = allocated here, or a contiguous uint8 (F, H, W) / float32 (F, H, W) to write into.
+    Nothing here waits for the device."""
+    from . import _native as N
+    scenes = N.arg(scenes, "scenes", torch.float32, (None, None, N.PNR_SYNTH_REC), contiguous=True)
+    scene_ids = N.arg(scene_ids, "scene_ids", torch.int32, (None,), contiguous=True)
+    F, W, H = int(scene_ids.shape[0]), int(W), int(H)
+    poses = N.arg(poses, "poses", torch.float32, (F, 4, 4), contiguous=True)
+    if min(F, W, H) < 1:
+        raise ValueError(f"frames and image sizes must be positive, got F = {F}, W = {W}, H = {H}")
+    out = N.out(out, "out", torch.uint8, (F, H, W, 3), scenes.device)
+    if mask_out is not None:
+        mask_out = N.out(None if mask_out is True else mask_out, "mask_out", torch.uint8, (F, H, W), scenes.device)
+    if depth_out is not None:
+        depth_out = N.out(None if depth_out is True else depth_out, "depth_out", torch.float32, (F, H, W), scenes.device)
+    light = tuple(float(v) for v in light)
+    if len(light) != 3:
+        raise ValueError(f"light must be three numbers, got {light}")
+    dev = N.same_device(scenes, scene_ids, poses, out, mask_out, depth_out)
+    fx, fy, cx, cy = intrinsics(focal, c, W, H)
+    N.check(N.lib.pnr_synth_render(scenes.data_ptr(), int(scenes.shape[0]), int(scenes.shape[1]), scene_ids.data_ptr(),
+                                   poses.data_ptr(), F, W, H, fx, fy, cx, cy, int(ss), float(ambient), *light, out.data_ptr(),
+                                   3 * H * W, N.dptr(mask_out), N.dptr(depth_out), N.current_stream(dev)), "pnr_synth_render")
+    return out, mask_out, depth_out
+
+
 # ------------------------------------------------------------------------------------------- area resampling to an image_size
 def _target_size(size):
     """(Ht, Wt) of a `size` argument: a pair, or one int for a square target."""
